@@ -28,6 +28,10 @@ The JSON line also carries
   extras       : side numbers measured after the timed region (bounded): INT8 frames/s on the same workload, prompt-switch
                  (recache) latency, VAE decode frames/s, umT5 ms per prompt -- none of them is part of `value`
   cpu_baseline : the CPU oracle (a port of the reference's PyTorch path, oracle/) timed on this host on a bounded sample.
+
+`--dump-outputs DIR` writes what the last timed block returned to the caller of the stream -- its denoised latents
+(latents.npy, float32) and its first frame index (start_frame.npy) -- after the timed region.  Weights, noise, prompt and
+the re-noise draws are all seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -76,9 +80,26 @@ def parse(argv=None):
                          "their own roofline and cpu_baseline objects; single GPU, not the driver's metric")
     ap.add_argument("--quant", choices=["none", "int8"], default="none",
                     help="int8: W8A8 block linears (BASELINE config 5); the headline metric is the default bf16 path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (replica 0) as DIR/<name>.npy in float32; "
+                         "the inputs are seeded, so two builds run with the same arguments can be compared output for output")
     ap.add_argument("--stub-workload", action="store_true",
                     help=argparse.SUPPRESS)      # tests only: replaces the GPU body by a sleep (launcher / rank plumbing on CPU)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and args.workload != "dit":
+        ap.error("--dump-outputs covers the headline (dit) workload only")
+    return args
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Writes every tensor of `arrays` as out_dir/<name>.npy in float32 (float64 stays float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), (t if t.dtype == torch.float64 else t.float()).numpy())
 
 
 # ---- CPU baselines (the only place outside tests/ and smoke() that may run the oracle) --------------------------------
@@ -648,6 +669,7 @@ def run_replica(args, rank, world, local_rank, sync):
     # one independent stream per replica (inference.py:49,146: seed + rank, prompts sharded by rank)
     noise = synth.synth_noise(cfg, T, seed=rank, device=dev)
     prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=1 + rank, device=dev)}
+    torch.manual_seed(rank)           # the re-noise between denoising steps draws from torch's generator: same draws on every run
 
     stream = pipe.stream(noise, prompt)
     for _ in range(args.warmup):
@@ -664,12 +686,15 @@ def run_replica(args, rank, world, local_rank, sync):
         tele.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        next(stream)
+        start, latents = next(stream)
     torch.cuda.synchronize()
     sync.end_barrier()
     elapsed = time.perf_counter() - t0
     ops.timer = None
     telemetry = tele.stop(local_rank) if tele is not None else None
+    if args.dump_outputs and rank == 0:      # before the kernels-table block below advances the stream
+        # latents: the last timed block's denoised latents [1, 3, 16, 60, 104] (1.2 MB in float32)
+        dump_outputs(args.dump_outputs, {"latents": latents, "start_frame": torch.tensor([start], dtype=torch.float64)})
     res = dict(frames=args.steps * 3 * PIXEL_FRAMES_PER_LATENT, elapsed=elapsed, roofline=None, kernels=None, extras=None,
                cpu_baseline=None, overlap_context=bool(pipe.overlap_context), telemetry=telemetry,
                visible=os.environ.get("HIP_VISIBLE_DEVICES"))

@@ -106,13 +106,24 @@ def test_gemm_plan_names_the_kernel_family_a_call_takes():
         _lib.check(lib.ll_gemm_plan_epi(M, N, K, i8, epi, plain, buf, 256), "plan")
         return buf.value.decode()
 
+    # where the library sees a device, a launch with more tiles than CUs takes the persistent form (one workgroup per CU walks them)
+    import torch
+    cus = (torch.cuda.get_device_properties(0).multi_processor_count & ~7) if torch.cuda.is_available() else 0
+
+    def family(wn, tail, tiles):
+        if cus >= 8 and tiles > cus:
+            return f"gemm_asmp_{wn}_{tail}", f"{cus} persistent workgroups walk {tiles} tiles"
+        return f"gemm_asm_{wn}_{tail}", f"{tiles} workgroups"
+
     L, Cw, F1 = 4680, 1536, 8960
-    assert plan(L, F1, Cw, 0, 1, 1).startswith("gemm_asm_224_gelu")
-    assert plan(L, 3 * Cw, Cw, 0, 0, 2).startswith("gemm_asm_192_bias")            # fused QKV, one batch element
-    assert plan(L, Cw, Cw, 0, 2, 1).startswith("gemm_asm_128_gate_res")
-    assert plan(L, Cw, Cw, 0, 3, 1).startswith("gemm_asm_128_res")
-    assert plan(L, Cw, Cw, 0, 0, 1).startswith("gemm_asm_128_bias")
-    assert "760 workgroups" in plan(L, F1, Cw, 0, 1, 1) and "456 workgroups" in plan(L, 3 * Cw, Cw, 0, 0, 2)
+    for args, want in (((L, F1, Cw, 0, 1, 1), (224, "gelu", 760)),
+                       ((L, 3 * Cw, Cw, 0, 0, 2), (192, "bias", 456)),                # fused QKV, one batch element
+                       ((L, Cw, Cw, 0, 2, 1), (128, "gate_res", 228)),
+                       ((L, Cw, Cw, 0, 3, 1), (128, "res", 228)),
+                       ((L, Cw, Cw, 0, 0, 1), (128, "bias", 228))):
+        name, grid = family(*want)
+        text = plan(*args)
+        assert text.startswith(name) and grid in text, text
     for text in (plan(L, Cw, Cw, 1, 2, 1), plan(L, Cw, Cw, 0, 2, 0), plan(L, 1000, Cw, 0, 0, 1), plan(L, F1, 192, 0, 1, 1)):
         assert text.startswith("gemm_kernel_v"), text                                # int8; modulation vector; N % 128; K < 256
     assert lib.ll_gemm_plan_epi(L, Cw, Cw, 0, 0, 1, None, 0) == -1

@@ -13,7 +13,10 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 
 def _env(**kw):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LL_BENCH_CHILD")}
+    # an inherited device mask (a GPU machine that allots one device) would cap the stub launcher's replicas: the tests that need
+    # a mask set their own
+    drop = ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LL_BENCH_CHILD", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")
+    env = {k: v for k, v in os.environ.items() if k not in drop}
     env.update(kw)
     return env
 
@@ -95,3 +98,21 @@ def test_launcher_translates_ranks_through_the_inherited_device_mask():
                           "import sys; sys.path.insert(0, %r); import bench; print(bench.child_visibility({'HIP_VISIBLE_DEVICES': '4'}, 1, 2))" % ROOT],
                          capture_output=True, text=True, timeout=120)
     assert out.returncode != 0 and "inherited device mask" in out.stderr
+
+
+def test_dump_outputs_option(tmp_path):
+    """--dump-outputs DIR: the arrays are written as DIR/<name>.npy in float32 (float64 kept); the option is refused where there is
+    no headline output to write, and --steps must name at least one timed step."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path)
+    for bad in (["--steps", "0"], ["--workload", "vae", "--dump-outputs", str(tmp_path)]):
+        out = subprocess.run([sys.executable, BENCH] + bad, env=_env(), capture_output=True, text=True, timeout=120)
+        assert out.returncode != 0 and "error" in out.stderr, bad
+    x = torch.randn(1, 3, 16, 6, 10).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "d"), {"latents": x, "start_frame": torch.tensor([12.0], dtype=torch.float64)})
+    got = np.load(tmp_path / "d" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    assert np.load(tmp_path / "d" / "start_frame.npy").dtype == np.float64
