@@ -44,7 +44,7 @@ enum ll_epilogue {
  * (longlive_amd/_lib.py) and any other caller must find ll_version() == LL_ABI_VERSION or refuse the library: a stale .so would
  * otherwise shift `stream` and the pointers silently.  100 = rounds 1-3; 105 = round 4's removals (workspace arguments of
  * ll_flash_attn, the split-K hand-off entry points); 106 = round 5 (ll_conv_cl_rms added). */
-#define LL_ABI_VERSION 106
+#define LL_ABI_VERSION 107
 int ll_version(void);
 const char* ll_last_error(void);
 /* Development knob for A/B timing of kernel variants (tools/kbench, tools/kenergy, LL_TUNING=key=value,... for bench.py);
@@ -190,6 +190,33 @@ int ll_gemm_w8a8_qkv(const int8_t* xq, const float* sx, const int8_t* wq, const 
 /* Symmetric per-row int8 quantisation: scale[r] = max|x[r,:]| / 127 (1 for an all-zero row), q = rint(x / scale).
  * Per token for activations, per output channel for weights ([N,K] rows), x row stride ldx elements. */
 int ll_quantize_rows(const ll_bf16* x, int8_t* q, float* scale, int rows, int K, int ldx, ll_stream stream);
+
+/* MXFP8 mode of the block linears (v_mfma_scale_f32_16x16x128_f8f6f4, both operands OCP e4m3fn).  A row is quantised along K in
+ * blocks of 32: amax = m 2^p (frexp), e = p - 9 + (m > 0.875) clamped to [-127, 127] (the smallest e with amax <= 448 2^e), scale
+ * byte e + 127 (E8M0; an all-zero block stores 127), codes e4m3fn(RNE(x 2^-e)) with subnormals kept.  Codes [rows, K] (1 byte each),
+ * scales [rows, K / 32] (uint8), row-major.
+ *   ll_quantize_mx: bf16 rows (stride ldx elements) -> codes + scales, one launch; K % 32 == 0.
+ *   ll_gemm_mx:     out = epilogue(sum_k (cx 2^ex)(cw 2^ew) + bias) with ll_gemm_bf16's epilogues and rounding points; K % 128 == 0.
+ *                   With the GELU epilogue, q_out / s_out (instead of out) receive the MX codes + scales of the bf16 GELU output
+ *                   (N % 32 == 0, ldo == N), bit-identical to ll_quantize_mx of the bf16 result.  Exactly one form is given.
+ *   ll_gemm_mx_qkv: ll_gemm_bf16_qkv's fused q|k|v projection (V third into cache_v) on MX operands.
+ *   ll_ln_modulate_mx / ll_ln_modulate_tab_mx / ll_layernorm_affine_mx: the producers of the same names emitting MX codes + scales
+ *                   of their bf16 output (bit-identical to ll_quantize_mx of it); C % 32 == 0.
+ *   ll_gemm_plan_mx: kernel instance, tile and grid of an ll_gemm_mx / ll_gemm_mx_qkv call (host only). */
+int ll_quantize_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, int rows, int K, int ldx, ll_stream stream);
+int ll_gemm_mx(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+               uint8_t* q_out, uint8_t* s_out, int M, int N, int K, int ldo, int epilogue, const ll_bf16* res, const ll_bf16* e,
+               const ll_bf16* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len, ll_stream stream);
+int ll_gemm_mx_qkv(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                   int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset,
+                   int write_len, ll_stream stream);
+int ll_ln_modulate_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod, int shift_idx,
+                      int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_ln_modulate_tab_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx, int scale_idx,
+                          int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_layernorm_affine_mx(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
+                           float eps, ll_stream stream);
+int ll_gemm_plan_mx(int M, int N, int K, char* out, int cap);
 
 /* Small-M linear (M <= 8): out = act_out(act_in(x) @ w^T + b); act: 0 none, 1 SiLU.  time_embedding /
  * time_projection (wan/modules/causal_model.py:605-608,976-979). */

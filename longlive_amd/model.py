@@ -132,7 +132,8 @@ class CausalWanModelHIP(nn.Module):
         self.num_frame_per_block = 1
         self.block_mask = None
         # None: bf16 linears (the reference's precision).  "int8": W8A8 for the six per-token linears of every block
-        # (BASELINE config 5; per-token activation scales, per-output-channel weight scales, int32 accumulation).
+        # (BASELINE config 5; per-token activation scales, per-output-channel weight scales, int32 accumulation).  "mxfp8": the same
+        # six on the block-scaled e4m3 MFMA (one power-of-two scale per 32 elements of K for activations and weights alike).
         self.quant: Optional[str] = None
         self.use_modulation_table = True      # modulation + e0 once per (layer, frame) instead of once per token row (A/B switch)
         self.fuse_v_insert = True             # the QKV projection's epilogue writes V into the KV cache (A/B switch)
@@ -186,7 +187,7 @@ class CausalWanModelHIP(nn.Module):
         for blk in self.blocks:
             sa = blk.self_attn
             ts = [sa.q.weight, sa.k.weight, sa.v.weight, sa.q.bias, sa.k.bias, sa.v.bias, blk.modulation]
-            if self.quant == "int8":
+            if self.quant in ("int8", "mxfp8"):
                 ts += [sa.o.weight, blk.cross_attn.q.weight, blk.cross_attn.o.weight, blk.ffn[0].weight, blk.ffn[2].weight]
             key.extend((t.data_ptr(), t._version) for t in ts)
         return tuple(key)
@@ -204,10 +205,11 @@ class CausalWanModelHIP(nn.Module):
                 bqkv=torch.cat([sa.q.bias, sa.k.bias, sa.v.bias], 0).contiguous(),
                 mod=blk.modulation.detach().reshape(6, -1).contiguous(),
             )
-            if self.quant == "int8":
+            if self.quant is not None:
+                quantize = ops.quantize_rows if self.quant == "int8" else ops.quantize_mx
                 for name, w in (("qkv", d["wqkv"]), ("o", sa.o.weight), ("cq", ca.q.weight), ("co", ca.o.weight),
                                 ("f1", blk.ffn[0].weight), ("f2", blk.ffn[2].weight)):
-                    d["q_" + name], d["s_" + name] = ops.quantize_rows(w.detach().contiguous())
+                    d["q_" + name], d["s_" + name] = quantize(w.detach().contiguous())
             P.append(d)
         self._packed = P
         self._mods = torch.stack([d["mod"] for d in P], 0).contiguous()      # [NL, 6, C] for ops.modulation_table
@@ -215,18 +217,23 @@ class CausalWanModelHIP(nn.Module):
         return P
 
     def set_quant(self, mode: Optional[str]):
-        """None (bf16) or "int8" (W8A8 block linears).  Weights are (re)quantised lazily at the next forward."""
-        if mode not in (None, "int8"):
+        """None (bf16), "int8" (W8A8 block linears) or "mxfp8" (MXFP8 block linears).  Weights are (re)quantised lazily at the
+        next forward."""
+        if mode not in (None, "int8", "mxfp8"):
             raise ValueError(f"unknown quantisation mode {mode!r}")
-        if mode == "int8" and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
-            raise ValueError("int8 linears need dim and ffn_dim to be multiples of 128")
+        if mode is not None and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
+            raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 128")
         self.quant = mode
         self._packed = None
         return self
 
     def _lin(self, x, pk, key, w, b, epilogue=0, **kw):
         """One block linear: bf16 MFMA GEMM, or W8A8 GEMM in int8 mode (same fused epilogues).  In int8 mode `x` is either
-        a bf16 tensor (quantised here, per token) or an already quantised (int8, scale) pair from a fused producer."""
+        a bf16 tensor (quantised here, per token) or an already quantised (int8, scale) pair from a fused producer; in mxfp8 mode
+        likewise a bf16 tensor or an (e4m3 codes, block scales) pair."""
+        if self.quant == "mxfp8":
+            xm = x if isinstance(x, tuple) else ops.quantize_mx(x)
+            return ops.gemm_mx(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
         if self.quant == "int8":
             xq, sx = x if isinstance(x, tuple) else ops.quantize_rows(x)
             return ops.gemm_w8a8(xq, sx, pk["q_" + key], pk["s_" + key], b, epilogue, tag="gemm_" + key, **kw)
@@ -324,18 +331,24 @@ class CausalWanModelHIP(nn.Module):
         sa, ca = blk.self_attn, blk.cross_attn
         # --- self attention (causal_model.py:444-456) ---
         q8 = self.quant == "int8"
+        mx = self.quant == "mxfp8"
         G, E = _kv_state(kvc)
         S = kvc["k"].shape[1]
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
                            sa.max_attention_size, sink_recache_after_switch)
         if plan.roll is not None:          # before the projection: its epilogue writes V into the rolled window
             ops.kv_roll(kvc["k"], kvc["v"], *plan.roll)
-        if tab32 is not None:
+        if mx:
+            h1 = ops.ln_modulate_tab_mx(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 0, 1, F, c.eps)
+        elif tab32 is not None:
             h1 = ops.ln_modulate_tab(xs, tab32, 0, 1, F, c.eps, q8=q8)
         else:
             h1 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 0, 1, F, c.eps)
         if self.fuse_v_insert:             # V third of the projection goes straight into its cache slots (GEMM epilogue)
-            if q8:
+            if mx:
+                qkv = ops.gemm_mx_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
+                                               plan.roped_offset, plan.write_len, B, L)
+            elif q8:
                 qkv = ops.gemm_qkv_v_insert(None, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
                                             plan.roped_offset, plan.write_len, xq=h1)
             else:
@@ -360,8 +373,9 @@ class CausalWanModelHIP(nn.Module):
         self._lin(att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=2, rows_per_batch=L, frame_len=fs)
         # --- cross attention (causal_model.py:460; model.py:159-194) ---
-        xn = (ops.layernorm_affine_q8 if q8 else ops.layernorm_affine)(xs, blk.norm3.weight, blk.norm3.bias, c.eps)
-        fuse_qn = (self.fuse_cross_qnorm and not q8 and ops.gemm_ssq_planes(B * L, C, C) == Hh and ops.flash_attn_qnorm_ok(Hh, c.text_len))
+        xn = (ops.layernorm_affine_mx if mx else ops.layernorm_affine_q8 if q8 else ops.layernorm_affine)(xs, blk.norm3.weight,
+                                                                                                           blk.norm3.bias, c.eps)
+        fuse_qn = (self.fuse_cross_qnorm and self.quant is None and ops.gemm_ssq_planes(B * L, C, C) == Hh and ops.flash_attn_qnorm_ok(Hh, c.text_len))
         if fuse_qn:
             qraw, ssq = ops.gemm_ssq(xn, ca.q.weight, ca.q.bias, tag="gemm_cq_ssq")
         else:
@@ -380,11 +394,14 @@ class CausalWanModelHIP(nn.Module):
             atc = ops.flash_attn(qc.view(B, L, Hh, D), cac["k"], cac["v"], [(0, c.text_len)], tag="flash_attn_cross")
         self._lin(atc.view(B, L, C), pk, "co", ca.o.weight, ca.o.bias, ops.EPI_BIAS_RES, out=xs, res=xs)
         # --- FFN (causal_model.py:462-468) ---
-        if tab32 is not None:
+        if mx:
+            h2 = ops.ln_modulate_tab_mx(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 3, 4, F, c.eps)
+        elif tab32 is not None:
             h2 = ops.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps, q8=q8)
         else:
             h2 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 3, 4, F, c.eps)
-        ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU)
+        # (mxfp8: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
+        ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU, **(dict(mx_out=True) if mx else {}))
         self._lin(ff, pk, "f2", blk.ffn[2].weight, blk.ffn[2].bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=5, rows_per_batch=L, frame_len=fs)
         return plan

@@ -1,0 +1,98 @@
+"""Frames/s of the three block-linear precisions (none = bf16, int8 = W8A8, mxfp8 = MXFP8), alternated in one process.
+
+Workload = bench.py's fps_of: the LongLive-1.3B random-init generator, config 2's steady state (4 warm-up blocks, then timed blocks
+through pipe.stream).  The modes run in turn for --rounds rounds, so a clock drift of the device lands on all of them alike; the
+record holds the median frames/s, ms per block and average GPU clock per mode, and a per-kernel table of one extra (timed-launch)
+MXFP8 pass with the MX GEMM plan strings.
+
+    python tools/quant_fps.py --rounds 3 --blocks 4 --out profiles/quant_fps.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MODES = ("none", "int8", "mxfp8")
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--blocks", type=int, default=4)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+
+    import torch
+    import bench
+    from longlive_amd import _lib, ops, synth
+    from longlive_amd.pipeline import CausalInferencePipeline
+    from longlive_amd.wan_wrapper import WanDiffusionWrapper
+
+    _lib.load()
+    dev = torch.device("cuda", 0)
+    cfg = synth.longlive_1_3b(local_attn_size=12, sink_size=3)
+    gen = WanDiffusionWrapper(timestep_shift=5.0, local_attn_size=12, sink_size=3, cfg=cfg, device=dev,
+                              state_dict=synth.synth_state_dict(cfg, seed=0, device=dev))
+    prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=1, device=dev)}
+
+    def run(mode, blocks, timer=None):
+        gen.model.set_quant(None if mode == "none" else mode)
+        pipe = CausalInferencePipeline(bench._pipe_args(), dev, generator=gen)
+        st = pipe.stream(synth.synth_noise(cfg, 3 * (4 + blocks), seed=0, device=dev), prompt)
+        for _ in range(4):
+            next(st)
+        torch.cuda.synchronize()
+        tel = bench.Telemetry(0)
+        tel.start()
+        ops.timer = timer
+        t0 = time.perf_counter()
+        for _ in range(blocks):
+            next(st)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        ops.timer = None
+        clk = tel.stop(0).get("sclk_mhz_avg")
+        return dict(fps=12 * blocks / dt, ms_per_block=1e3 * dt / blocks, sclk_mhz=clk)
+
+    rows = {m: [] for m in MODES}
+    for r in range(args.rounds):
+        for m in MODES:
+            rows[m].append(run(m, args.blocks))
+            print(f"round {r} {m:6s}: {rows[m][-1]['fps']:.2f} frames/s, {rows[m][-1]['ms_per_block']:.1f} ms/block, "
+                  f"sclk {rows[m][-1]['sclk_mhz']}", flush=True)
+    med = {}
+    for m in MODES:
+        clks = [x["sclk_mhz"] for x in rows[m] if x["sclk_mhz"] is not None]
+        med[m] = dict(fps=statistics.median(x["fps"] for x in rows[m]), ms_per_block=statistics.median(x["ms_per_block"] for x in rows[m]),
+                      sclk_mhz=statistics.median(clks) if clks else None)
+
+    timer = ops.KernelTimer()
+    run("mxfp8", 1, timer)
+    torch.cuda.synchronize()
+    summ = timer.summary()
+    kernels = {t: dict(launches=v["launches"], avg_us=1e3 * v["avg_ms"], total_ms=v["total_ms"]) for t, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])}
+    M = 3 * cfg.frame_seqlen
+    plans = {name: ops.gemm_plan_mx(M, n, k) for name, n, k in (("gemm_qkv", 3 * cfg.dim, cfg.dim), ("gemm_o / gemm_cq / gemm_co", cfg.dim, cfg.dim),
+                                                                 ("gemm_f1", cfg.ffn_dim, cfg.dim), ("gemm_f2", cfg.dim, cfg.ffn_dim))}
+    gen.model.set_quant(None)
+    rec = dict(tool="tools/quant_fps.py", device=torch.cuda.get_device_name(0), rounds=args.rounds, blocks=args.blocks,
+               workload="bench.py fps_of: LongLive-1.3B random-init, config 2 steady state, 4 warm-up blocks, timed blocks via pipe.stream",
+               median=med, runs=rows, mxfp8_kernels_one_block=kernels, mxfp8_gemm_plans=plans)
+    print(json.dumps(dict(median=med)), flush=True)
+    for t, v in kernels.items():
+        print(f"  {t:28s} {v['launches']:5d} launches  {v['avg_us']:9.1f} us avg  {v['total_ms']:8.2f} ms")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
