@@ -43,8 +43,9 @@ enum ll_epilogue {
 /* ABI version of this header.  Any change to an existing signature or the removal of an entry point bumps it; the Python binding
  * (longlive_amd/_lib.py) and any other caller must find ll_version() == LL_ABI_VERSION or refuse the library: a stale .so would
  * otherwise shift `stream` and the pointers silently.  100 = rounds 1-3; 105 = round 4's removals (workspace arguments of
- * ll_flash_attn, the split-K hand-off entry points); 106 = round 5 (ll_conv_cl_rms added). */
-#define LL_ABI_VERSION 107
+ * ll_flash_attn, the split-K hand-off entry points); 106 = round 5 (ll_conv_cl_rms added); 107 = MXFP8 block linears;
+ * 108 = MXFP8 self-attention (ll_kv_shadow_mx, ll_flash_attn_mx, ll_flash_attn_mx_plan). */
+#define LL_ABI_VERSION 108
 int ll_version(void);
 const char* ll_last_error(void);
 /* Development knob for A/B timing of kernel variants (tools/kbench, tools/kenergy, LL_TUNING=key=value,... for bench.py);
@@ -217,6 +218,28 @@ int ll_ln_modulate_tab_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float
 int ll_layernorm_affine_mx(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
                            float eps, ll_stream stream);
 int ll_gemm_plan_mx(int M, int N, int K, char* out, int cap);
+
+/* MXFP8 self-attention (set_attn_quant("mxfp8")) over a block-scaled SHADOW of one layer's bf16 KV cache k, v [B, S, H, 128]; the bf16
+ * cache stays the master, S32 = S rounded up to a multiple of 32.  MX rule as ll_quantize_mx.
+ *   K^: codes kq [B, S32, H, 128] e4m3fn + scales ks [B, S32, H, 4]: each slot's K row quantised along channels (ll_quantize_mx of it).
+ *   V^: codes vq [B, H, S32 / 32, 128, 32] + scales vs [B, H, S32 / 32, 128]: per (head, channel d, slots 32 j .. 32 j + 31) the MX rule
+ *       over the 32 values V[32 j + i, head, d] (slots >= S read as 0); code position 16 hh + jj of a row holds slot
+ *       32 j + (jj & 3) + 8 (jj >> 2) + 4 hh (the order in which the kernel's score registers arrive).
+ *   ll_kv_shadow_mx: re-derives K^ rows and V^ blocks of the slots [lo, hi), widened to whole 32-slot blocks.  It follows every write
+ *       of the cache in block_forward (the QKV epilogue's V insert and qk_norm_rope_kv_store's K insert, causal_model.py:264-269,302-311;
+ *       ll_kv_roll, :257-260) and any external change of k / v (the pipelines' in-place zero_ before a recache).
+ *   ll_flash_attn_mx: ll_flash_attn's self-attention (wan/modules/attention.py:43-197 over the sink/window of causal_model.py:331-360)
+ *       on v_mfma_scale_f32_32x32x64_f8f6f4: q [B, Lq, H*128] (row stride ldq) quantised per row in the kernel's prologue,
+ *       s = sum_b 2^(eq + ek) sum q^ k^ in fp32, P^ = e4m3fn(exp2(c s - c m_ref)) with the lazy max (m_ref moves only when a tile's max
+ *       exceeds it by more than 8 / c), O = sum P^ V^ / sum P^ written as bf16 (row stride ldo).  Key tiles of 64 slots start at each
+ *       range's start rounded down to 32 (adjacent ranges are merged first); slots outside the ranges are masked.  head_dim must be 128.
+ *   ll_flash_attn_mx_plan: kernel, tile and grid of an ll_flash_attn_mx call (host only). */
+int ll_kv_shadow_mx(const ll_bf16* k, const ll_bf16* v, uint8_t* kq, uint8_t* ks, uint8_t* vq, uint8_t* vs, int B, int S, int S32, int H,
+                    int head_dim, int lo, int hi, ll_stream stream);
+int ll_flash_attn_mx(const ll_bf16* q, const uint8_t* kq, const uint8_t* ks, const uint8_t* vq, const uint8_t* vs, ll_bf16* out, int B,
+                     int Lq, int H, int head_dim, int ldq, int ldo, int S, int S32, int seg0_start, int seg0_len, int seg1_start,
+                     int seg1_len, float scale, ll_stream stream);
+int ll_flash_attn_mx_plan(int Lq, int H, int B, int seg0_start, int seg0_len, int seg1_start, int seg1_len, char* out, int cap);
 
 /* Small-M linear (M <= 8): out = act_out(act_in(x) @ w^T + b); act: 0 none, 1 SiLU.  time_embedding /
  * time_projection (wan/modules/causal_model.py:605-608,976-979). */

@@ -305,6 +305,17 @@ def quant_mode(value) -> Optional[str]:
     return None if v == "none" else v
 
 
+ATTN_QUANT_MODES = ("none", "mxfp8")
+
+
+def attn_quant_mode(value) -> Optional[str]:
+    """The yaml's `attn_quant:` key (none | mxfp8, default none) as CausalWanModelHIP.set_attn_quant's argument."""
+    v = "none" if value is None else str(value).strip().lower()
+    if v not in ATTN_QUANT_MODES:
+        raise ValueError(f"attn_quant: {value!r} is not one of {', '.join(ATTN_QUANT_MODES)}")
+    return None if v == "none" else v
+
+
 def _dist_env():
     if "LOCAL_RANK" in os.environ:
         lr = int(os.environ["LOCAL_RANK"])
@@ -324,6 +335,7 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     synthetic = synthetic or bool(config.get("synthetic", False))
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
     gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8 or MXFP8
+    gen.model.set_attn_quant(attn_quant_mode(config.get("attn_quant", "none")))   # self-attention: bf16 or MXFP8
     interactive = mode == "interactive"
     cls = InteractiveCausalInferencePipeline if interactive else CausalInferencePipeline
     pipeline = cls(config, device, generator=gen, text_encoder=enc, vae=vae)

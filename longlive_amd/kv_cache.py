@@ -67,3 +67,28 @@ def plan_update(current_start: int, num_new: int, G: int, E: int, cache_size: in
         segments = [(max(0, local_end - max_attention_size), local_end)]
     return KVPlan(current_end, is_recompute, roll, local_start, local_end, write_start, roped_offset, write_len,
                   segments, G if is_recompute else current_end, E if is_recompute else local_end)
+
+
+def shadow_refresh_ranges(plan: KVPlan, stale: bool, cache_size: int) -> List[Tuple[int, int]]:
+    """Slot ranges [lo, hi) whose MX attention shadow (ops.kv_shadow_mx) block_forward re-derives after this layer's cache writes,
+    so that every slot the layer's attention reads -- and every slot a later forward reads without writing it first -- carries
+    the bits of its current bf16 value.  stale: the shadow is new, or k / v were changed outside the model (an in-place zero_ /
+    copy_ bumps their version counter, a new tensor changes the data pointer or shape): all of it is re-derived.  Otherwise
+    only what this forward wrote: the rolled window (causal_model.py:257-260) and the inserted tokens (:264-269,302-311).
+    Adjacent or overlapping ranges are merged (one launch each)."""
+    if stale:
+        return [(0, cache_size)]
+    rs = []
+    if plan.roll is not None:
+        dst, _, n = plan.roll
+        rs.append((dst, dst + n))
+    if plan.write_len > 0:
+        rs.append((plan.write_start, plan.write_start + plan.write_len))
+    rs.sort()
+    out: List[Tuple[int, int]] = []
+    for lo, hi in rs:
+        if out and lo <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], hi))
+        else:
+            out.append((lo, hi))
+    return out

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .kv_cache import KVPlan, plan_update
+from .kv_cache import KVPlan, plan_update, shadow_refresh_ranges
 from .synth import WanConfig
 
 bf16 = torch.bfloat16
@@ -71,6 +71,16 @@ class _Conv(nn.Module):
         self.weight = nn.Parameter(torch.zeros(cfg.dim, cfg.in_dim, *cfg.patch_size, device=device, dtype=dtype),
                                    requires_grad=False)
         self.bias = nn.Parameter(torch.zeros(cfg.dim, device=device, dtype=dtype), requires_grad=False)
+
+
+_MX_SHADOW = "_ll_mx"      # a layer's cache dict in MX attention mode: the block-scaled shadow of k / v (ops.kv_shadow_mx_alloc)
+
+
+def mx_shadow_key(k: torch.Tensor, v: torch.Tensor) -> tuple:
+    """What the MX shadow of a layer's k / v was derived from: data pointers, shape and version counters.  An outside in-place write
+    (zero_, copy_) bumps a version, a new tensor changes a pointer or the shape; the model's own writes go through the C ABI and
+    change none of them."""
+    return (k.data_ptr(), v.data_ptr(), tuple(k.shape), k._version, v._version)
 
 
 def _idx_versions(cache: dict):
@@ -135,6 +145,9 @@ class CausalWanModelHIP(nn.Module):
         # (BASELINE config 5; per-token activation scales, per-output-channel weight scales, int32 accumulation).  "mxfp8": the same
         # six on the block-scaled e4m3 MFMA (one power-of-two scale per 32 elements of K for activations and weights alike).
         self.quant: Optional[str] = None
+        # None: bf16 self-attention.  "mxfp8": self-attention on the block-scaled e4m3 MFMA over an MX shadow of each layer's KV cache
+        # (kept in the cache dict under _MX_SHADOW, re-derived after every write; orthogonal to `quant`).
+        self.attn_quant: Optional[str] = None
         self.use_modulation_table = True      # modulation + e0 once per (layer, frame) instead of once per token row (A/B switch)
         self.fuse_v_insert = True             # the QKV projection's epilogue writes V into the KV cache (A/B switch)
         self.use_modulation_f32 = True        # LN + modulate from the fp32 table (1 + scale, shift: ops.modulation_table_f32) beside the
@@ -226,6 +239,28 @@ class CausalWanModelHIP(nn.Module):
         self.quant = mode
         self._packed = None
         return self
+
+    def set_attn_quant(self, mode: Optional[str]):
+        """None (bf16 self-attention) or "mxfp8" (MXFP8 self-attention over a block-scaled shadow of the KV cache).
+        Independent of set_quant; cross-attention stays bf16 in every mode."""
+        if mode not in (None, "mxfp8"):
+            raise ValueError(f"unknown attention quantisation mode {mode!r}")
+        if mode is not None and self.cfg.head_dim != 128:
+            raise ValueError("MX attention needs head_dim 128")
+        self.attn_quant = mode
+        return self
+
+    @staticmethod
+    def _mx_shadow(kvc: dict):
+        """(shadow, stale) of a layer's cache: allocated at the first MX forward; stale when it is new or k / v changed outside the
+        model since the last refresh (version counter, data pointer or shape: our own writes go through the C ABI and bump nothing)."""
+        k = kvc["k"]
+        sh = kvc.get(_MX_SHADOW)
+        if sh is None or sh["kq"].shape[0] != k.shape[0] or sh["S"] != k.shape[1] or sh["kq"].shape[2] != k.shape[2]:
+            sh = ops.kv_shadow_mx_alloc(k)
+            sh["key"] = None
+            kvc[_MX_SHADOW] = sh
+        return sh, sh["key"] != mx_shadow_key(k, kvc["v"])
 
     def _lin(self, x, pk, key, w, b, epilogue=0, **kw):
         """One block linear: bf16 MFMA GEMM, or W8A8 GEMM in int8 mode (same fused epilogues).  In int8 mode `x` is either
@@ -336,6 +371,11 @@ class CausalWanModelHIP(nn.Module):
         S = kvc["k"].shape[1]
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
                            sa.max_attention_size, sink_recache_after_switch)
+        amx = self.attn_quant == "mxfp8"
+        if amx:
+            shadow, stale = self._mx_shadow(kvc)
+        else:
+            kvc.pop(_MX_SHADOW, None)      # bf16 writes from here on are not mirrored: a later MX forward starts from a new shadow
         if plan.roll is not None:          # before the projection: its epilogue writes V into the rolled window
             ops.kv_roll(kvc["k"], kvc["v"], *plan.roll)
         if mx:
@@ -361,13 +401,20 @@ class CausalWanModelHIP(nn.Module):
         ops.qk_norm_rope_kv_store(qkv, sa.norm_q.weight, sa.norm_k.weight, rope_f, rope_hw, q_buf.view(B, L, C),
                                   kvc["k"], v_dst, D, fs, current_start // fs, plan.write_start,
                                   plan.roped_offset, plan.write_len, c.eps)
+        if amx:                            # the shadow follows the roll and the insert (or all of the cache after an outside change)
+            for lo, hi in shadow_refresh_ranges(plan, stale, S):
+                ops.kv_shadow_mx(kvc["k"], kvc["v"], shadow, lo, hi, tag="kv_shadow_mx_co" if co_running else "kv_shadow_mx")
+            shadow["key"] = mx_shadow_key(kvc["k"], kvc["v"])
         if kv_insert_only:
             if cache_done_event is not None:
                 cache_done_event.record(torch.cuda.current_stream())
             return plan
         # (a forward that runs beside another one on a second stream -- the pipelines' context-pass overlap -- times its launches
         #  under another tag: bench.py's roofline describes the kernel running alone on the device)
-        att = ops.flash_attn(q_buf, kvc["k"], kvc["v"], plan.segments, tag="flash_attn_self_co" if co_running else "flash_attn_self")
+        if amx:
+            att = ops.flash_attn_mx(q_buf, shadow, plan.segments, tag="flash_attn_self_mx_co" if co_running else "flash_attn_self_mx")
+        else:
+            att = ops.flash_attn(q_buf, kvc["k"], kvc["v"], plan.segments, tag="flash_attn_self_co" if co_running else "flash_attn_self")
         if cache_done_event is not None:
             cache_done_event.record(torch.cuda.current_stream())
         self._lin(att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,

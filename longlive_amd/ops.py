@@ -936,3 +936,75 @@ def gemm_plan_mx(M: int, N: int, K: int) -> str:
     buf = ctypes.create_string_buffer(256)
     _lib.check(_lib.load().ll_gemm_plan_mx(M, N, K, buf, 256), "ll_gemm_plan_mx")
     return buf.value.decode()
+
+
+# ---- MXFP8 self-attention over a block-scaled shadow of the KV cache (attention_mx.hip) ------------------------------------------
+def kv_shadow_mx_alloc(cache_k) -> dict:
+    """Uninitialised MX shadow of one layer's cache k (or v) [B, S, H, 128]: K^ codes [B, S32, H, 128] + scales [B, S32, H, 4],
+    V^ codes [B, H, S32 / 32, 128, 32] + scales [B, H, S32 / 32, 128] (include/longlive_hip.h ll_kv_shadow_mx)."""
+    _chk(cache_k, "cache_k")
+    B, S, H, D = cache_k.shape
+    assert D == 128, "the shadow is specialised for head_dim 128"
+    S32 = (S + 31) // 32 * 32
+    dev = cache_k.device
+    return dict(kq=torch.empty(B, S32, H, D, dtype=fp8, device=dev), ks=torch.empty(B, S32, H, 4, dtype=u8, device=dev),
+                vq=torch.empty(B, H, S32 // 32, D, 32, dtype=fp8, device=dev), vs=torch.empty(B, H, S32 // 32, D, dtype=u8, device=dev),
+                S=S)
+
+
+def kv_shadow_mx(cache_k, cache_v, shadow: dict, lo: int, hi: int, tag: str = "kv_shadow_mx"):
+    """Re-derive the shadow of cache slots [lo, hi) (widened to whole 32-slot blocks) from the bf16 cache.  Replaces nothing in
+    the reference: it follows the cache writes of causal_model.py:257-311 in MX attention mode."""
+    _chk(cache_k, "cache_k"); _chk(cache_v, "cache_v")
+    B, S, H, D = cache_k.shape
+    assert cache_v.shape == cache_k.shape and shadow["S"] == S and shadow["kq"].shape[:1] == (B,), (cache_k.shape, shadow["kq"].shape)
+    S32 = shadow["kq"].shape[1]
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_kv_shadow_mx(cache_k.data_ptr(), cache_v.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(),
+                                   shadow["vq"].data_ptr(), shadow["vs"].data_ptr(), B, S, S32, H, D, int(lo), int(hi), _stream()),
+               "ll_kv_shadow_mx")
+    n = ((int(hi) + 31) // 32 - int(lo) // 32) * 32
+    _t1(tag, t0, 2.0 * B * n * H * D * (2 + 1))         # bytes: k and v read (bf16), codes written
+
+
+def _segs2(segments, S):
+    segs = [(int(a), int(b)) for a, b in segments if b > a]
+    assert 1 <= len(segs) <= 2, segments
+    for a, b_ in segs:
+        assert 0 <= a < b_ <= S, (segments, S)
+    (s0, e0) = segs[0]
+    (s1, e1) = segs[1] if len(segs) == 2 else (0, 0)
+    return s0, e0, s1, e1
+
+
+def flash_attn_mx(q, shadow: dict, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None):
+    """flash_attn over the MX shadow of the cache: q [B,Lq,H,128] bf16 (quantised per row in the kernel), keys = up to two slot
+    ranges [(start, end), ...].  Returns [B,Lq,H,128] bf16."""
+    _chk(q, "q")
+    B, Lq, H, D = q.shape
+    assert D == 128, "kernel is specialised for head_dim 128"
+    S, S32 = shadow["S"], shadow["kq"].shape[1]
+    assert shadow["kq"].shape == (B, S32, H, D) and shadow["vq"].shape == (B, H, S32 // 32, D, 32), (q.shape, shadow["kq"].shape)
+    s0, e0, s1, e1 = _segs2(segments, S)
+    out = torch.empty_like(q) if out is None else _chk(out, "out")
+    assert out.shape == q.shape
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    lib = _lib.load()
+    tag = tag or "flash_attn_mx"
+    t0 = _t0(tag)
+    _lib.check(lib.ll_flash_attn_mx(q.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(), shadow["vq"].data_ptr(),
+                                    shadow["vs"].data_ptr(), out.data_ptr(), B, Lq, H, D, H * D, H * D, S, S32, s0, e0 - s0, s1, e1 - s1,
+                                    scale, _stream()), "ll_flash_attn_mx")
+    _t1(tag, t0, 4.0 * B * H * Lq * ((e0 - s0) + (e1 - s1)) * D)     # algorithmic FLOPs: QK^T + PV
+    return out
+
+
+def flash_attn_mx_plan(Lq: int, H: int, B: int, segments) -> str:
+    """Kernel, tile and grid of a flash_attn_mx call (host only)."""
+    import ctypes
+    s0, e0, s1, e1 = _segs2(segments, 1 << 30)
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().ll_flash_attn_mx_plan(Lq, H, B, s0, e0 - s0, s1, e1 - s1, buf, 256), "ll_flash_attn_mx_plan")
+    return buf.value.decode()

@@ -1,0 +1,166 @@
+"""Host restatement of MXFP8 self-attention over the block-scaled shadow of the KV cache (include/longlive_hip.h ll_kv_shadow_mx /
+ll_flash_attn_mx).  The MX rule is tests/mx_ref.py's.
+
+  * Q^: every query row (bf16, after RMSNorm + RoPE) quantised in blocks of 32 channels (= ll_quantize_mx of the row);
+  * K^ shadow: every cache slot's K row the same way: codes [B, S32, H, 128], scales [B, S32, H, 4] (S32 = S rounded up to 32);
+  * V^ shadow: per (head, channel d, slot block j = slots 32 j .. 32 j + 31) the MX rule over V[32 j + i, head, d], slots >= S read
+    as 0; codes [B, H, S32 / 32, 128, 32] with position 16 hh + jj holding slot 32 j + frag(jj, hh), scales [B, H, S32 / 32, 128];
+  * scores s = sum_b 2^(eq + ek) sum q^ k^ in fp32; key tiles of 64 slots start at each range's start rounded down to 32 (adjacent
+    ranges merged first); slots outside the ranges are masked to -inf;
+  * lazy max per query: M = c m_ref moves to a tile's c * max only when that exceeds M by more than THR = 8; O and l are rescaled by
+    exp2(M_old - M_new) then;
+  * P^ = e4m3fn(RNE(exp2(c s - M))) (unit scale: P <= 2^8 < 448), l = sum P^, O = sum P^ V^, output bf16(O / l).
+
+The kernel and this restatement differ only by the fp32 summation order and v_exp_f32's ulp.
+MXAttnRefModel is the oracle's RefModel (optionally with tests/mx_ref.py's MX block linears) with self-attention on this scheme."""
+import math
+from typing import List, Tuple
+
+import torch
+from torch import Tensor
+
+import mx_ref
+from oracle import ref_model as RM
+from oracle import ref_ops as R
+
+FP8 = torch.float8_e4m3fn
+KT = 64
+THR = 8.0
+LOG2E = 1.4426950408889634
+
+
+def frag_slot(p: int) -> int:
+    """Slot (within its 32-block) of code position p of a V^ row: the key order of a score tile's accumulator registers."""
+    jj, hh = p & 15, p >> 4
+    return (jj & 3) + 8 * (jj >> 2) + 4 * hh
+
+
+FRAG = torch.tensor([frag_slot(p) for p in range(32)])
+
+
+def shadow_k(k: Tensor) -> Tuple[Tensor, Tensor]:
+    """bf16 cache k [B, S, H, 128] -> (codes [B, S32, H, 128] e4m3fn, scales [B, S32, H, 4] uint8)."""
+    B, S, H, D = k.shape
+    S32 = (S + 31) // 32 * 32
+    kp = torch.zeros(B, S32, H, D, dtype=torch.bfloat16, device=k.device)
+    kp[:, :S] = k
+    q, s = mx_ref.quantize(kp.reshape(-1, D))
+    return q.reshape(B, S32, H, D), s.reshape(B, S32, H, D // 32)
+
+
+def shadow_v(v: Tensor) -> Tuple[Tensor, Tensor]:
+    """bf16 cache v [B, S, H, 128] -> (codes [B, H, S32/32, 128, 32] in fragment order, scales [B, H, S32/32, 128] uint8)."""
+    B, S, H, D = v.shape
+    S32 = (S + 31) // 32 * 32
+    vp = torch.zeros(B, S32, H, D, dtype=torch.bfloat16, device=v.device)
+    vp[:, :S] = v
+    blocks = vp.reshape(B, S32 // 32, 32, H, D).permute(0, 3, 1, 4, 2)          # [B, H, NB, D, 32 slots]
+    blocks = blocks[..., FRAG.to(v.device)].contiguous()                        # fragment order
+    q, s = mx_ref.quantize(blocks.reshape(-1, 32))
+    return q.reshape(B, H, S32 // 32, D, 32), s.reshape(B, H, S32 // 32, D)
+
+
+def deq_k(kq: Tensor, ks: Tensor, dtype=torch.float64) -> Tensor:
+    """[B, S32, H, 128] dequantised K^ (exact in fp32 and fp64)."""
+    e = ks.to(torch.int32) - 127
+    return (kq.to(dtype).reshape(*ks.shape, 32) * torch.pow(2.0, e.to(dtype)).unsqueeze(-1)).reshape(kq.shape)
+
+
+def deq_v(vq: Tensor, vs: Tensor, dtype=torch.float64) -> Tensor:
+    """[B, S32, H, 128] dequantised V^ in natural slot order."""
+    B, H, NB, D, _ = vq.shape
+    x = vq.to(dtype) * torch.pow(2.0, (vs.to(torch.int32) - 127).to(dtype)).unsqueeze(-1)
+    nat = torch.empty_like(x)
+    nat[..., FRAG.to(vq.device)] = x
+    return nat.permute(0, 2, 4, 1, 3).reshape(B, NB * 32, H, D)
+
+
+def merge_segments(segments) -> List[Tuple[int, int]]:
+    segs = [(int(a), int(b)) for a, b in segments if b > a]
+    if len(segs) == 2 and segs[1][0] == segs[0][1]:
+        segs = [(segs[0][0], segs[1][1])]
+    return segs
+
+
+def tiles(segments) -> List[Tuple[int, int, int]]:
+    """(base, lo, hi) of every key tile, in the kernel's order: tiles of range [lo, hi) start at lo & ~31, step 64."""
+    out = []
+    for lo, hi in merge_segments(segments):
+        base = lo & ~31
+        while base < hi:
+            out.append((base, lo, hi))
+            base += KT
+    return out
+
+
+def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = None, dtype=torch.float32) -> Tensor:
+    """The kernel's arithmetic on dequantised shadows kd, vd [B, S32, H, 128] (deq_k / deq_v): q [B, Lq, H, 128] bf16 -> fp32 O / l
+    [B, Lq, H, 128].  dtype: the accumulation type (float32 = the kernel's; float64 to measure the quantisation alone)."""
+    B, Lq, H, D = q.shape
+    S32 = kd.shape[1]
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    c = torch.tensor(scale * LOG2E, dtype=torch.float32).item()
+    qc, qsc = mx_ref.quantize(q.reshape(-1, D).to(torch.bfloat16))
+    qd = mx_ref.dequantize(qc, qsc).to(q.device).to(dtype).reshape(B, Lq, H, D).permute(0, 2, 1, 3)   # [B, H, Lq, D]
+    kdh = kd.to(dtype).permute(0, 2, 1, 3)                                                            # [B, H, S32, D]
+    vdh = vd.to(dtype).permute(0, 2, 1, 3)
+    M = torch.full((B, H, Lq, 1), -math.inf, dtype=torch.float32, device=q.device)
+    l = torch.zeros(B, H, Lq, 1, dtype=dtype, device=q.device)
+    O = torch.zeros(B, H, Lq, D, dtype=dtype, device=q.device)
+    slot_ids = torch.arange(KT, device=q.device)
+    for base, lo, hi in tiles(segments):
+        idx = (base + slot_ids).clamp(max=S32 - 1)
+        s = (qd @ kdh[:, :, idx].transpose(-1, -2)).float()                      # [B, H, Lq, 64] fp32 scores
+        valid = ((base + slot_ids) >= lo) & ((base + slot_ids) < hi)
+        s = s.masked_fill(~valid, -math.inf)
+        tm = s.amax(-1, keepdim=True) * c
+        Mn = torch.where(tm - M > THR, tm, M)
+        alpha = torch.exp2(M - Mn)
+        p = torch.exp2(s * c - Mn)
+        ph = p.to(FP8).to(dtype)
+        ph = ph.masked_fill(~valid, 0.0)
+        l = l * alpha.to(dtype) + ph.sum(-1, keepdim=True)
+        O = O * alpha.to(dtype) + ph @ vdh[:, :, idx]
+        M = Mn
+    return (O / l).permute(0, 2, 1, 3).float()
+
+
+def mx_attention_cache(q: Tensor, k: Tensor, v: Tensor, segments, scale: float = None, dtype=torch.float32) -> Tensor:
+    """mx_attention straight from the bf16 cache k, v [B, S, H, 128] (shadows derived here)."""
+    kd = deq_k(*shadow_k(k), dtype=dtype)
+    vd = deq_v(*shadow_v(v), dtype=dtype)
+    return mx_attention(q, kd, vd, segments, scale, dtype)
+
+
+class MXAttnRefModel(mx_ref.MXRefModel):
+    """RefModel with self-attention on the MX shadow scheme.  mx_linears: also the six MX block linears (set_quant("mxfp8")),
+    otherwise the bf16 linears of the oracle.  The cache is the oracle's (bf16 k / v written as RefModel writes them); attention
+    reads it through the shadow with ABSOLUTE slot indices, so the V^ blocks are the kernel's."""
+
+    def __init__(self, *a, mx_linears: bool = False, **kw):
+        super().__init__(*a, **kw)
+        self.mx_linears = mx_linears
+
+    def lin(self, x: Tensor, name: str) -> Tensor:
+        if self.mx_linears:
+            return super().lin(x, name)
+        return RM.RefModel.lin(self, x, name)
+
+    def self_attn(self, x: Tensor, p: str, grid, kv_cache: dict, current_start: int, sink_recache_after_switch: bool):
+        c = self.cfg
+        b, s, n, d = x.shape[0], x.shape[1], c.num_heads, c.dim // c.num_heads
+        q = R.rms_norm(self.lin(x, p + "q"), self.sd[p + "norm_q.weight"], c.eps).view(b, s, n, d)
+        k = R.rms_norm(self.lin(x, p + "k"), self.sd[p + "norm_k.weight"], c.eps).view(b, s, n, d)
+        v = self.lin(x, p + "v").view(b, s, n, d)
+        frame_seqlen = grid[1] * grid[2]
+        start_frame = current_start // frame_seqlen
+        rq = R.causal_rope_apply(q, grid, self.freqs, start_frame).type_as(v)
+        rk = R.causal_rope_apply(k, grid, self.freqs, start_frame).type_as(v)
+        plan = R.kv_plan(current_start, s, kv_cache["global_end_index"], kv_cache["local_end_index"],
+                         kv_cache["k"].shape[1], c.sink_size * frame_seqlen, self.local_attn_size,
+                         self.max_attention_size, sink_recache_after_switch)
+        R.kv_apply(kv_cache["k"], kv_cache["v"], plan, rk, v)
+        y = mx_attention_cache(rq.to(torch.bfloat16), kv_cache["k"].to(torch.bfloat16), kv_cache["v"].to(torch.bfloat16),
+                               plan["segments"]).to(self.dtype)
+        return self.lin(y.flatten(2), p + "o"), plan

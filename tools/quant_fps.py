@@ -1,9 +1,10 @@
-"""Frames/s of the three block-linear precisions (none = bf16, int8 = W8A8, mxfp8 = MXFP8), alternated in one process.
+"""Frames/s of the block-linear precisions (none = bf16, int8 = W8A8, mxfp8 = MXFP8), each with bf16 self-attention or with MXFP8
+self-attention over the shadow of the KV cache ("+attn": set_attn_quant("mxfp8")), alternated in one process.
 
 Workload = bench.py's fps_of: the LongLive-1.3B random-init generator, config 2's steady state (4 warm-up blocks, then timed blocks
 through pipe.stream).  The modes run in turn for --rounds rounds, so a clock drift of the device lands on all of them alike; the
-record holds the median frames/s, ms per block and average GPU clock per mode, and a per-kernel table of one extra (timed-launch)
-MXFP8 pass with the MX GEMM plan strings.
+record holds the median frames/s, ms per block and average GPU clock per mode, and per-kernel tables of one extra (timed-launch)
+block of mxfp8 and of none+attn, with the MX GEMM and MX attention plan strings.
 
     python tools/quant_fps.py --rounds 3 --blocks 4 --out profiles/quant_fps.json
 """
@@ -19,7 +20,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = ("none", "int8", "mxfp8")
+MODES = ("none", "int8", "mxfp8", "none+attn", "int8+attn", "mxfp8+attn")
 
 
 def main(argv=None):
@@ -27,6 +28,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--modes", default=",".join(MODES), help="comma-separated subset of " + ", ".join(MODES))
     args = ap.parse_args(argv)
 
     import torch
@@ -42,8 +44,15 @@ def main(argv=None):
                               state_dict=synth.synth_state_dict(cfg, seed=0, device=dev))
     prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=1, device=dev)}
 
+    modes = [m.strip() for m in args.modes.split(",") if m.strip()]
+    for m in modes:
+        if m not in MODES:
+            raise SystemExit(f"unknown mode {m!r}: one of {', '.join(MODES)}")
+
     def run(mode, blocks, timer=None):
-        gen.model.set_quant(None if mode == "none" else mode)
+        lin, _, attn = mode.partition("+")
+        gen.model.set_quant(None if lin == "none" else lin)
+        gen.model.set_attn_quant("mxfp8" if attn == "attn" else None)
         pipe = CausalInferencePipeline(bench._pipe_args(), dev, generator=gen)
         st = pipe.stream(synth.synth_noise(cfg, 3 * (4 + blocks), seed=0, device=dev), prompt)
         for _ in range(4):
@@ -61,33 +70,51 @@ def main(argv=None):
         clk = tel.stop(0).get("sclk_mhz_avg")
         return dict(fps=12 * blocks / dt, ms_per_block=1e3 * dt / blocks, sclk_mhz=clk)
 
-    rows = {m: [] for m in MODES}
+    rows = {m: [] for m in modes}
     for r in range(args.rounds):
-        for m in MODES:
+        for m in modes:
             rows[m].append(run(m, args.blocks))
-            print(f"round {r} {m:6s}: {rows[m][-1]['fps']:.2f} frames/s, {rows[m][-1]['ms_per_block']:.1f} ms/block, "
+            print(f"round {r} {m:10s}: {rows[m][-1]['fps']:.2f} frames/s, {rows[m][-1]['ms_per_block']:.1f} ms/block, "
                   f"sclk {rows[m][-1]['sclk_mhz']}", flush=True)
     med = {}
-    for m in MODES:
+    for m in modes:
         clks = [x["sclk_mhz"] for x in rows[m] if x["sclk_mhz"] is not None]
         med[m] = dict(fps=statistics.median(x["fps"] for x in rows[m]), ms_per_block=statistics.median(x["ms_per_block"] for x in rows[m]),
                       sclk_mhz=statistics.median(clks) if clks else None)
 
-    timer = ops.KernelTimer()
-    run("mxfp8", 1, timer)
-    torch.cuda.synchronize()
-    summ = timer.summary()
-    kernels = {t: dict(launches=v["launches"], avg_us=1e3 * v["avg_ms"], total_ms=v["total_ms"]) for t, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])}
+    def kernel_table(mode):
+        timer = ops.KernelTimer()
+        run(mode, 1, timer)
+        torch.cuda.synchronize()
+        summ = timer.summary()
+        return {t: dict(launches=v["launches"], avg_us=1e3 * v["avg_ms"], total_ms=v["total_ms"])
+                for t, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])}
+
+    tables = {m: kernel_table(m) for m in ("mxfp8", "none+attn") if m in modes}
     M = 3 * cfg.frame_seqlen
+    S = cfg.local_attn_size * cfg.frame_seqlen
     plans = {name: ops.gemm_plan_mx(M, n, k) for name, n, k in (("gemm_qkv", 3 * cfg.dim, cfg.dim), ("gemm_o / gemm_cq / gemm_co", cfg.dim, cfg.dim),
                                                                  ("gemm_f1", cfg.ffn_dim, cfg.dim), ("gemm_f2", cfg.dim, cfg.ffn_dim))}
+    sink = cfg.sink_size * cfg.frame_seqlen
+    attn_plan = ops.flash_attn_mx_plan(M, cfg.num_heads, 1, [(0, sink), (sink, S)])
     gen.model.set_quant(None)
+    gen.model.set_attn_quant(None)
     rec = dict(tool="tools/quant_fps.py", device=torch.cuda.get_device_name(0), rounds=args.rounds, blocks=args.blocks,
                workload="bench.py fps_of: LongLive-1.3B random-init, config 2 steady state, 4 warm-up blocks, timed blocks via pipe.stream",
-               median=med, runs=rows, mxfp8_kernels_one_block=kernels, mxfp8_gemm_plans=plans)
+               median=med, runs=rows, mxfp8_gemm_plans=plans, flash_attn_mx_plan=attn_plan)
+    for m, kern in tables.items():
+        rec[m.replace("+", "_") + "_kernels_one_block"] = kern
     print(json.dumps(dict(median=med)), flush=True)
-    for t, v in kernels.items():
-        print(f"  {t:28s} {v['launches']:5d} launches  {v['avg_us']:9.1f} us avg  {v['total_ms']:8.2f} ms")
+    for m, kern in tables.items():
+        print(f"per-kernel, one timed block of {m}:")
+        for t, v in kern.items():
+            print(f"  {t:28s} {v['launches']:5d} launches  {v['avg_us']:9.1f} us avg  {v['total_ms']:8.2f} ms")
+    if "none+attn" in tables:
+        print(f"flash_attn_mx: {attn_plan}")
+        for t in ("flash_attn_self_mx", "kv_shadow_mx"):
+            v = tables["none+attn"].get(t)
+            if v:
+                print(f"  {t}: {v['launches']} launches, {v['avg_us']:.1f} us avg, {v['total_ms']:.2f} ms per block (lone-stream launches)")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
