@@ -44,8 +44,10 @@ enum ll_epilogue {
  * (longlive_amd/_lib.py) and any other caller must find ll_version() == LL_ABI_VERSION or refuse the library: a stale .so would
  * otherwise shift `stream` and the pointers silently.  100 = rounds 1-3; 105 = round 4's removals (workspace arguments of
  * ll_flash_attn, the split-K hand-off entry points); 106 = round 5 (ll_conv_cl_rms added); 107 = MXFP8 block linears;
- * 108 = MXFP8 self-attention (ll_kv_shadow_mx, ll_flash_attn_mx, ll_flash_attn_mx_plan). */
-#define LL_ABI_VERSION 108
+ * 108 = MXFP8 self-attention (ll_kv_shadow_mx, ll_flash_attn_mx, ll_flash_attn_mx_plan);
+ * 109 = FP8 rowwise block linears (ll_quantize_rows_f8, ll_gemm_f8, ll_gemm_f8_qkv, ll_ln_modulate_f8, ll_ln_modulate_tab_f8,
+ * ll_layernorm_affine_f8, ll_gemm_plan_f8). */
+#define LL_ABI_VERSION 109
 int ll_version(void);
 const char* ll_last_error(void);
 /* Development knob for A/B timing of kernel variants (tools/kbench, tools/kenergy, LL_TUNING=key=value,... for bench.py);
@@ -218,6 +220,33 @@ int ll_ln_modulate_tab_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float
 int ll_layernorm_affine_mx(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
                            float eps, ll_stream stream);
 int ll_gemm_plan_mx(int M, int N, int K, char* out, int cap);
+
+/* FP8 rowwise mode of the block linears (set_quant("fp8_rowwise")): ll_gemm_w8a8's per-token / per-output-channel scheme with OCP e4m3fn
+ * codes instead of int8.  Per row (a token of the activations, an output channel of a [N, K] weight): amax = max |x| over its bf16
+ * values (fp32), sc = amax / 448 (1 for an all-zero row), inv = 1 / sc, code = e4m3fn(RNE(clamp(x * inv, -448, 448))) with subnormals
+ * kept.  Codes [rows, K] (uint8), scales [rows] (fp32).
+ *   ll_quantize_rows_f8: bf16 rows (stride ldx elements) -> codes + scales; ll_quantize_rows' kernels and dispatch.
+ *   ll_gemm_f8:     out = epilogue(sx[m] * sw[n] * sum_k dec(xq[m,k]) dec(wq[n,k]) + bias), fp32 accumulation on
+ *                   v_mfma_scale_f32_16x16x128_f8f6f4 at unit block scales, ll_gemm_w8a8's kernels, epilogues and rounding points;
+ *                   K % 128 == 0, ldo % 8 == 0.
+ *   ll_gemm_f8_qkv: ll_gemm_w8a8_qkv's fused q|k|v projection (V third into cache_v) on FP8 operands.
+ *   ll_ln_modulate_f8 / ll_ln_modulate_tab_f8 / ll_layernorm_affine_f8: the producers of the same names emitting the codes + row scale of
+ *                   their bf16 output (bit-identical to ll_quantize_rows_f8 of it).
+ *   ll_gemm_plan_f8: kernel instance, tile and grid of an ll_gemm_f8 / ll_gemm_f8_qkv call (host only). */
+int ll_quantize_rows_f8(const ll_bf16* x, uint8_t* q, float* scale, int rows, int K, int ldx, ll_stream stream);
+int ll_gemm_f8(const uint8_t* xq, const float* sx, const uint8_t* wq, const float* sw, const ll_bf16* bias, ll_bf16* out,
+               int M, int N, int K, int ldo, int epilogue, const ll_bf16* res, const ll_bf16* e, const ll_bf16* mod,
+               int nmod, int gate_idx, int rows_per_batch, int frame_len, ll_stream stream);
+int ll_gemm_f8_qkv(const uint8_t* xq, const float* sx, const uint8_t* wq, const float* sw, const ll_bf16* bias, ll_bf16* out,
+                   int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset,
+                   int write_len, ll_stream stream);
+int ll_ln_modulate_f8(const ll_bf16* x, uint8_t* q, float* qscale, const ll_bf16* e, const ll_bf16* mod, int nmod, int shift_idx,
+                      int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_ln_modulate_tab_f8(const ll_bf16* x, uint8_t* q, float* qscale, const float* tab, int nmod, int shift_idx, int scale_idx,
+                          int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_layernorm_affine_f8(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, float* qscale, int rows, int C,
+                           float eps, ll_stream stream);
+int ll_gemm_plan_f8(int M, int N, int K, char* out, int cap);
 
 /* MXFP8 self-attention (set_attn_quant("mxfp8")) over a block-scaled SHADOW of one layer's bf16 KV cache k, v [B, S, H, 128]; the bf16
  * cache stays the master, S32 = S rounded up to a multiple of 32.  MX rule as ll_quantize_mx.

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void conv_cl_kernel(ConvGeo g, const char* 
     __builtin_amdgcn_s_setprio(0);
     slot = slot == 2 ? 0 : slot + 1;
   }
-  gemm_epilogue<EPI, false, NT, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * (16 * NT), fr, fg, ea);
+  gemm_epilogue<EPI, GQ_BF16, NT, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * (16 * NT), fr, fg, ea);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void conv_halo_kernel(const char* __restric
     if (hrow >= Ho) continue;
     int m_row = (t * Ho + hrow) * Wo + w0;
     if (RMS) conv_epilogue_rms<EPI, NCB>(acc[i], Y, Y2, (t * Ho + hrow + 1) * Wo, ldo, m_row, fr, fg, ea, rms_gamma, rms_silu, rms_sqrt_c);
-    else gemm_epilogue<EPI, false, NCB, 2>(acc[i], Y, (t * Ho + hrow + 1) * Wo, N, ldo, m_row, n0, fr, fg, ea);
+    else gemm_epilogue<EPI, GQ_BF16, NCB, 2>(acc[i], Y, (t * Ho + hrow + 1) * Wo, N, ldo, m_row, n0, fr, fg, ea);
   }
 }
 

@@ -83,8 +83,8 @@ __device__ __forceinline__ void layernorm_center(RowRegs& r, int C, int lane, fl
 
 // Row output from packed bf16 pairs: stored as they are, or (int8 mode) symmetric per-row int8 + scale computed from the SAME
 // bf16-rounded values the bf16 path stores, so fused and unfused quantisation are bit-identical (scale = max|y| / 127,
-// q = rint(y / scale)).
-template <int NCH, bool FULL>
+// q = rint(y / scale)).  F8 (FP8 rowwise mode): e4m3fn codes + scale, ll_quantize_rows_f8's arithmetic (scale = max|y| / 448, mx.h).
+template <int NCH, bool FULL, bool F8 = false>
 __device__ __forceinline__ void emit_row(const RowWords& y, int C, int lane, int row, bf16* __restrict__ out,
                                          int8_t* __restrict__ q, float* __restrict__ qscale) {
   if (q == nullptr) {
@@ -109,9 +109,24 @@ __device__ __forceinline__ void emit_row(const RowWords& y, int C, int lane, int
     }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  float sc = mx > 0.f ? mx / 127.0f : 1.0f;
+  float sc = mx > 0.f ? mx / (F8 ? F8_MAX : 127.0f) : 1.0f;
   float inv = 1.0f / sc;
   if (lane == 0) qscale[row] = sc;
+  if constexpr (F8) {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      int c = (lane + 64 * i) * 8;
+      if (in_row<FULL>(c, C)) {
+        f32x2 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = unpack2(y.w[i][j]);
+        uint32_t lo = f8_code4(v[0].x * inv, v[0].y * inv, v[1].x * inv, v[1].y * inv);
+        uint32_t hi = f8_code4(v[2].x * inv, v[2].y * inv, v[3].x * inv, v[3].y * inv);
+        *reinterpret_cast<uint2*>(q + (size_t)row * C + c) = make_uint2(lo, hi);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     int c = (lane + 64 * i) * 8;
@@ -136,7 +151,7 @@ __device__ __forceinline__ void emit_row(const RowWords& y, int C, int lane, int
 //   y = bf16(LN(x)); s1 = bf16(1 + bf16(mod_s + e_s)); out = bf16(bf16(y * s1) + bf16(mod_t + e_t))
 // PRE: `e` already holds bf16(mod + e) for every chunk (ll_modulation_table, once per forward for all layers): two vector
 // loads and three operations per element less; the values are the ones the unfused form computes, bit for bit.
-template <int NCH, bool FULL, bool PRE>
+template <int NCH, bool FULL, bool PRE, bool F8 = false>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(const bf16* __restrict__ x, bf16* __restrict__ out,
                                                           const bf16* __restrict__ e, const bf16* __restrict__ mod,
                                                           int nmod, int shift_idx, int scale_idx, int rows, int L,
@@ -172,13 +187,13 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const bf16* __restrict
       f32x2 s1 = rbf2(one + sc);
       o.w[i][j] = pack2(rbf2(y * s1) + t);
     }
-  emit_row<NCH, FULL>(o, C, lane, row, out, q, qscale);
+  emit_row<NCH, FULL, F8>(o, C, lane, row, out, q, qscale);
 }
 
 // The same from an fp32 table (ll_modulation_table_f32): tab[b, f, scale_idx] = 1 + scale and tab[b, f, shift_idx] = shift, each already
 // rounded to bf16 where the reference rounds (s1 and t above, bit for bit) and widened to fp32 -- per pair of elements no unpacking
 // and no `1 +` / rounding of the scale: 10 vector instructions instead of 18 in a kernel bound by their count.
-template <int NCH, bool FULL>
+template <int NCH, bool FULL, bool F8 = false>
 __global__ __launch_bounds__(256) void ln_modulate_tab_kernel(const bf16* __restrict__ x, bf16* __restrict__ out,
                                                               const float* __restrict__ tab, int nmod, int shift_idx, int scale_idx,
                                                               int rows, int L, int C, int frame_len, int F, float eps,
@@ -214,11 +229,11 @@ __global__ __launch_bounds__(256) void ln_modulate_tab_kernel(const bf16* __rest
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(rbf2(rbf2(r.p[i][j] * r2) * s1[i][j]) + t[i][j]);
-  emit_row<NCH, FULL>(o, C, lane, row, out, q, qscale);
+  emit_row<NCH, FULL, F8>(o, C, lane, row, out, q, qscale);
 }
 
 // LN with affine (norm3): F.layer_norm computes (x-mean)*rstd*w + b in fp32 and rounds once.
-template <int NCH, bool FULL>
+template <int NCH, bool FULL, bool F8 = false>
 __global__ __launch_bounds__(256) void layernorm_affine_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
                                                                const bf16* __restrict__ bb, bf16* __restrict__ out,
                                                                int rows, int C, float eps, int8_t* __restrict__ q,
@@ -241,7 +256,7 @@ __global__ __launch_bounds__(256) void layernorm_affine_kernel(const bf16* __res
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
-  emit_row<NCH, FULL>(o, C, lane, row, out, q, qscale);
+  emit_row<NCH, FULL, F8>(o, C, lane, row, out, q, qscale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -694,24 +709,29 @@ static inline bool row_ok(int C) { return C > 0 && C <= 2048 && (C % 8) == 0; }
 
 static int ln_modulate_launch(const ll_bf16* x, ll_bf16* out, int8_t* q, float* qscale, const ll_bf16* e,
                               const ll_bf16* mod, int nmod, int shift_idx, int scale_idx, int B, int L, int C, int F,
-                              float eps, ll_stream stream) {
+                              float eps, ll_stream stream, bool f8 = false) {
   LL_REQUIRE(row_ok(C), "ll_ln_modulate: C=%d must be a multiple of 8 and <= 2048", C);
   LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate: L=%d not divisible by F=%d", L, F);
   LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate: bad mod index");
   int rows = B * L;
   if (rows == 0) return LL_OK;
   dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                          \
+#define CALL2(N, FL, F8)                                                                                                     \
   do {                                                                                                                   \
     if (mod)                                                                                                             \
-      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out, \
+      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, false, F8>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out, \
                          (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qscale); \
     else                                                                                                                 \
-      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out,  \
+      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, true, F8>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out,  \
                          (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qscale); \
   } while (0)
-  DISPATCH_NCH(C, CALL);
+#define CALL(N, FL) CALL2(N, FL, false)
+#define CALL_F8(N, FL) CALL2(N, FL, true)
+  if (f8) DISPATCH_NCH(C, CALL_F8);
+  else DISPATCH_NCH(C, CALL);
 #undef CALL
+#undef CALL_F8
+#undef CALL2
   return ll_check_launch("ll_ln_modulate");
 }
 
@@ -736,6 +756,13 @@ extern "C" int ll_ln_modulate_q8(const ll_bf16* x, int8_t* q, float* qscale, con
                                  ll_stream stream) {
   LL_REQUIRE(q && qscale, "ll_ln_modulate_q8: q and qscale are required");
   return ln_modulate_launch(x, nullptr, q, qscale, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream);
+}
+
+extern "C" int ll_ln_modulate_f8(const ll_bf16* x, uint8_t* q, float* qscale, const ll_bf16* e, const ll_bf16* mod, int nmod,
+                                 int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
+  LL_REQUIRE(x != nullptr && e != nullptr, "ll_ln_modulate_f8: x and e are required");
+  LL_REQUIRE(q && qscale, "ll_ln_modulate_f8: codes and scales are required");
+  return ln_modulate_launch(x, nullptr, (int8_t*)q, qscale, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream, true);
 }
 
 extern "C" int ll_modulation_table_f32(const ll_bf16* e, const ll_bf16* mods, float* out, int num_layers, int BF, int nmod, int C,
@@ -768,16 +795,39 @@ extern "C" int ll_ln_modulate_tab(const ll_bf16* x, ll_bf16* out, int8_t* q, flo
   return ll_check_launch("ll_ln_modulate_tab");
 }
 
+extern "C" int ll_ln_modulate_tab_f8(const ll_bf16* x, uint8_t* q, float* qscale, const float* tab, int nmod, int shift_idx, int scale_idx,
+                                     int B, int L, int C, int F, float eps, ll_stream stream) {
+  LL_REQUIRE(x != nullptr && tab != nullptr, "ll_ln_modulate_tab_f8: x and tab are required");
+  LL_REQUIRE(q && qscale, "ll_ln_modulate_tab_f8: codes and scales are required");
+  LL_REQUIRE(row_ok(C), "ll_ln_modulate_tab_f8: C=%d must be a multiple of 8 and <= 2048", C);
+  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab_f8: L=%d not divisible by F=%d", L, F);
+  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab_f8: bad mod index");
+  int rows = B * L;
+  if (rows == 0) return LL_OK;
+  dim3 grid((rows + 3) / 4);
+#define CALL(N, FL)                                                                                                           \
+  hipLaunchKernelGGL((ln_modulate_tab_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)nullptr, \
+                     tab, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, (int8_t*)q, qscale)
+  DISPATCH_NCH(C, CALL);
+#undef CALL
+  return ll_check_launch("ll_ln_modulate_tab_f8");
+}
+
 static int layernorm_affine_launch(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, ll_bf16* out, int8_t* q,
-                                   float* qscale, int rows, int C, float eps, ll_stream stream) {
+                                   float* qscale, int rows, int C, float eps, ll_stream stream, bool f8 = false) {
   LL_REQUIRE(row_ok(C), "ll_layernorm_affine: C=%d must be a multiple of 8 and <= 2048", C);
   if (rows == 0) return LL_OK;
   dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                              \
-  hipLaunchKernelGGL((layernorm_affine_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,   \
+#define CALL2(N, FL, F8)                                                                                         \
+  hipLaunchKernelGGL((layernorm_affine_kernel<N, FL, F8>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, \
                      (const bf16*)w, (const bf16*)b, (bf16*)out, rows, C, eps, q, qscale)
-  DISPATCH_NCH(C, CALL);
+#define CALL(N, FL) CALL2(N, FL, false)
+#define CALL_F8(N, FL) CALL2(N, FL, true)
+  if (f8) DISPATCH_NCH(C, CALL_F8);
+  else DISPATCH_NCH(C, CALL);
 #undef CALL
+#undef CALL_F8
+#undef CALL2
   return ll_check_launch("ll_layernorm_affine");
 }
 
@@ -790,6 +840,13 @@ extern "C" int ll_layernorm_affine_q8(const ll_bf16* x, const ll_bf16* w, const 
                                       int rows, int C, float eps, ll_stream stream) {
   LL_REQUIRE(q && qscale, "ll_layernorm_affine_q8: q and qscale are required");
   return layernorm_affine_launch(x, w, b, nullptr, q, qscale, rows, C, eps, stream);
+}
+
+extern "C" int ll_layernorm_affine_f8(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, float* qscale, int rows, int C,
+                                      float eps, ll_stream stream) {
+  LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "ll_layernorm_affine_f8: x, w and b are required");
+  LL_REQUIRE(q && qscale, "ll_layernorm_affine_f8: codes and scales are required");
+  return layernorm_affine_launch(x, w, b, nullptr, (int8_t*)q, qscale, rows, C, eps, stream, true);
 }
 
 // ---- MXFP8 producers (codes [rows, C] e4m3fn, scales [rows, C / 32] E8M0)

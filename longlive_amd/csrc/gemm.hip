@@ -1,5 +1,6 @@
-// GEMM  out[M,N] = epilogue(x[M,K] @ w[N,K]^T + bias)  on gfx950 MFMA, bf16 (v_mfma_f32_16x16x32_bf16) or
-// W8A8 int8 (v_mfma_i32_16x16x64_i8, per-row activation scale x per-output-channel weight scale).
+// GEMM  out[M,N] = epilogue(x[M,K] @ w[N,K]^T + bias)  on gfx950 MFMA, bf16 (v_mfma_f32_16x16x32_bf16),
+// W8A8 int8 (v_mfma_i32_16x16x64_i8, per-row activation scale x per-output-channel weight scale) or FP8 rowwise (e4m3fn codes with
+// the same two scales, v_mfma_scale_f32_16x16x128_f8f6f4 at unit block scales: gemm_common.h Ty<GQ_F8>).
 //
 // Both operands are K-contiguous (activations [M,K], nn.Linear weights [N,K]), which is exactly the MFMA fragment
 // shape (16 consecutive bytes of k per lane), so there are no transposes anywhere.  Common structure:
@@ -23,6 +24,7 @@
 #include <atomic>
 
 #include "gemm_common.h"
+#include "mx.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // v2: 256 x 128 tile, 3-stage ring (3 x 48 KiB).  Two K-tiles stay in flight across the barrier: the only wait in the
@@ -30,12 +32,12 @@
 #define V2_BM 256
 #define V2_STAGE ((V2_BM + BN) * ROWB)   // 48 KiB
 
-template <int EPI, bool I8>
+template <int EPI, int Q>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v2(const char* __restrict__ X, const char* __restrict__ Wt,
                                                          bf16* __restrict__ Y, int M, int N, int nk, size_t xrow_bytes,
                                                          size_t wrow_bytes, int ldo, int ntm, int ntn, int gm, int lds_epi, EpiArgs ea) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename Ty<I8>::frag frag_t;
+  typedef typename Ty<Q>::frag frag_t;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
@@ -43,11 +45,11 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v2(const char* __restrict_
   tile_of(lid, ntm, ntn, gm, mt_, nt_);
   const int m0 = mt_ * V2_BM, n0 = nt_ * BN;
 
-  typename Ty<I8>::acc acc[4][4];
+  typename Ty<Q>::acc acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = acc_zero<I8>();
+    for (int b = 0; b < 4; ++b) acc[a][b] = acc_zero<Q>();
 
   auto stage = [&](int kt, int slot) {
     char* base = smem + slot * V2_STAGE;
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v2(const char* __restrict_
   }
 #define V2_MMA(WF, XF)                                                                           \
   _Pragma("unroll") for (int a = 0; a < 4; ++a)                                                  \
-  _Pragma("unroll") for (int b = 0; b < 4; ++b) acc[a][b] = Ty<I8>::mma(WF[a], XF[b], acc[a][b]);
+  _Pragma("unroll") for (int b = 0; b < 4; ++b) acc[a][b] = Ty<Q>::mma(WF[a], XF[b], acc[a][b]);
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // tile kt landed; tile kt+1 may be in flight
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -86,11 +88,21 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v2(const char* __restrict_
       continue;
     }
     __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    if constexpr (Q == GQ_F8) {       // one 16x16x128 MFMA per 128-byte stage (gemm_common.h Ty<GQ_F8>)
       frag_t wf[4], xf[4];
-      V2_READ(wf, xf, ks);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        wf[t] = frag_f8(ws, wn * 64 + t * 16 + fr, fg);
+        xf[t] = frag_f8(xs, wm * 64 + t * 16 + fr, fg);
+      }
       V2_MMA(wf, xf);
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        frag_t wf[4], xf[4];
+        V2_READ(wf, xf, ks);
+        V2_MMA(wf, xf);
+      }
     }
     __builtin_amdgcn_s_setprio(0);
     slot = slot == 2 ? 0 : slot + 1;
@@ -99,9 +111,9 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v2(const char* __restrict_
 #undef V2_MMA
   if (lds_epi) {
     __builtin_amdgcn_s_barrier();      // every wave has read its last K-step's fragments: the ring is free
-    gemm_epilogue_lds<EPI, I8, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, lane, smem + wave * (64 * EPI_ROW_BYTES(4)), ea);
+    gemm_epilogue_lds<EPI, Q, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, lane, smem + wave * (64 * EPI_ROW_BYTES(4)), ea);
   } else {
-    gemm_epilogue<EPI, I8, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, fr, fg, ea);
+    gemm_epilogue<EPI, Q, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, fr, fg, ea);
   }
 }
 
@@ -112,12 +124,12 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v2(const char* __restrict_
 #define V3_BN 256
 #define V3_STAGE ((V3_BM + V3_BN) * ROWB)   // 64 KiB
 
-template <int EPI, bool I8>
+template <int EPI, int Q>
 __global__ __launch_bounds__(512, 2) void gemm_kernel_v3(const char* __restrict__ X, const char* __restrict__ Wt,
                                                          bf16* __restrict__ Y, int M, int N, int nk, size_t xrow_bytes,
                                                          size_t wrow_bytes, int ldo, int ntm, int ntn, int gm, int lds_epi, EpiArgs ea) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename Ty<I8>::frag frag_t;
+  typedef typename Ty<Q>::frag frag_t;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -125,11 +137,11 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v3(const char* __restrict_
   tile_of(lid, ntm, ntn, gm, mt_, nt_);
   const int m0 = mt_ * V3_BM, n0 = nt_ * V3_BN;
 
-  typename Ty<I8>::acc acc[4][8];
+  typename Ty<Q>::acc acc[4][8];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = acc_zero<I8>();
+    for (int b = 0; b < 8; ++b) acc[a][b] = acc_zero<Q>();
 
   auto stage = [&](int kt, int slot) {
     char* base = smem + slot * V3_STAGE;
@@ -148,6 +160,17 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v3(const char* __restrict_
     const char* ws = xs + V3_BM * ROWB;
     if (!live) continue;               // rows past M: stage and sync only (see v2)
     __builtin_amdgcn_s_setprio(1);
+    if constexpr (Q == GQ_F8) {
+      frag_t wf[4], xf[8];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) wf[t] = frag_f8(ws, wn * 64 + t * 16 + fr, fg);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) xf[t] = frag_f8(xs, wm * 128 + t * 16 + fr, fg);
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) acc[a][b] = Ty<Q>::mma(wf[a], xf[b], acc[a][b]);
+    } else
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       frag_t wf[4], xf[8];
@@ -165,11 +188,11 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v3(const char* __restrict_
 #pragma unroll
       for (int b = 0; b < 8; ++b)
 #pragma unroll
-        for (int a = 0; a < 4; ++a) acc[a][b] = Ty<I8>::mma(wf[a], xf[b], acc[a][b]);
+        for (int a = 0; a < 4; ++a) acc[a][b] = Ty<Q>::mma(wf[a], xf[b], acc[a][b]);
     }
     __builtin_amdgcn_s_setprio(0);
   }
-  gemm_epilogue<EPI, I8, 4, 8>(acc, Y, M, N, ldo, m0 + wm * 128, n0 + wn * 64, fr, fg, ea);
+  gemm_epilogue<EPI, Q, 4, 8>(acc, Y, M, N, ldo, m0 + wm * 128, n0 + wn * 64, fr, fg, ea);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -177,14 +200,14 @@ __global__ __launch_bounds__(512, 2) void gemm_kernel_v3(const char* __restrict_
 // 256-column tiles quantise badly on 256 CUs: WM x WN waves of (MT x NT) 16 x 16 tiles, BN = WN * NT * 16.
 //   <2, 4, 8, 3>: 256 x 192 (QKV, N = 4608: 456 tiles = 2 rounds of 0.75 instead of 342 = 2 rounds of 1.0)
 //   <4, 2, 4, 7>: 256 x 224 (FFN1, N = 8960: 760 tiles = 2.97 rounds of 0.875 instead of 665 = 3 rounds of 1.0)
-template <int EPI, bool I8, int WM, int WN, int MT, int NT>
+template <int EPI, int Q, int WM, int WN, int MT, int NT>
 __global__ __launch_bounds__(512, 1) void gemm_kernel_v5(const char* __restrict__ X, const char* __restrict__ Wt,
                                                          bf16* __restrict__ Y, int M, int N, int nk, size_t xrow_bytes,
                                                          size_t wrow_bytes, int ldo, int ntm, int ntn, int gm, int lds_epi, EpiArgs ea) {
   static_assert(WM * WN == 8 && WM * MT * 16 == 256, "8 waves, 256 rows");
   constexpr int BNv = WN * NT * 16, STAGE = (256 + BNv) * ROWB, NB = BNv / 8;   // NB = B pieces of 8 rows per K-step
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef typename Ty<I8>::frag frag_t;
+  typedef typename Ty<Q>::frag frag_t;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
@@ -192,11 +215,11 @@ __global__ __launch_bounds__(512, 1) void gemm_kernel_v5(const char* __restrict_
   tile_of(lid, ntm, ntn, gm, mt_, nt_);
   const int m0 = mt_ * 256, n0 = nt_ * BNv;
 
-  typename Ty<I8>::acc acc[NT][MT];
+  typename Ty<Q>::acc acc[NT][MT];
 #pragma unroll
   for (int a = 0; a < NT; ++a)
 #pragma unroll
-    for (int b = 0; b < MT; ++b) acc[a][b] = acc_zero<I8>();
+    for (int b = 0; b < MT; ++b) acc[a][b] = acc_zero<Q>();
 
   auto stage = [&](int kt, int slot) {
     char* base = smem + slot * STAGE;
@@ -216,6 +239,17 @@ __global__ __launch_bounds__(512, 1) void gemm_kernel_v5(const char* __restrict_
     const char* ws = xs + 256 * ROWB;
     if (!live || (lds_epi & 0x200)) continue;               // rows past M: stage and sync only (see v2)
     __builtin_amdgcn_s_setprio(1);
+    if constexpr (Q == GQ_F8) {
+      frag_t wf[NT], xf[MT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) wf[t] = frag_f8(ws, wn * NT * 16 + t * 16 + fr, fg);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) xf[t] = frag_f8(xs, wm * MT * 16 + t * 16 + fr, fg);
+#pragma unroll
+      for (int b = 0; b < MT; ++b)
+#pragma unroll
+        for (int a = 0; a < NT; ++a) acc[a][b] = Ty<Q>::mma(wf[a], xf[b], acc[a][b]);
+    } else
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       frag_t wf[NT], xf[MT];
@@ -233,16 +267,16 @@ __global__ __launch_bounds__(512, 1) void gemm_kernel_v5(const char* __restrict_
 #pragma unroll
       for (int b = 0; b < MT; ++b)
 #pragma unroll
-        for (int a = 0; a < NT; ++a) acc[a][b] = Ty<I8>::mma(wf[a], xf[b], acc[a][b]);
+        for (int a = 0; a < NT; ++a) acc[a][b] = Ty<Q>::mma(wf[a], xf[b], acc[a][b]);
     }
     __builtin_amdgcn_s_setprio(0);
   }
   if (lds_epi) {
     __builtin_amdgcn_s_barrier();
-    gemm_epilogue_lds<EPI, I8, NT, MT>(acc, Y, M, N, ldo, m0 + wm * MT * 16, n0 + wn * NT * 16, lane,
+    gemm_epilogue_lds<EPI, Q, NT, MT>(acc, Y, M, N, ldo, m0 + wm * MT * 16, n0 + wn * NT * 16, lane,
                                        smem + wave * (MT * 16 * EPI_ROW_BYTES(NT)), ea);
   } else {
-    gemm_epilogue<EPI, I8, NT, MT>(acc, Y, M, N, ldo, m0 + wm * MT * 16, n0 + wn * NT * 16, fr, fg, ea);
+    gemm_epilogue<EPI, Q, NT, MT>(acc, Y, M, N, ldo, m0 + wm * MT * 16, n0 + wn * NT * 16, fr, fg, ea);
   }
 }
 
@@ -326,8 +360,35 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const bf16* __restric
 // Per-row symmetric int8 quantisation: scale[r] = max|x[r,:]| / 127 (1 if the row is all zero), q = rint(x / scale).
 // One wave per row, two passes over the row (the second one is served by L2).  Used for activations (per token) and,
 // once at load time, for weights (rows of [N,K] = per output channel).
-__global__ __launch_bounds__(256) void quantize_rows_kernel(const bf16* __restrict__ x, int8_t* __restrict__ q,
-                                                            float* __restrict__ scale, int rows, int K, int ldx) {
+// F8: the FP8 rowwise form (mx.h): scale = max|x| / 448, q = e4m3fn(clamp(x / scale)), same structure and dispatch.
+template <bool F8>
+__device__ __forceinline__ float qrow_scale(float mx) {
+  return mx > 0.f ? mx / (F8 ? F8_MAX : 127.0f) : 1.0f;
+}
+
+// 8 codes of one 16-byte chunk (element j in byte j)
+template <bool F8>
+__device__ __forceinline__ uint2 qrow_codes8(const bf16x8& v, float inv) {
+  unsigned lo = 0, hi = 0;
+  if constexpr (F8) {
+    lo = f8_code4((float)v[0] * inv, (float)v[1] * inv, (float)v[2] * inv, (float)v[3] * inv);
+    hi = f8_code4((float)v[4] * inv, (float)v[5] * inv, (float)v[6] * inv, (float)v[7] * inv);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int a = __float2int_rn((float)v[j] * inv), b = __float2int_rn((float)v[4 + j] * inv);
+      a = a < -127 ? -127 : (a > 127 ? 127 : a);
+      b = b < -127 ? -127 : (b > 127 ? 127 : b);
+      lo |= (unsigned)(a & 0xFF) << (8 * j);
+      hi |= (unsigned)(b & 0xFF) << (8 * j);
+    }
+  }
+  return make_uint2(lo, hi);
+}
+
+template <bool F8>
+__device__ __forceinline__ void quantize_rows_body(const bf16* __restrict__ x, int8_t* __restrict__ q, float* __restrict__ scale,
+                                                   int rows, int K, int ldx) {
   int lane = threadIdx.x & 63;
   int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -340,30 +401,30 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const bf16* __restri
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  float sc = mx > 0.f ? mx / 127.0f : 1.0f;
+  float sc = qrow_scale<F8>(mx);
   float inv = 1.0f / sc;
   if (lane == 0) scale[row] = sc;
   int8_t* qr = q + (size_t)row * K;
   for (int k = lane * 8; k < K; k += 512) {
     bf16x8 v = *reinterpret_cast<const bf16x8*>(xr + k);
-    unsigned lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int a = __float2int_rn((float)v[j] * inv), b = __float2int_rn((float)v[4 + j] * inv);
-      a = a < -127 ? -127 : (a > 127 ? 127 : a);
-      b = b < -127 ? -127 : (b > 127 ? 127 : b);
-      lo |= (unsigned)(a & 0xFF) << (8 * j);
-      hi |= (unsigned)(b & 0xFF) << (8 * j);
-    }
-    *reinterpret_cast<uint2*>(qr + k) = make_uint2(lo, hi);
+    *reinterpret_cast<uint2*>(qr + k) = qrow_codes8<F8>(v, inv);
   }
+}
+
+__global__ __launch_bounds__(256) void quantize_rows_kernel(const bf16* __restrict__ x, int8_t* __restrict__ q,
+                                                            float* __restrict__ scale, int rows, int K, int ldx) {
+  quantize_rows_body<false>(x, q, scale, rows, K, ldx);
+}
+__global__ __launch_bounds__(256) void quantize_rows_f8_kernel(const bf16* __restrict__ x, uint8_t* __restrict__ q,
+                                                               float* __restrict__ scale, int rows, int K, int ldx) {
+  quantize_rows_body<true>(x, (int8_t*)q, scale, rows, K, ldx);
 }
 
 // The same arithmetic with the row RESIDENT IN REGISTERS between the two passes (K <= 512 NCH: the FFN hidden, 8960 = 17.5 x 512, is
 // 18 x 16 bytes per lane): one read of the row instead of two.  Every chunk's load is issued before the first maximum is taken.
-template <int NCH>
-__global__ __launch_bounds__(256) void quantize_rows_reg_kernel(const bf16* __restrict__ x, int8_t* __restrict__ q,
-                                                                float* __restrict__ scale, int rows, int K, int ldx) {
+template <int NCH, bool F8>
+__device__ __forceinline__ void quantize_rows_reg_body(const bf16* __restrict__ x, int8_t* __restrict__ q, float* __restrict__ scale,
+                                                       int rows, int K, int ldx) {
   int lane = threadIdx.x & 63;
   int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (row >= rows) return;
@@ -384,7 +445,7 @@ __global__ __launch_bounds__(256) void quantize_rows_reg_kernel(const bf16* __re
     for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf((float)v[i][j]));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  float sc = mx > 0.f ? mx / 127.0f : 1.0f;
+  float sc = qrow_scale<F8>(mx);
   float inv = 1.0f / sc;
   if (lane == 0) scale[row] = sc;
   int8_t* qr = q + (size_t)row * K;
@@ -392,17 +453,19 @@ __global__ __launch_bounds__(256) void quantize_rows_reg_kernel(const bf16* __re
   for (int i = 0; i < NCH; ++i) {
     int k = lane * 8 + 512 * i;
     if (k >= K) continue;
-    unsigned lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int a = __float2int_rn((float)v[i][j] * inv), b = __float2int_rn((float)v[i][4 + j] * inv);
-      a = a < -127 ? -127 : (a > 127 ? 127 : a);
-      b = b < -127 ? -127 : (b > 127 ? 127 : b);
-      lo |= (unsigned)(a & 0xFF) << (8 * j);
-      hi |= (unsigned)(b & 0xFF) << (8 * j);
-    }
-    *reinterpret_cast<uint2*>(qr + k) = make_uint2(lo, hi);
+    *reinterpret_cast<uint2*>(qr + k) = qrow_codes8<F8>(v[i], inv);
   }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(256) void quantize_rows_reg_kernel(const bf16* __restrict__ x, int8_t* __restrict__ q,
+                                                                float* __restrict__ scale, int rows, int K, int ldx) {
+  quantize_rows_reg_body<NCH, false>(x, q, scale, rows, K, ldx);
+}
+template <int NCH>
+__global__ __launch_bounds__(256) void quantize_rows_f8_reg_kernel(const bf16* __restrict__ x, uint8_t* __restrict__ q,
+                                                                   float* __restrict__ scale, int rows, int K, int ldx) {
+  quantize_rows_reg_body<NCH, true>(x, (int8_t*)q, scale, rows, K, ldx);
 }
 
 // variant 2 = 256x128 / 3-stage ring, 3 = 256x256 (128x64 per wave), 5 = 256x192, 6 = 256x224;
@@ -430,10 +493,9 @@ static int pick_gemm_variant(int M, int N) {
   return variant;
 }
 
-// Which kernel instance and tile ll_gemm_bf16 / ll_gemm_w8a8 launch for this shape under the current tuning (host only;
+// Which kernel instance and tile ll_gemm_bf16 / ll_gemm_w8a8 / ll_gemm_f8 launch for this shape under the current tuning (host only;
 // bench.py's per-kernel table takes its kernel names from here instead of hard-coding them).
-extern "C" int ll_gemm_plan(int M, int N, int K, int int8, char* out, int cap) {
-  LL_REQUIRE(out != nullptr && cap > 0, "ll_gemm_plan: needs an output buffer");
+static void gemm_plan_text(int M, int N, const char* kind, char* out, int cap) {
   const int v = pick_gemm_variant(M, N);
   const int bn = v == 3 ? 256 : v == 5 ? 192 : v == 6 ? 224 : 128;
   char walk[48];
@@ -441,7 +503,20 @@ extern "C" int ll_gemm_plan(int M, int N, int K, int int8, char* out, int cap) {
   else snprintf(walk, sizeof walk, ", N fastest");
   const char* name = v == 2 ? "gemm_kernel_v2" : v == 3 ? "gemm_kernel_v3" : "gemm_kernel_v5";
   int ntm = (M + 255) / 256, ntn = (N + bn - 1) / bn;
-  snprintf(out, (size_t)cap, "%s<%s> tile 256x%d, %d workgroups%s", name, int8 ? "i8" : "bf16", bn, ntm * ntn, walk);
+  snprintf(out, (size_t)cap, "%s<%s> tile 256x%d, %d workgroups%s", name, kind, bn, ntm * ntn, walk);
+}
+
+extern "C" int ll_gemm_plan(int M, int N, int K, int int8, char* out, int cap) {
+  LL_REQUIRE(out != nullptr && cap > 0, "ll_gemm_plan: needs an output buffer");
+  gemm_plan_text(M, N, int8 ? "i8" : "bf16", out, cap);
+  (void)K;
+  return LL_OK;
+}
+
+// ll_gemm_f8 / ll_gemm_f8_qkv: always the HIP kernels (no generated FP8 form; gemm_asm bit 4 is int8-only)
+extern "C" int ll_gemm_plan_f8(int M, int N, int K, char* out, int cap) {
+  LL_REQUIRE(out != nullptr && cap > 0, "ll_gemm_plan_f8: needs an output buffer");
+  gemm_plan_text(M, N, "f8", out, cap);
   (void)K;
   return LL_OK;
 }
@@ -470,20 +545,20 @@ static bool gemm_asm_wanted(int epilogue) {
   return (g_gemm_asm & 1) && !((g_gemm_asm & 4) && epilogue == LL_EPI_BIAS_GELU) && !((g_gemm_asm & 8) && epilogue != LL_EPI_BIAS_GELU);
 }
 
-template <bool I8>
+template <int Q>
 static int launch_gemm(const void* x, const void* w, bf16* out, int M, int N, int K, size_t xrow_bytes, size_t wrow_bytes,
                        int ldo, int epilogue, const EpiArgs& ea, hipStream_t s) {
   // gemm_asm: bit 0 = generated kernels for the shapes they cover; bit 2 / bit 3 leave the GELU (256 x 224) / the 128-wide kernels
   // out (A/B of their share in the pipeline's power budget)
-  if (!I8 && gemm_asm_wanted(epilogue) && wrow_bytes == (size_t)K * 2) {
+  if (Q == GQ_BF16 && gemm_asm_wanted(epilogue) && wrow_bytes == (size_t)K * 2) {
     const int r = gemm_asm_launch((const bf16*)x, (const bf16*)w, out, M, N, K, (int)(xrow_bytes / 2), ldo, epilogue, ea, g_gemm_group_m, s);
     if (r) return r < 0 ? r : 0;                      // launched, or failed (error code); 0 = not covered: the HIP kernels below
   }
-  if (I8 && (g_gemm_asm & 16) && gemm_asm_wanted(epilogue) && xrow_bytes == (size_t)K && wrow_bytes == (size_t)K) {      // bit 4: W8A8 on the generated kernels
+  if (Q == GQ_I8 && (g_gemm_asm & 16) && gemm_asm_wanted(epilogue) && xrow_bytes == (size_t)K && wrow_bytes == (size_t)K) {      // bit 4: W8A8 on the generated kernels
     const int r = gemm_asm_launch_i8((const int8_t*)x, (const int8_t*)w, out, M, N, K, ldo, epilogue, ea, g_gemm_group_m, s);
     if (r) return r < 0 ? r : 0;
   }
-  const int kbytes = I8 ? K : 2 * K;
+  const int kbytes = Q == GQ_BF16 ? 2 * K : K;
   const int nk = kbytes / ROWB;
   const int variant = pick_gemm_variant(M, N);
   const bool v3 = (variant == 3);
@@ -498,21 +573,21 @@ static int launch_gemm(const void* x, const void* w, bf16* out, int M, int N, in
 #define LAUNCH(E)                                                                                                      \
   do {                                                                                                                 \
     if (v5 || v6) {                                                                                                    \
-      (void)ll_lds_attr((const void*)gemm_kernel_v5<E, I8, 2, 4, 8, 3>, 2 * (256 + 192) * ROWB);                       \
-      (void)ll_lds_attr((const void*)gemm_kernel_v5<E, I8, 4, 2, 4, 7>, 2 * (256 + 224) * ROWB);                       \
+      (void)ll_lds_attr((const void*)gemm_kernel_v5<E, Q, 2, 4, 8, 3>, 2 * (256 + 192) * ROWB);                       \
+      (void)ll_lds_attr((const void*)gemm_kernel_v5<E, Q, 4, 2, 4, 7>, 2 * (256 + 224) * ROWB);                       \
       if (v5)                                                                                                          \
-        hipLaunchKernelGGL((gemm_kernel_v5<E, I8, 2, 4, 8, 3>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk, \
+        hipLaunchKernelGGL((gemm_kernel_v5<E, Q, 2, 4, 8, 3>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk, \
                            xrow_bytes, wrow_bytes, ldo, ntm, ntn, gm, lds_epi, ea);                                                 \
       else                                                                                                             \
-        hipLaunchKernelGGL((gemm_kernel_v5<E, I8, 4, 2, 4, 7>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk, \
+        hipLaunchKernelGGL((gemm_kernel_v5<E, Q, 4, 2, 4, 7>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk, \
                            xrow_bytes, wrow_bytes, ldo, ntm, ntn, gm, lds_epi, ea);                                                 \
     } else if (v3) {                                                                                                   \
-      (void)ll_lds_attr((const void*)gemm_kernel_v3<E, I8>, (int)lds);                                                 \
-      hipLaunchKernelGGL((gemm_kernel_v3<E, I8>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk,   \
+      (void)ll_lds_attr((const void*)gemm_kernel_v3<E, Q>, (int)lds);                                                 \
+      hipLaunchKernelGGL((gemm_kernel_v3<E, Q>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk,   \
                          xrow_bytes, wrow_bytes, ldo, ntm, ntn, gm, lds_epi, ea);                                      \
     } else {                                                                                                           \
-      (void)ll_lds_attr((const void*)gemm_kernel_v2<E, I8>, (int)lds);                                          \
-      hipLaunchKernelGGL((gemm_kernel_v2<E, I8>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk, \
+      (void)ll_lds_attr((const void*)gemm_kernel_v2<E, Q>, (int)lds);                                          \
+      hipLaunchKernelGGL((gemm_kernel_v2<E, Q>), grid, block, lds, s, (const char*)x, (const char*)w, out, M, N, nk, \
                          xrow_bytes, wrow_bytes, ldo, ntm, ntn, gm, lds_epi, ea);                                      \
     }                                                                                                                  \
   } while (0)
@@ -552,7 +627,7 @@ extern "C" int ll_gemm_bf16(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b
   if (M == 0) return LL_OK;
   EpiArgs ea{(const bf16*)bias, (const bf16*)res, (const bf16*)e, (const bf16*)mod, nullptr, nullptr, nmod, gate_idx,
              rows_per_batch, frame_len, frame_len > 0 && rows_per_batch > 0 ? rows_per_batch / frame_len : 0};
-  if (int lrc = launch_gemm<false>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
+  if (int lrc = launch_gemm<GQ_BF16>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_bf16");
 }
 
@@ -611,7 +686,7 @@ extern "C" int ll_gemm_bf16_ksplit(const ll_bf16* x, const ll_bf16* w, const ll_
     if (r) return r < 0 ? r : ll_check_launch("ll_gemm_bf16_ksplit");
   }
   EpiArgs ea{(const bf16*)bias, (const bf16*)res, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-  if (int lrc = launch_gemm<false>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
+  if (int lrc = launch_gemm<GQ_BF16>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_bf16_ksplit");
 }
 
@@ -667,7 +742,7 @@ extern "C" int ll_gemm_plan_epi(int M, int N, int K, int int8, int epilogue, int
     const int wn = gemm_asm_width(M, N, K, K, epilogue, plain != 0, plain == 2, plain == 2 && (2 * (N / 3)) % 192 == 0, 1);
     if (wn) { gemm_asm_plan(M, N, wn, epilogue, out, cap, false); ll_plan_append_knobs(out, cap); return LL_OK; }
   }
-  if (int8 && (g_gemm_asm & 16) && gemm_asm_wanted(epilogue)) {      // bit 4: W8A8 calls on the generated kernels (launch_gemm<true>)
+  if (int8 && (g_gemm_asm & 16) && gemm_asm_wanted(epilogue)) {      // bit 4: W8A8 calls on the generated kernels (launch_gemm<GQ_I8>; never the FP8 calls)
     const int wn = gemm_asm_width_i8(M, N, K, epilogue, plain != 0, plain == 2, plain == 2 && (2 * (N / 3)) % 192 == 0, 1);
     if (wn) { gemm_asm_plan(M, N, wn, epilogue, out, cap, true); ll_plan_append_knobs(out, cap); return LL_OK; }
   }
@@ -685,7 +760,7 @@ extern "C" int ll_gemm_w8a8(const int8_t* xq, const float* sx, const int8_t* wq,
   if (M == 0) return LL_OK;
   EpiArgs ea{(const bf16*)bias, (const bf16*)res, (const bf16*)e, (const bf16*)mod, sx, sw, nmod, gate_idx,
              rows_per_batch, frame_len, frame_len > 0 && rows_per_batch > 0 ? rows_per_batch / frame_len : 0};
-  if (int lrc = launch_gemm<true>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
+  if (int lrc = launch_gemm<GQ_I8>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_w8a8");
 }
 
@@ -716,7 +791,7 @@ extern "C" int ll_gemm_bf16_qkv(const ll_bf16* x, const ll_bf16* w, const ll_bf1
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
   ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
   ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
-  if (int lrc = launch_gemm<false>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
+  if (int lrc = launch_gemm<GQ_BF16>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_bf16_qkv");
 }
 
@@ -733,7 +808,7 @@ extern "C" int ll_gemm_w8a8_qkv(const int8_t* xq, const float* sx, const int8_t*
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, sx, sw, 0, 0, 0, 0, 0};
   ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
   ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
-  if (int lrc = launch_gemm<true>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
+  if (int lrc = launch_gemm<GQ_I8>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_w8a8_qkv");
 }
 
@@ -748,6 +823,63 @@ extern "C" int ll_quantize_rows(const ll_bf16* x, int8_t* q, float* scale, int r
   else if (K <= 9216) hipLaunchKernelGGL(quantize_rows_reg_kernel<18>, grid, block, 0, s, (const bf16*)x, q, scale, rows, K, ldx);
   else hipLaunchKernelGGL(quantize_rows_kernel, grid, block, 0, s, (const bf16*)x, q, scale, rows, K, ldx);
   return ll_check_launch("ll_quantize_rows");
+}
+
+// ---- FP8 rowwise: e4m3fn codes [rows, K] + one fp32 scale per row (mx.h), on the W8A8 kernels' structure (Ty<GQ_F8>)
+static int f8_check(const char* fn, const void* xq, const void* sx, const void* wq, const void* sw, const void* out, int M, int N, int K,
+                    int ldo) {
+  LL_REQUIRE(xq && sx && wq && sw, "%s: codes and scales of both operands are required", fn);
+  LL_REQUIRE(out != nullptr, "%s: out is required", fn);
+  LL_REQUIRE(K > 0 && K % 128 == 0, "%s: K=%d must be a positive multiple of 128", fn, K);
+  LL_REQUIRE(M >= 0, "%s: M=%d", fn, M);
+  LL_REQUIRE(ldo % 8 == 0, "%s: ldo=%d must be a multiple of 8", fn, ldo);
+  return LL_OK;
+}
+
+extern "C" int ll_gemm_f8(const uint8_t* xq, const float* sx, const uint8_t* wq, const float* sw, const ll_bf16* bias, ll_bf16* out,
+                          int M, int N, int K, int ldo, int epilogue, const ll_bf16* res, const ll_bf16* e, const ll_bf16* mod,
+                          int nmod, int gate_idx, int rows_per_batch, int frame_len, ll_stream stream) {
+  int rc = f8_check("ll_gemm_f8", xq, sx, wq, sw, out, M, N, K, ldo);
+  if (rc) return rc;
+  rc = check_epilogue("ll_gemm_f8", M, N, ldo, epilogue, bias, res, e, mod, nmod, gate_idx, rows_per_batch, frame_len);
+  if (rc) return rc;
+  if (M == 0) return LL_OK;
+  EpiArgs ea{(const bf16*)bias, (const bf16*)res, (const bf16*)e, (const bf16*)mod, sx, sw, nmod, gate_idx,
+             rows_per_batch, frame_len, frame_len > 0 && rows_per_batch > 0 ? rows_per_batch / frame_len : 0};
+  if (int lrc = launch_gemm<GQ_F8>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
+  return ll_check_launch("ll_gemm_f8");
+}
+
+extern "C" int ll_gemm_f8_qkv(const uint8_t* xq, const float* sx, const uint8_t* wq, const float* sw, const ll_bf16* bias,
+                              ll_bf16* out, int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start,
+                              int roped_offset, int write_len, ll_stream stream) {
+  int rc = f8_check("ll_gemm_f8_qkv", xq, sx, wq, sw, out, M, N, K, ldo);
+  if (rc) return rc;
+  rc = check_epilogue("ll_gemm_f8_qkv", M, N, ldo, LL_EPI_BIAS, bias, nullptr, nullptr, nullptr, 0, 0, 0, 0);
+  if (rc) return rc;
+  rc = check_v_insert("ll_gemm_f8_qkv", M, N, B, L, S, write_start, roped_offset, write_len, cache_v);
+  if (rc) return rc;
+  if (M == 0) return LL_OK;
+  EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, sx, sw, 0, 0, 0, 0, 0};
+  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
+  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+  if (int lrc = launch_gemm<GQ_F8>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
+  return ll_check_launch("ll_gemm_f8_qkv");
+}
+
+extern "C" int ll_quantize_rows_f8(const ll_bf16* x, uint8_t* q, float* scale, int rows, int K, int ldx, ll_stream stream) {
+  LL_REQUIRE(x != nullptr && q != nullptr && scale != nullptr, "ll_quantize_rows_f8: x, codes and scales are required");
+  LL_REQUIRE(K > 0 && K % 8 == 0, "ll_quantize_rows_f8: K=%d must be a positive multiple of 8", K);
+  LL_REQUIRE(ldx >= K && ldx % 8 == 0, "ll_quantize_rows_f8: ldx=%d must be >= K and a multiple of 8", ldx);
+  LL_REQUIRE(rows >= 0, "ll_quantize_rows_f8: rows=%d", rows);
+  if (rows == 0) return LL_OK;
+  const dim3 grid((rows + 3) / 4), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  // ll_quantize_rows' dispatch: rows of up to 9216 elements stay in registers between the maximum and the rounding pass
+  if (K <= 2048) hipLaunchKernelGGL(quantize_rows_f8_reg_kernel<4>, grid, block, 0, s, (const bf16*)x, q, scale, rows, K, ldx);
+  else if (K <= 9216) hipLaunchKernelGGL(quantize_rows_f8_reg_kernel<18>, grid, block, 0, s, (const bf16*)x, q, scale, rows, K, ldx);
+  else hipLaunchKernelGGL(quantize_rows_f8_kernel, grid, block, 0, s, (const bf16*)x, q, scale, rows, K, ldx);
+  return ll_check_launch("ll_quantize_rows_f8");
 }
 
 extern "C" int ll_linear_small(const ll_bf16* x, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, int M, int N,

@@ -5,14 +5,19 @@
 #define BN 128
 #define ROWB 128                    // LDS / staging row = 128 bytes of k
 typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+
+// Operand kinds of the GEMM family: bf16, W8A8 int8, FP8 rowwise (e4m3fn codes).  The two 8-bit kinds share the 1-byte LDS rows and
+// the scaled epilogue (per-row activation scale x per-output-channel weight scale).
+enum { GQ_BF16 = 0, GQ_I8 = 1, GQ_F8 = 2 };
 
 struct EpiArgs {
   const bf16* bias;
   const bf16* res;
   const bf16* e;
   const bf16* mod;
-  const float* sx;                  // int8: per-row activation scale [M]
-  const float* sw;                  // int8: per-output-channel weight scale [N]
+  const float* sx;                  // int8 / fp8: per-row activation scale [M]
+  const float* sw;                  // int8 / fp8: per-output-channel weight scale [N]
   int nmod, gate_idx, rows_per_batch, frame_len, F;
   // Fused QKV projection: output columns >= v_col0 (the V third) go straight into the KV cache instead of the output buffer,
   // token t of batch b to cache row v_write_start + (t - v_roped_offset) when that index is in [0, v_write_len)
@@ -29,10 +34,10 @@ __device__ __forceinline__ bf16* epi_dest(const EpiArgs& ea, bf16* __restrict__ 
   return ea.v_out + ((size_t)bb * ea.v_S + ea.v_write_start + wi) * (size_t)ea.v_C + (n - ea.v_col0);
 }
 
-template <bool I8>
+template <int Q>
 struct Ty;
 template <>
-struct Ty<false> {
+struct Ty<GQ_BF16> {
   typedef bf16x8 frag;
   typedef f32x4 acc;
   static __device__ __forceinline__ acc mma(frag a, frag b, acc c) {
@@ -40,7 +45,7 @@ struct Ty<false> {
   }
 };
 template <>
-struct Ty<true> {
+struct Ty<GQ_I8> {
   // A and B fragments are fetched with the SAME (row, 16-byte chunk) addressing, so whatever order the instruction
   // assigns to the 16 k-values inside a lane's fragment, products pair equal k: the exact int32 sum is layout-agnostic.
   typedef i32x4 frag;
@@ -49,6 +54,25 @@ struct Ty<true> {
     return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
   }
 };
+template <>
+struct Ty<GQ_F8> {
+  // One 128-byte LDS stage is ONE 16x16x128 MFMA: the fragment joins the two 16-byte chunks the int8 loop feeds to two MFMAs (chunks
+  // fg and 4 + fg, frag_f8).  The same pairing argument as int8 holds, so the lane map of the operands does not matter; every scale
+  // byte is E8M0 127 (2^0): a plain e4m3 x e4m3 product at the scaled instruction's doubled rate (the non-scaled fp8 MFMAs of gfx950
+  // run at the bf16 rate).  The per-row / per-channel scales are applied in the epilogue, as for int8.
+  typedef i32x8 frag;
+  typedef f32x4 acc;
+  static __device__ __forceinline__ acc mma(frag a, frag b, acc c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
+  }
+};
+
+// FP8 fragment of LDS row r (the XOR-swizzled 128-byte rows of stage_rows): chunks fg and 4 + fg of the row, joined.
+__device__ __forceinline__ i32x8 frag_f8(const char* __restrict__ base, int r, int fg) {
+  i32x4 lo = *reinterpret_cast<const i32x4*>(base + r * ROWB + ((fg ^ (r & 7)) << 4));
+  i32x4 hi = *reinterpret_cast<const i32x4*>(base + r * ROWB + (((fg + 4) ^ (r & 7)) << 4));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -74,9 +98,10 @@ __device__ __forceinline__ void stage_rows(const char* __restrict__ src, size_t 
 // from clamped addresses (rows past M re-read row M-1, columns past N re-read the last 4 columns; never stored), so the
 // MT x NTL residual loads of a lane are ONE round trip.  Guarded by `if (m >= M) continue` they were MT dependent round
 // trips of ~1 us each at the end of every O / cross-O / FFN2 launch.
-template <int EPI, bool I8, int NTL, int MT>
-__device__ __forceinline__ void gemm_epilogue(typename Ty<I8>::acc (&acc)[NTL][MT], bf16* __restrict__ Y, int M, int N,
+template <int EPI, int Q, int NTL, int MT>
+__device__ __forceinline__ void gemm_epilogue(typename Ty<Q>::acc (&acc)[NTL][MT], bf16* __restrict__ Y, int M, int N,
                                               int ldo, int mw, int nw, int fr, int fg, const EpiArgs& ea) {
+  constexpr bool I8 = Q != GQ_BF16;          // scaled epilogue (int8 and fp8 alike: acc * (sx * sw))
   constexpr bool RES = (EPI == LL_EPI_BIAS_GATE_RES || EPI == LL_EPI_BIAS_RES);
   constexpr bool GATE = (EPI == LL_EPI_BIAS_GATE_RES);
   int nc[NTL];
@@ -91,7 +116,8 @@ __device__ __forceinline__ void gemm_epilogue(typename Ty<I8>::acc (&acc)[NTL][M
     if (I8) swv[a] = *reinterpret_cast<const f32x4*>(ea.sw + nc[a]);
   }
   // m-subtiles per batch of loads: <= 16 (m, n) subtiles in flight per lane, or the wide tilings' epilogues spill
-  constexpr int CH = NTL > 4 ? 2 : (MT > 4 ? 4 : MT);
+  // (FP8 gate-residual: half that batch -- at int8's, the FP8 instances of the 256 x 256 and 256 x 224 tilings spill)
+  constexpr int CH = (Q == GQ_F8 && GATE) ? (NTL > 4 ? 1 : (MT > 4 ? 2 : MT)) : NTL > 4 ? 2 : (MT > 4 ? 4 : MT);
   static_assert(MT % CH == 0, "epilogue batches must tile MT");
 #pragma unroll
   for (int b0 = 0; b0 < MT; b0 += CH) {
@@ -165,9 +191,10 @@ __device__ __forceinline__ void gemm_epilogue(typename Ty<I8>::acc (&acc)[NTL][M
 
 // (Loading the residual rows at kernel entry instead, 32 registers held across the K-loop, measured no gain: 72.4-72.7 vs
 // 72.4-72.7 frames/s in an interleaved A/B -- the read is short once it is whole lines; not kept.)
-template <int EPI, bool I8, int NTL, int MT>
-__device__ __forceinline__ void gemm_epilogue_lds(typename Ty<I8>::acc (&acc)[NTL][MT], bf16* __restrict__ Y, int M, int N,
+template <int EPI, int Q, int NTL, int MT>
+__device__ __forceinline__ void gemm_epilogue_lds(typename Ty<Q>::acc (&acc)[NTL][MT], bf16* __restrict__ Y, int M, int N,
                                                   int ldo, int mw, int nw, int lane, char* __restrict__ ep, const EpiArgs& ea) {
+  constexpr bool I8 = Q != GQ_BF16;          // scaled epilogue (int8 and fp8 alike: acc * (sx * sw))
   constexpr bool RES = (EPI == LL_EPI_BIAS_GATE_RES || EPI == LL_EPI_BIAS_RES);
   constexpr bool GATE = (EPI == LL_EPI_BIAS_GATE_RES);
   constexpr int RS = EPI_ROW_BYTES(NTL), CP = NTL * 2, R = MT * 16, NIT = R * CP / 64;
@@ -271,9 +298,9 @@ __device__ __forceinline__ void tile_of(int lid, int ntm, int ntn, int gm, int& 
   nt = w / gs;
 }
 
-template <bool I8>
-__device__ __forceinline__ typename Ty<I8>::acc acc_zero() {
-  typename Ty<I8>::acc z = {0, 0, 0, 0};
+template <int Q>
+__device__ __forceinline__ typename Ty<Q>::acc acc_zero() {
+  typename Ty<Q>::acc z = {0, 0, 0, 0};
   return z;
 }
 

@@ -18,7 +18,6 @@
 #include "gemm_common.h"
 #include "mx.h"
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 #define MX_BM 256
 #define MX_BN 128
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = acc_zero<false>();
+    for (int b = 0; b < 4; ++b) acc[a][b] = acc_zero<GQ_BF16>();
 
   // scale bytes of this lane's rows: (row, K-block kt * 4 + fg); rows past the edge re-read the last row (never stored)
   const uint8_t* sxr[4];
@@ -146,10 +145,10 @@ __global__ __launch_bounds__(512, 1) void gemm_mx_kernel(const uint8_t* __restri
   if (MXOUT) {
     gemm_epilogue_gelu_mx(acc, QO, SO, M, N, m0 + wm * 64, n0 + wn * 64, fr, fg, ea.bias);
   } else if (EPI == LL_EPI_BIAS_GELU) {     // (register form, as the bf16 GELU call takes it by default: same values either way)
-    gemm_epilogue<EPI, false, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, fr, fg, ea);
+    gemm_epilogue<EPI, GQ_BF16, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, fr, fg, ea);
   } else {
     __builtin_amdgcn_s_barrier();           // every wave has read its last K-step's fragments: the ring is free
-    gemm_epilogue_lds<EPI, false, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, lane, smem + wave * (64 * EPI_ROW_BYTES(4)), ea);
+    gemm_epilogue_lds<EPI, GQ_BF16, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, lane, smem + wave * (64 * EPI_ROW_BYTES(4)), ea);
   }
 }
 

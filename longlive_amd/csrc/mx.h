@@ -39,3 +39,17 @@ __host__ __device__ __forceinline__ uint32_t mx_code(float x, int e) {
 __host__ __device__ __forceinline__ uint32_t mx_code4(float x0, float x1, float x2, float x3, int e) {
   return mx_code(x0, e) | (mx_code(x1, e) << 8) | (mx_code(x2, e) << 16) | (mx_code(x3, e) << 24);
 }
+
+// ---- FP8 rowwise (ll_quantize_rows_f8 and the producers' f8 forms): one fp32 scale per row, sc = amax / 448 (1 for an all-zero row),
+// code = e4m3fn(RNE(clamp(x * (1 / sc), -448, 448))), subnormals kept.  v_cvt_pk_fp8_f32 rounds to nearest even and keeps e4m3
+// subnormals but does not saturate (above 448 it writes NaN), hence the clamp; its first operand lands in the low byte.
+#define F8_MAX 448.0f
+
+__device__ __forceinline__ float f8_clamp(float v) { return fminf(fmaxf(v, -F8_MAX), F8_MAX); }
+
+// four codes of (already scaled) values packed into a little-endian word (a in byte 0)
+__device__ __forceinline__ uint32_t f8_code4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(a), f8_clamp(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(c), f8_clamp(d), w, true);
+  return (uint32_t)w;
+}

@@ -938,6 +938,142 @@ def gemm_plan_mx(M: int, N: int, K: int) -> str:
     return buf.value.decode()
 
 
+# ---- FP8 rowwise (e4m3fn codes [rows, K] as uint8 + one float32 scale per row; include/longlive_hip.h ll_quantize_rows_f8) ---------
+def _f8_empty(shape, device):
+    K = shape[-1]
+    rows = math.prod(shape) // K
+    return torch.empty(shape, dtype=u8, device=device), torch.empty(rows, dtype=torch.float32, device=device)
+
+
+def quantize_rows_f8(x, tag: str = "quantize_rows_f8"):
+    """FP8 rowwise quantisation of a [..., K] bf16 tensor -> (e4m3fn codes as uint8 [..., K], float32 scale [rows]):
+    scale = max|x| / 448 per row, code = e4m3fn(clamp(x / scale, +-448))."""
+    _chk(x, "x")
+    K = x.shape[-1]
+    rows = x.numel() // K
+    q, sc = _f8_empty(tuple(x.shape), x.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_quantize_rows_f8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, K, K, _stream()), "ll_quantize_rows_f8")
+    _t1(tag, t0, 3.0 * x.numel())
+    return q, sc
+
+
+def _f8_operand(q, sc, name: str):
+    _chk(q, name, u8); _chk(sc, name + " scales", torch.float32)
+    K = q.shape[-1]
+    rows = q.numel() // K
+    assert sc.numel() == rows, (q.shape, sc.shape)
+    return rows, K
+
+
+def gemm_f8(xq, sx, wq, sw, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
+            rows_per_batch: int = 0, frame_len: int = 0, tag: str = "gemm"):
+    """out[M,N] = epilogue(sx[m] sw[n] sum_k dec(xq[m,k]) dec(wq[n,k]) + bias): gemm_w8a8 with e4m3fn codes (uint8) and fp32
+    accumulation."""
+    M, K = _f8_operand(xq, sx, "xq")
+    N, Kw = _f8_operand(wq, sw, "wq")
+    _chk(bias, "bias")
+    assert Kw == K and wq.shape == (N, K) and bias.numel() == N, (wq.shape, K, bias.shape)
+    if out is None:
+        out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
+    _chk(out, "out")
+    assert out.numel() == M * N
+    nmod = 0
+    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
+        _chk(res, "res")
+        assert res.numel() == M * N
+    if epilogue == EPI_BIAS_GATE_RES:
+        _chk(e, "e")
+        nmod = e.shape[-2]
+        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
+        if mod is not None:
+            _chk(mod, "mod")
+            assert mod.numel() == nmod * N
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_gemm_f8(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, N,
+                              epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()), "ll_gemm_f8")
+    _t1(tag, t0, 2.0 * M * N * K)
+    return out
+
+
+def gemm_f8_qkv_v_insert(xf, wf, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int, tag: str = "gemm_qkv"):
+    """gemm_qkv_v_insert on FP8 rowwise operands: xf = (codes [B*L or B,L, K], scales [B*L]), wf = (codes [3C, K], scales [3C]).
+    Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v [B, S, H, D]."""
+    xq, sx = xf
+    wq, sw = wf
+    M, K = _f8_operand(xq, sx, "xq")
+    N, Kw = _f8_operand(wq, sw, "wq")
+    _chk(bias, "bias"); _chk(cache_v, "cache_v")
+    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
+    S = cache_v.shape[1]
+    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
+    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_gemm_f8_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                  M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
+               "ll_gemm_f8_qkv")
+    _t1(tag, t0, 2.0 * M * N * K)
+    return out
+
+
+def ln_modulate_f8(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate emitting the FP8 rowwise codes + row scales of its bf16 output."""
+    _chk(x, "x"); _chk(e, "e")
+    B, L, Cc = x.shape
+    nmod = e.shape[-2]
+    assert e.shape == (B, num_frames, nmod, Cc)
+    if mod is not None:
+        _chk(mod, "mod")
+        assert mod.numel() == nmod * Cc
+    q, sc = _f8_empty((B, L, Cc), x.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_ln_modulate_f8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
+                                     B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_f8")
+    _t1(tag, t0, 3.0 * x.numel())
+    return q, sc
+
+
+def ln_modulate_tab_f8(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate_tab emitting the FP8 rowwise codes + row scales of its bf16 output."""
+    _chk(x, "x"); _chk(tab, "tab", torch.float32)
+    B, L, Cc = x.shape
+    nmod = tab.shape[2]
+    assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
+    q, sc = _f8_empty((B, L, Cc), x.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_ln_modulate_tab_f8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
+                                         B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab_f8")
+    _t1(tag, t0, 3.0 * B * L * Cc)
+    return q, sc
+
+
+def layernorm_affine_f8(x, w, b, eps: float):
+    """layernorm_affine emitting the FP8 rowwise codes + row scales of its bf16 output."""
+    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
+    Cc = x.shape[-1]
+    assert w.numel() == Cc and b.numel() == Cc
+    q, sc = _f8_empty(tuple(x.shape), x.device)
+    lib = _lib.load()
+    t0 = _t0("layernorm_affine")
+    _lib.check(lib.ll_layernorm_affine_f8(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), sc.data_ptr(), x.numel() // Cc, Cc,
+                                          eps, _stream()), "ll_layernorm_affine_f8")
+    _t1("layernorm_affine", t0, 3.0 * x.numel())
+    return q, sc
+
+
+def gemm_plan_f8(M: int, N: int, K: int) -> str:
+    """Kernel instance, tile and grid of a gemm_f8 / gemm_f8_qkv_v_insert call (host only)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().ll_gemm_plan_f8(M, N, K, buf, 256), "ll_gemm_plan_f8")
+    return buf.value.decode()
+
+
 # ---- MXFP8 self-attention over a block-scaled shadow of the KV cache (attention_mx.hip) ------------------------------------------
 def kv_shadow_mx_alloc(cache_k) -> dict:
     """Uninitialised MX shadow of one layer's cache k (or v) [B, S, H, 128]: K^ codes [B, S32, H, 128] + scales [B, S32, H, 4],

@@ -6,9 +6,14 @@ Two steady-state forwards of the 30-layer LongLive-1.3B (random init, cache full
 in none+attn mode (bf16 linears, set_attn_quant("mxfp8")).  The first forward allocates each layer's shadow and re-derives all of it
 (one kv_shadow_mx_kernel launch per layer, covering the roll and the insert); the second refreshes the rolled window and the inserted
 tokens as one merged range per layer.  Expected: 60 flash_attn_mx_kernel, 60 kv_shadow_mx_kernel, no flash_attn_asm_kernel (the
-self-attention kernel of bf16 mode; cross-attention keeps flash_attn_asm_qn_kernel)."""
+self-attention kernel of bf16 mode; cross-attention keeps flash_attn_asm_qn_kernel).
+
+--quant / --attn-quant pick other modes for the same two forwards, e.g. the FP8 rowwise trace:
+
+    rocprofv3 --kernel-trace --stats -d <dir> -o run -- python tools/mx_attn_trace.py --quant fp8_rowwise --attn-quant none"""
 from __future__ import annotations
 
+import argparse
 import os
 import sys
 
@@ -16,7 +21,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quant", default="none", help="block linears: none | int8 | mxfp8 | fp8_rowwise")
+    ap.add_argument("--attn-quant", default="mxfp8", help="self-attention: none | mxfp8")
+    args = ap.parse_args(argv)
     import torch
     from longlive_amd import synth
     from longlive_amd.wan_wrapper import WanDiffusionWrapper
@@ -28,7 +37,8 @@ def main():
     for mod in gen.model.modules():
         if hasattr(mod, "max_attention_size"):
             mod.max_attention_size = S
-    gen.model.set_attn_quant("mxfp8")
+    gen.model.set_quant(None if args.quant == "none" else args.quant)
+    gen.model.set_attn_quant(None if args.attn_quant == "none" else args.attn_quant)
     bf = torch.bfloat16
     kv = []
     for i in range(cfg.num_layers):
@@ -43,7 +53,7 @@ def main():
         gen(noise[:, 3 * f: 3 * f + 3], prompt, torch.full((1, 3), 625.0, device=dev), kv_cache=kv, crossattn_cache=ca,
             current_start=S + 3 * f * fs)
     torch.cuda.synchronize()
-    print("mx_attn_trace: 2 forwards done")
+    print(f"mx_attn_trace: 2 forwards done (quant {args.quant}, attn_quant {args.attn_quant})")
 
 
 if __name__ == "__main__":
