@@ -46,8 +46,10 @@ enum ll_epilogue {
  * ll_flash_attn, the split-K hand-off entry points); 106 = round 5 (ll_conv_cl_rms added); 107 = MXFP8 block linears;
  * 108 = MXFP8 self-attention (ll_kv_shadow_mx, ll_flash_attn_mx, ll_flash_attn_mx_plan);
  * 109 = FP8 rowwise block linears (ll_quantize_rows_f8, ll_gemm_f8, ll_gemm_f8_qkv, ll_ln_modulate_f8, ll_ln_modulate_tab_f8,
- * ll_layernorm_affine_f8, ll_gemm_plan_f8). */
-#define LL_ABI_VERSION 109
+ * ll_layernorm_affine_f8, ll_gemm_plan_f8);
+ * 110 = MXFP6 block linears (ll_quantize_mx6, ll_gemm_mx6, ll_gemm_mx6_qkv, ll_ln_modulate_mx6, ll_ln_modulate_tab_mx6,
+ * ll_layernorm_affine_mx6, ll_gemm_plan_mx6). */
+#define LL_ABI_VERSION 110
 int ll_version(void);
 const char* ll_last_error(void);
 /* Development knob for A/B timing of kernel variants (tools/kbench, tools/kenergy, LL_TUNING=key=value,... for bench.py);
@@ -220,6 +222,37 @@ int ll_ln_modulate_tab_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float
 int ll_layernorm_affine_mx(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
                            float eps, ll_stream stream);
 int ll_gemm_plan_mx(int M, int N, int K, char* out, int cap);
+
+/* MXFP6 mode of the block linears (v_mfma_scale_f32_16x16x128_f8f6f4 with both operands OCP FP6 E2M3: the FP4 rate, twice the int8 /
+ * FP8 modes').  A row is quantised along K in blocks of 32: amax = m 2^p (frexp), e = p - 3 + (m > 0.9375) clamped to [-127, 127]
+ * (the smallest e with amax <= 7.5 2^e, so no code saturates), scale byte e + 127 (E8M0; an all-zero block stores 127), codes
+ * E2M3(RNE(x 2^-e)) with subnormals kept (steps of 0.125, maximum 7.5).  Scales [rows, K / 32] (uint8), row-major.
+ * Codes [rows, 3K / 4] bytes, K % 256 == 0, packed 6 bits per code in 192-byte super-blocks of 256 k: the 32-k block j = 0..7 of a
+ * super-block (k 32 j .. 32 j + 31, one scale block) occupies the 24 bytes at 48 (j % 4) + 24 (j / 4), code i of the block in bits
+ * 6 i .. 6 i + 5 of that little-endian 192-bit word.  (The 48 bytes at 48 g are then blocks g and g + 4: the two 16x16x128 K-steps'
+ * operand fragments of MFMA lane group g, read as one contiguous piece.)
+ *   ll_quantize_mx6: bf16 rows (stride ldx elements) -> codes + scales, one launch; K % 256 == 0.
+ *   ll_gemm_mx6:     out = epilogue(sum_k (cx 2^ex)(cw 2^ew) + bias) with ll_gemm_bf16's epilogues and rounding points; K % 256 == 0.
+ *                    With the GELU epilogue, q_out / s_out (instead of out) receive the MXFP6 codes + scales of the bf16 GELU output
+ *                    (N % 256 == 0, ldo == N), bit-identical to ll_quantize_mx6 of the bf16 result.  Exactly one form is given.
+ *   ll_gemm_mx6_qkv: ll_gemm_bf16_qkv's fused q|k|v projection (V third into cache_v) on MXFP6 operands.
+ *   ll_ln_modulate_mx6 / ll_ln_modulate_tab_mx6 / ll_layernorm_affine_mx6: the producers of the same names emitting MXFP6 codes +
+ *                    scales of their bf16 output (bit-identical to ll_quantize_mx6 of it); C % 256 == 0.
+ *   ll_gemm_plan_mx6: kernel instance, tile and grid of an ll_gemm_mx6 / ll_gemm_mx6_qkv call (host only). */
+int ll_quantize_mx6(const ll_bf16* x, uint8_t* q, uint8_t* qs, int rows, int K, int ldx, ll_stream stream);
+int ll_gemm_mx6(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                uint8_t* q_out, uint8_t* s_out, int M, int N, int K, int ldo, int epilogue, const ll_bf16* res, const ll_bf16* e,
+                const ll_bf16* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len, ll_stream stream);
+int ll_gemm_mx6_qkv(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                    int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset,
+                    int write_len, ll_stream stream);
+int ll_ln_modulate_mx6(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod, int shift_idx,
+                       int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_ln_modulate_tab_mx6(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx, int scale_idx,
+                           int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_layernorm_affine_mx6(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
+                            float eps, ll_stream stream);
+int ll_gemm_plan_mx6(int M, int N, int K, char* out, int cap);
 
 /* FP8 rowwise mode of the block linears (set_quant("fp8_rowwise")): ll_gemm_w8a8's per-token / per-output-channel scheme with OCP e4m3fn
  * codes instead of int8.  Per row (a token of the activations, an output channel of a [N, K] weight): amax = max |x| over its bf16

@@ -144,7 +144,8 @@ class CausalWanModelHIP(nn.Module):
         # None: bf16 linears (the reference's precision).  "int8": W8A8 for the six per-token linears of every block
         # (BASELINE config 5; per-token activation scales, per-output-channel weight scales, int32 accumulation).  "mxfp8": the same
         # six on the block-scaled e4m3 MFMA (one power-of-two scale per 32 elements of K for activations and weights alike).
-        # "fp8_rowwise": int8's per-token / per-output-channel scales with e4m3 codes, on the W8A8 kernels' structure.
+        # "fp8_rowwise": int8's per-token / per-output-channel scales with e4m3 codes, on the W8A8 kernels' structure.  "mxfp6": mxfp8's
+        # per-32 block scales with E2M3 (FP6) codes packed 6 bits each, on the MFMA's FP4-rate form.
         self.quant: Optional[str] = None
         # None: bf16 self-attention.  "mxfp8": self-attention on the block-scaled e4m3 MFMA over an MX shadow of each layer's KV cache
         # (kept in the cache dict under _MX_SHADOW, re-derived after every write; orthogonal to `quant`).
@@ -201,7 +202,7 @@ class CausalWanModelHIP(nn.Module):
         for blk in self.blocks:
             sa = blk.self_attn
             ts = [sa.q.weight, sa.k.weight, sa.v.weight, sa.q.bias, sa.k.bias, sa.v.bias, blk.modulation]
-            if self.quant in ("int8", "mxfp8", "fp8_rowwise"):
+            if self.quant in ("int8", "mxfp8", "fp8_rowwise", "mxfp6"):
                 ts += [sa.o.weight, blk.cross_attn.q.weight, blk.cross_attn.o.weight, blk.ffn[0].weight, blk.ffn[2].weight]
             key.extend((t.data_ptr(), t._version) for t in ts)
         return tuple(key)
@@ -220,7 +221,8 @@ class CausalWanModelHIP(nn.Module):
                 mod=blk.modulation.detach().reshape(6, -1).contiguous(),
             )
             if self.quant is not None:
-                quantize = {"int8": ops.quantize_rows, "mxfp8": ops.quantize_mx, "fp8_rowwise": ops.quantize_rows_f8}[self.quant]
+                quantize = {"int8": ops.quantize_rows, "mxfp8": ops.quantize_mx, "fp8_rowwise": ops.quantize_rows_f8,
+                            "mxfp6": ops.quantize_mx6}[self.quant]
                 for name, w in (("qkv", d["wqkv"]), ("o", sa.o.weight), ("cq", ca.q.weight), ("co", ca.o.weight),
                                 ("f1", blk.ffn[0].weight), ("f2", blk.ffn[2].weight)):
                     d["q_" + name], d["s_" + name] = quantize(w.detach().contiguous())
@@ -231,12 +233,14 @@ class CausalWanModelHIP(nn.Module):
         return P
 
     def set_quant(self, mode: Optional[str]):
-        """None (bf16), "int8" (W8A8 block linears), "mxfp8" (MXFP8 block linears) or "fp8_rowwise" (e4m3 codes with per-token /
-        per-output-channel scales).  Weights are (re)quantised lazily at the next forward."""
-        if mode not in (None, "int8", "mxfp8", "fp8_rowwise"):
+        """None (bf16), "int8" (W8A8 block linears), "mxfp8" (MXFP8 block linears), "fp8_rowwise" (e4m3 codes with per-token /
+        per-output-channel scales) or "mxfp6" (MXFP6 E2M3 block linears).  Weights are (re)quantised lazily at the next forward."""
+        if mode not in (None, "int8", "mxfp8", "fp8_rowwise", "mxfp6"):
             raise ValueError(f"unknown quantisation mode {mode!r}")
         if mode is not None and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
             raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 128")
+        if mode == "mxfp6" and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
+            raise ValueError("mxfp6 linears need dim and ffn_dim to be multiples of 256 (packed 256-k super-blocks)")
         self.quant = mode
         self._packed = None
         return self
@@ -267,6 +271,9 @@ class CausalWanModelHIP(nn.Module):
         """One block linear: bf16 MFMA GEMM, or W8A8 GEMM in int8 mode (same fused epilogues).  In int8 mode `x` is either
         a bf16 tensor (quantised here, per token) or an already quantised (int8, scale) pair from a fused producer; in mxfp8 mode
         likewise a bf16 tensor or an (e4m3 codes, block scales) pair, and in fp8_rowwise mode an (e4m3 codes, row scale) pair."""
+        if self.quant == "mxfp6":
+            xm = x if isinstance(x, tuple) else ops.quantize_mx6(x)
+            return ops.gemm_mx6(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
         if self.quant == "fp8_rowwise":
             xq, sx = x if isinstance(x, tuple) else ops.quantize_rows_f8(x)
             return ops.gemm_f8(xq, sx, pk["q_" + key], pk["s_" + key], b, epilogue, tag="gemm_" + key, **kw)
@@ -372,6 +379,7 @@ class CausalWanModelHIP(nn.Module):
         q8 = self.quant == "int8"
         mx = self.quant == "mxfp8"
         f8 = self.quant == "fp8_rowwise"
+        m6 = self.quant == "mxfp6"
         G, E = _kv_state(kvc)
         S = kvc["k"].shape[1]
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
@@ -385,6 +393,8 @@ class CausalWanModelHIP(nn.Module):
             ops.kv_roll(kvc["k"], kvc["v"], *plan.roll)
         if mx:
             h1 = ops.ln_modulate_tab_mx(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 0, 1, F, c.eps)
+        elif m6:
+            h1 = ops.ln_modulate_tab_mx6(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx6(xs, e0, mod, 0, 1, F, c.eps)
         elif f8:
             h1 = ops.ln_modulate_tab_f8(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_f8(xs, e0, mod, 0, 1, F, c.eps)
         elif tab32 is not None:
@@ -395,6 +405,9 @@ class CausalWanModelHIP(nn.Module):
             if mx:
                 qkv = ops.gemm_mx_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
                                                plan.roped_offset, plan.write_len, B, L)
+            elif m6:
+                qkv = ops.gemm_mx6_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
+                                                plan.roped_offset, plan.write_len, B, L)
             elif f8:
                 qkv = ops.gemm_f8_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
                                                plan.roped_offset, plan.write_len, B, L)
@@ -430,7 +443,7 @@ class CausalWanModelHIP(nn.Module):
         self._lin(att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=2, rows_per_batch=L, frame_len=fs)
         # --- cross attention (causal_model.py:460; model.py:159-194) ---
-        xn = (ops.layernorm_affine_mx if mx else ops.layernorm_affine_f8 if f8 else ops.layernorm_affine_q8 if q8 else
+        xn = (ops.layernorm_affine_mx if mx else ops.layernorm_affine_mx6 if m6 else ops.layernorm_affine_f8 if f8 else ops.layernorm_affine_q8 if q8 else
               ops.layernorm_affine)(xs, blk.norm3.weight, blk.norm3.bias, c.eps)
         fuse_qn = (self.fuse_cross_qnorm and self.quant is None and ops.gemm_ssq_planes(B * L, C, C) == Hh and ops.flash_attn_qnorm_ok(Hh, c.text_len))
         if fuse_qn:
@@ -453,14 +466,16 @@ class CausalWanModelHIP(nn.Module):
         # --- FFN (causal_model.py:462-468) ---
         if mx:
             h2 = ops.ln_modulate_tab_mx(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 3, 4, F, c.eps)
+        elif m6:
+            h2 = ops.ln_modulate_tab_mx6(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx6(xs, e0, mod, 3, 4, F, c.eps)
         elif f8:
             h2 = ops.ln_modulate_tab_f8(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_f8(xs, e0, mod, 3, 4, F, c.eps)
         elif tab32 is not None:
             h2 = ops.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps, q8=q8)
         else:
             h2 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 3, 4, F, c.eps)
-        # (mxfp8: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
-        ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU, **(dict(mx_out=True) if mx else {}))
+        # (mxfp8 / mxfp6: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
+        ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU, **(dict(mx_out=True) if mx or m6 else {}))
         self._lin(ff, pk, "f2", blk.ffn[2].weight, blk.ffn[2].bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=5, rows_per_batch=L, frame_len=fs)
         return plan

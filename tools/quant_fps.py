@@ -1,11 +1,12 @@
 """Frames/s of the block-linear precisions (none = bf16, int8 = W8A8, mxfp8 = MXFP8, fp8_rowwise = e4m3 with per-token / per-channel
-scales), each with bf16 self-attention or with MXFP8
+scales, mxfp6 = MXFP6 E2M3), each with bf16 self-attention or with MXFP8
 self-attention over the shadow of the KV cache ("+attn": set_attn_quant("mxfp8")), alternated in one process.
 
 Workload = bench.py's fps_of: the LongLive-1.3B random-init generator, config 2's steady state (4 warm-up blocks, then timed blocks
 through pipe.stream).  The modes run in turn for --rounds rounds, so a clock drift of the device lands on all of them alike; the
 record holds the median frames/s, ms per block and average GPU clock per mode, and per-kernel tables of one extra (timed-launch)
-block of mxfp8, fp8_rowwise and none+attn (those among --modes), with the MX / FP8 GEMM and MX attention plan strings.
+block of mxfp8, fp8_rowwise, mxfp6 and none+attn (those among --modes), with the MX / FP8 / MXFP6 GEMM and MX attention plan
+strings.
 
     python tools/quant_fps.py --rounds 3 --blocks 4 --out profiles/quant_fps.json
 """
@@ -21,7 +22,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "none+attn", "int8+attn", "mxfp8+attn", "fp8_rowwise+attn")
+MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "mxfp6", "none+attn", "int8+attn", "mxfp8+attn", "fp8_rowwise+attn", "mxfp6+attn")
 
 
 def main(argv=None):
@@ -91,20 +92,22 @@ def main(argv=None):
         return {t: dict(launches=v["launches"], avg_us=1e3 * v["avg_ms"], total_ms=v["total_ms"])
                 for t, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])}
 
-    tables = {m: kernel_table(m) for m in ("mxfp8", "fp8_rowwise", "none+attn") if m in modes}
+    tables = {m: kernel_table(m) for m in ("mxfp8", "fp8_rowwise", "mxfp6", "none+attn") if m in modes}
     M = 3 * cfg.frame_seqlen
     S = cfg.local_attn_size * cfg.frame_seqlen
     shapes = (("gemm_qkv", 3 * cfg.dim, cfg.dim), ("gemm_o / gemm_cq / gemm_co", cfg.dim, cfg.dim), ("gemm_f1", cfg.ffn_dim, cfg.dim),
               ("gemm_f2", cfg.dim, cfg.ffn_dim))
     plans = {name: ops.gemm_plan_mx(M, n, k) for name, n, k in shapes}
     plans_f8 = {name: ops.gemm_plan_f8(M, n, k) for name, n, k in shapes}
+    plans_mx6 = {name: ops.gemm_plan_mx6(M, n, k) for name, n, k in shapes}
     sink = cfg.sink_size * cfg.frame_seqlen
     attn_plan = ops.flash_attn_mx_plan(M, cfg.num_heads, 1, [(0, sink), (sink, S)])
     gen.model.set_quant(None)
     gen.model.set_attn_quant(None)
     rec = dict(tool="tools/quant_fps.py", device=torch.cuda.get_device_name(0), rounds=args.rounds, blocks=args.blocks,
                workload="bench.py fps_of: LongLive-1.3B random-init, config 2 steady state, 4 warm-up blocks, timed blocks via pipe.stream",
-               median=med, runs=rows, mxfp8_gemm_plans=plans, fp8_rowwise_gemm_plans=plans_f8, flash_attn_mx_plan=attn_plan)
+               median=med, runs=rows, mxfp8_gemm_plans=plans, fp8_rowwise_gemm_plans=plans_f8, mxfp6_gemm_plans=plans_mx6,
+               flash_attn_mx_plan=attn_plan)
     for m, kern in tables.items():
         rec[m.replace("+", "_") + "_kernels_one_block"] = kern
     print(json.dumps(dict(median=med)), flush=True)
@@ -115,6 +118,9 @@ def main(argv=None):
     if "fp8_rowwise" in tables:
         for name, p in plans_f8.items():
             print(f"fp8_rowwise {name}: {p}")
+    if "mxfp6" in tables:
+        for name, p in plans_mx6.items():
+            print(f"mxfp6 {name}: {p}")
     if "none+attn" in tables:
         print(f"flash_attn_mx: {attn_plan}")
         for t in ("flash_attn_self_mx", "kv_shadow_mx"):
