@@ -48,8 +48,9 @@ enum ll_epilogue {
  * 109 = FP8 rowwise block linears (ll_quantize_rows_f8, ll_gemm_f8, ll_gemm_f8_qkv, ll_ln_modulate_f8, ll_ln_modulate_tab_f8,
  * ll_layernorm_affine_f8, ll_gemm_plan_f8);
  * 110 = MXFP6 block linears (ll_quantize_mx6, ll_gemm_mx6, ll_gemm_mx6_qkv, ll_ln_modulate_mx6, ll_ln_modulate_tab_mx6,
- * ll_layernorm_affine_mx6, ll_gemm_plan_mx6). */
-#define LL_ABI_VERSION 110
+ * ll_layernorm_affine_mx6, ll_gemm_plan_mx6);
+ * 111 = MXFP4 weights over MXFP6 activations (ll_quantize_mx4, ll_gemm_mx4w6, ll_gemm_mx4w6_qkv, ll_gemm_plan_mx4w6). */
+#define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
 /* Development knob for A/B timing of kernel variants (tools/kbench, tools/kenergy, LL_TUNING=key=value,... for bench.py);
@@ -253,6 +254,29 @@ int ll_ln_modulate_tab_mx6(const ll_bf16* x, uint8_t* q, uint8_t* qs, const floa
 int ll_layernorm_affine_mx6(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
                             float eps, ll_stream stream);
 int ll_gemm_plan_mx6(int M, int N, int K, char* out, int cap);
+
+/* W4A6 mode of the block linears (set_quant("mxfp4_a6"): v_mfma_scale_f32_16x16x128_f8f6f4 with OCP FP4 E2M1 weights and the MXFP6
+ * E2M3 activations above, the FP4 rate).  Weights are quantised along K in blocks of 32: amax = m 2^p (frexp), e = p - 3 + (m > 0.75)
+ * clamped to [-127, 127] (the smallest e with amax <= 6 2^e, so no code saturates), scale byte e + 127 (E8M0; an all-zero block
+ * stores 127), codes E2M1(RNE(x 2^-e)) (sign bit 3, values 0, 0.5, 1, 1.5, 2, 3, 4, 6; a negative value rounding to zero keeps its
+ * sign).  Scales [rows, K / 32] (uint8), row-major.
+ * Codes [rows, K / 2] bytes, K % 256 == 0, packed 4 bits per code in 128-byte super-blocks of 256 k: the 32-k block j = 0..7 of a
+ * super-block (k 32 j .. 32 j + 31, one scale block) occupies the 16 bytes at 32 (j % 4) + 16 (j / 4), code i of the block in bits
+ * 4 i .. 4 i + 3 of that little-endian 128-bit word.  (The 32 bytes at 32 g are then blocks g and g + 4: the two 16x16x128 K-steps'
+ * operand fragments of MFMA lane group g.)
+ *   ll_quantize_mx4:    bf16 rows (stride ldx elements) -> codes + scales, one launch; K % 256 == 0.
+ *   ll_gemm_mx4w6:      ll_gemm_mx6 with E2M1 weights (wq / sw from ll_quantize_mx4) and MXFP6 activations (xq / sx from
+ *                       ll_quantize_mx6 or the MXFP6 producers): the same epilogues, rounding points and MXFP6 GELU output.
+ *   ll_gemm_mx4w6_qkv:  ll_gemm_mx6_qkv with E2M1 weights.
+ *   ll_gemm_plan_mx4w6: kernel instance, tile and grid of an ll_gemm_mx4w6 / ll_gemm_mx4w6_qkv call (host only). */
+int ll_quantize_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, int rows, int K, int ldx, ll_stream stream);
+int ll_gemm_mx4w6(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                  uint8_t* q_out, uint8_t* s_out, int M, int N, int K, int ldo, int epilogue, const ll_bf16* res, const ll_bf16* e,
+                  const ll_bf16* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len, ll_stream stream);
+int ll_gemm_mx4w6_qkv(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                      int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset,
+                      int write_len, ll_stream stream);
+int ll_gemm_plan_mx4w6(int M, int N, int K, char* out, int cap);
 
 /* FP8 rowwise mode of the block linears (set_quant("fp8_rowwise")): ll_gemm_w8a8's per-token / per-output-channel scheme with OCP e4m3fn
  * codes instead of int8.  Per row (a token of the activations, an output channel of a [N, K] weight): amax = max |x| over its bf16

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "liblonglive_hip.so")
 
-ABI_VERSION = 110      # include/longlive_hip.h: LL_ABI_VERSION (tests/test_abi.py holds the two together)
+ABI_VERSION = 111      # include/longlive_hip.h: LL_ABI_VERSION (tests/test_abi.py holds the two together)
 
 _p, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
 
@@ -89,6 +89,10 @@ SIGNATURES = {
     "ll_ln_modulate_tab_mx6": [_p] * 4 + [_i] * 7 + [_f, _p],
     "ll_layernorm_affine_mx6": [_p] * 5 + [_i, _i, _f, _p],
     "ll_gemm_plan_mx6": [_i, _i, _i, C.c_char_p, _i],
+    "ll_quantize_mx4": [_p, _p, _p, _i, _i, _i, _p],
+    "ll_gemm_mx4w6": [_p] * 8 + [_i] * 5 + [_p] * 3 + [_i] * 4 + [_p],
+    "ll_gemm_mx4w6_qkv": [_p] * 6 + [_i] * 4 + [_p] + [_i] * 6 + [_p],
+    "ll_gemm_plan_mx4w6": [_i, _i, _i, C.c_char_p, _i],
 }
 _RESTYPES = {"ll_last_error": C.c_char_p, "ll_gemm_ksplit_workspace_bytes": C.c_longlong}
 

@@ -145,7 +145,8 @@ class CausalWanModelHIP(nn.Module):
         # (BASELINE config 5; per-token activation scales, per-output-channel weight scales, int32 accumulation).  "mxfp8": the same
         # six on the block-scaled e4m3 MFMA (one power-of-two scale per 32 elements of K for activations and weights alike).
         # "fp8_rowwise": int8's per-token / per-output-channel scales with e4m3 codes, on the W8A8 kernels' structure.  "mxfp6": mxfp8's
-        # per-32 block scales with E2M3 (FP6) codes packed 6 bits each, on the MFMA's FP4-rate form.
+        # per-32 block scales with E2M3 (FP6) codes packed 6 bits each, on the MFMA's FP4-rate form.  "mxfp4_a6": mxfp6's activations
+        # with E2M1 (FP4) weights packed 4 bits each (W4A6).
         self.quant: Optional[str] = None
         # None: bf16 self-attention.  "mxfp8": self-attention on the block-scaled e4m3 MFMA over an MX shadow of each layer's KV cache
         # (kept in the cache dict under _MX_SHADOW, re-derived after every write; orthogonal to `quant`).
@@ -202,7 +203,7 @@ class CausalWanModelHIP(nn.Module):
         for blk in self.blocks:
             sa = blk.self_attn
             ts = [sa.q.weight, sa.k.weight, sa.v.weight, sa.q.bias, sa.k.bias, sa.v.bias, blk.modulation]
-            if self.quant in ("int8", "mxfp8", "fp8_rowwise", "mxfp6"):
+            if self.quant in ("int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6"):
                 ts += [sa.o.weight, blk.cross_attn.q.weight, blk.cross_attn.o.weight, blk.ffn[0].weight, blk.ffn[2].weight]
             key.extend((t.data_ptr(), t._version) for t in ts)
         return tuple(key)
@@ -222,7 +223,7 @@ class CausalWanModelHIP(nn.Module):
             )
             if self.quant is not None:
                 quantize = {"int8": ops.quantize_rows, "mxfp8": ops.quantize_mx, "fp8_rowwise": ops.quantize_rows_f8,
-                            "mxfp6": ops.quantize_mx6}[self.quant]
+                            "mxfp6": ops.quantize_mx6, "mxfp4_a6": ops.quantize_mx4}[self.quant]
                 for name, w in (("qkv", d["wqkv"]), ("o", sa.o.weight), ("cq", ca.q.weight), ("co", ca.o.weight),
                                 ("f1", blk.ffn[0].weight), ("f2", blk.ffn[2].weight)):
                     d["q_" + name], d["s_" + name] = quantize(w.detach().contiguous())
@@ -234,13 +235,14 @@ class CausalWanModelHIP(nn.Module):
 
     def set_quant(self, mode: Optional[str]):
         """None (bf16), "int8" (W8A8 block linears), "mxfp8" (MXFP8 block linears), "fp8_rowwise" (e4m3 codes with per-token /
-        per-output-channel scales) or "mxfp6" (MXFP6 E2M3 block linears).  Weights are (re)quantised lazily at the next forward."""
-        if mode not in (None, "int8", "mxfp8", "fp8_rowwise", "mxfp6"):
+        per-output-channel scales), "mxfp6" (MXFP6 E2M3 block linears) or "mxfp4_a6" (MXFP4 E2M1 weights over MXFP6 activations).
+        Weights are (re)quantised lazily at the next forward."""
+        if mode not in (None, "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6"):
             raise ValueError(f"unknown quantisation mode {mode!r}")
         if mode is not None and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
             raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 128")
-        if mode == "mxfp6" and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
-            raise ValueError("mxfp6 linears need dim and ffn_dim to be multiples of 256 (packed 256-k super-blocks)")
+        if mode in ("mxfp6", "mxfp4_a6") and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
+            raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 256 (packed 256-k super-blocks)")
         self.quant = mode
         self._packed = None
         return self
@@ -270,7 +272,11 @@ class CausalWanModelHIP(nn.Module):
     def _lin(self, x, pk, key, w, b, epilogue=0, **kw):
         """One block linear: bf16 MFMA GEMM, or W8A8 GEMM in int8 mode (same fused epilogues).  In int8 mode `x` is either
         a bf16 tensor (quantised here, per token) or an already quantised (int8, scale) pair from a fused producer; in mxfp8 mode
-        likewise a bf16 tensor or an (e4m3 codes, block scales) pair, and in fp8_rowwise mode an (e4m3 codes, row scale) pair."""
+        likewise a bf16 tensor or an (e4m3 codes, block scales) pair, and in fp8_rowwise mode an (e4m3 codes, row scale) pair; mxfp6 and
+        mxfp4_a6 take a bf16 tensor or an MXFP6 (packed E2M3 codes, block scales) pair."""
+        if self.quant == "mxfp4_a6":
+            xm = x if isinstance(x, tuple) else ops.quantize_mx6(x)
+            return ops.gemm_mx4w6(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
         if self.quant == "mxfp6":
             xm = x if isinstance(x, tuple) else ops.quantize_mx6(x)
             return ops.gemm_mx6(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
@@ -379,7 +385,7 @@ class CausalWanModelHIP(nn.Module):
         q8 = self.quant == "int8"
         mx = self.quant == "mxfp8"
         f8 = self.quant == "fp8_rowwise"
-        m6 = self.quant == "mxfp6"
+        m6 = self.quant in ("mxfp6", "mxfp4_a6")          # MXFP6 activations (E2M3 or E2M1 weights)
         G, E = _kv_state(kvc)
         S = kvc["k"].shape[1]
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
@@ -406,8 +412,9 @@ class CausalWanModelHIP(nn.Module):
                 qkv = ops.gemm_mx_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
                                                plan.roped_offset, plan.write_len, B, L)
             elif m6:
-                qkv = ops.gemm_mx6_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
-                                                plan.roped_offset, plan.write_len, B, L)
+                qkv_m6 = ops.gemm_mx4w6_qkv_v_insert if self.quant == "mxfp4_a6" else ops.gemm_mx6_qkv_v_insert
+                qkv = qkv_m6(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start, plan.roped_offset, plan.write_len,
+                             B, L)
             elif f8:
                 qkv = ops.gemm_f8_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
                                                plan.roped_offset, plan.write_len, B, L)
@@ -474,7 +481,7 @@ class CausalWanModelHIP(nn.Module):
             h2 = ops.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps, q8=q8)
         else:
             h2 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 3, 4, F, c.eps)
-        # (mxfp8 / mxfp6: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
+        # (mxfp8 / mxfp6 / mxfp4_a6: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
         ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU, **(dict(mx_out=True) if mx or m6 else {}))
         self._lin(ff, pk, "f2", blk.ffn[2].weight, blk.ffn[2].bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=5, rows_per_batch=L, frame_len=fs)

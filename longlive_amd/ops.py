@@ -1217,6 +1217,99 @@ def gemm_plan_mx6(M: int, N: int, K: int) -> str:
     return buf.value.decode()
 
 
+# ---- MXFP4 weights over MXFP6 activations (E2M1 codes packed 4 bits each, uint8 [rows, K/2] + E8M0 scale bytes [rows, K / 32];
+# include/longlive_hip.h ll_quantize_mx4: K % 256 == 0; activations as in the MXFP6 wrappers above) ----------------------------------
+def _mx4_pair(wm, name: str):
+    q, s = wm
+    _chk(q, name, u8); _chk(s, name + " scales", u8)
+    assert q.shape[-1] % 128 == 0, q.shape
+    K = q.shape[-1] * 2
+    rows = q.numel() // q.shape[-1]
+    assert s.numel() == rows * (K // 32), (q.shape, s.shape)
+    return q, s, rows, K
+
+
+def quantize_mx4(x, tag: str = "quantize_mx4"):
+    """MXFP4 quantisation of a [..., K] bf16 tensor along K (blocks of 32) -> (packed E2M1 uint8 [..., K/2], uint8 scales [rows, K / 32])."""
+    _chk(x, "x")
+    K = x.shape[-1]
+    assert K % 256 == 0, f"MXFP4 rows need K % 256 == 0, got {K}"
+    rows = x.numel() // K
+    q = torch.empty(*x.shape[:-1], K // 2, dtype=u8, device=x.device)
+    s = torch.empty(rows, K // 32, dtype=u8, device=x.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_quantize_mx4(x.data_ptr(), q.data_ptr(), s.data_ptr(), rows, K, K, _stream()), "ll_quantize_mx4")
+    _t1(tag, t0, 2.53 * x.numel())
+    return q, s
+
+
+def gemm_mx4w6(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
+               rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
+    """gemm_mx6 with MXFP4 weights: xm = (packed E2M3 codes [..., 3K/4], scales) as from quantize_mx6 or an MXFP6 producer,
+    wm = (packed E2M1 codes [N, K/2], scales) from quantize_mx4.  mx_out (GELU only): returns the MXFP6 codes + scales of the bf16
+    result instead of it."""
+    xq, sx, M, K = _mx6_pair(xm, "xq")
+    wq, sw, N, Kw = _mx4_pair(wm, "wq")
+    _chk(bias, "bias")
+    assert Kw == K and wq.dim() == 2 and bias.numel() == N, (wq.shape, K, bias.shape)
+    nmod = 0
+    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
+        _chk(res, "res")
+        assert res.numel() == M * N
+    if epilogue == EPI_BIAS_GATE_RES:
+        _chk(e, "e")
+        nmod = e.shape[-2]
+        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
+        if mod is not None:
+            _chk(mod, "mod")
+            assert mod.numel() == nmod * N
+    if mx_out:
+        assert epilogue == EPI_BIAS_GELU and out is None
+        qo, so = _mx6_empty((*xq.shape[:-1], N), xq.device)
+    else:
+        qo = so = None
+        if out is None:
+            out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
+        _chk(out, "out")
+        assert out.numel() == M * N
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_gemm_mx4w6(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), _ptr(out), _ptr(qo),
+                                 _ptr(so), M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len,
+                                 _stream()), "ll_gemm_mx4w6")
+    _t1(tag, t0, 2.0 * M * N * K)
+    return (qo, so) if mx_out else out
+
+
+def gemm_mx4w6_qkv_v_insert(xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int,
+                            tag: str = "gemm_qkv"):
+    """gemm_mx6_qkv_v_insert with MXFP4 weights.  Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v
+    [B, S, H, D]."""
+    xq, sx, M, K = _mx6_pair(xm, "xq")
+    wq, sw, N, Kw = _mx4_pair(wm, "wq")
+    _chk(bias, "bias"); _chk(cache_v, "cache_v")
+    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
+    S = cache_v.shape[1]
+    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
+    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_gemm_mx4w6_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                     M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
+               "ll_gemm_mx4w6_qkv")
+    _t1(tag, t0, 2.0 * M * N * K)
+    return out
+
+
+def gemm_plan_mx4w6(M: int, N: int, K: int) -> str:
+    """Kernel instance, tile and grid of a gemm_mx4w6 / gemm_mx4w6_qkv_v_insert call (host only)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().ll_gemm_plan_mx4w6(M, N, K, buf, 256), "ll_gemm_plan_mx4w6")
+    return buf.value.decode()
+
+
 # ---- MXFP8 self-attention over a block-scaled shadow of the KV cache (attention_mx.hip) ------------------------------------------
 def kv_shadow_mx_alloc(cache_k) -> dict:
     """Uninitialised MX shadow of one layer's cache k (or v) [B, S, H, 128]: K^ codes [B, S32, H, 128] + scales [B, S32, H, 4],
