@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: generated frames/s at 832x480 for LongLive-1.3B frame-level AR inference on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one autoregressive block of BASELINE.json's config 2: 3 latent frames (= 12 pixel frames at 832x480)
 produced by 4 denoising DiT forwards (warped schedule 1000/937.5/833.3/625, re-noised in between) plus the
@@ -23,10 +23,12 @@ time.  Two ways to get N replicas:
 The JSON line also carries
   roofline     : the dominant kernel (self-attention), timed live with HIP events on its launch stream over the timed
                  region; achieved = algorithmic FLOPs (4 * Lq * Lk * 128 * heads) / avg launch duration
+  telemetry    : clock / power of the device over the timed region (and `energy`, the J per block derived from it).
+A plain run stops there: set up, warm up, time the steps, dump, print.  `--full` also measures, after the timed region,
   kernels      : per-kernel table of one more (untimed) steady-state block with EVERY launch bracketed by HIP events:
                  avg us, algorithmic work, achieved, peak, fraction (MFMA kernels against 2.5 PFLOP/s, row kernels against 8 TB/s)
-  extras       : side numbers measured after the timed region (bounded): INT8 frames/s on the same workload, prompt-switch
-                 (recache) latency, VAE decode frames/s, umT5 ms per prompt -- none of them is part of `value`
+  extras       : side numbers (bounded): INT8 frames/s on the same workload, batched / interleaved streams, prompt-switch
+                 (recache) latency, VAE decode frames/s, live decode, umT5 ms per prompt -- none of them is part of `value`
   cpu_baseline : the CPU oracle (a port of the reference's PyTorch path, oracle/) timed on this host on a bounded sample.
 
 `--dump-outputs DIR` writes what the last timed block returned to the caller of the stream -- its denoised latents
@@ -70,14 +72,17 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=7, help="timed AR blocks (7 blocks = one 5-second clip)")
     ap.add_argument("--warmup", type=int, default=4, help="untimed AR blocks (4 fill the 12-frame window)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the per-kernel table, the side numbers (extras) and the CPU baseline; "
+                         "a plain run only sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--kernels-only", action="store_true", help="the per-kernel table of one more steady-state block, but none of the side numbers (extras)")
+    ap.add_argument("--kernels-only", action="store_true", help="with --full: the per-kernel table of one more steady-state block, but none of the side numbers (extras)")
     ap.add_argument("--no-extras", action="store_true", help="skip the kernels table and the side numbers after the timed region")
-    ap.add_argument("--cpu-layers", type=int, default=30, help="layers of one steady-state forward timed on the CPU (30 = the whole forward, ~20 s)")
+    ap.add_argument("--cpu-layers", type=int, default=30, help="with --full: layers of one steady-state forward timed on the CPU (30 = the whole forward, ~20 s)")
     ap.add_argument("--workload", choices=["dit", "vae", "t5"], default="dit",
                     help="dit (default): the headline metric.  vae / t5: the section-8f rows (VAE decoder, umT5 encoder) with "
-                         "their own roofline and cpu_baseline objects; single GPU, not the driver's metric")
+                         "their own roofline (and with --full cpu_baseline) objects; single GPU, not the driver's metric")
     ap.add_argument("--quant", choices=["none", "int8"], default="none",
                     help="int8: W8A8 block linears (BASELINE config 5); the headline metric is the default bf16 path")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -90,6 +95,8 @@ def parse(argv=None):
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs is not None and args.workload != "dit":
         ap.error("--dump-outputs covers the headline (dit) workload only")
+    if args.kernels_only and not args.full:
+        ap.error("--kernels-only selects what --full measures: give --full as well")
     return args
 
 
@@ -170,20 +177,20 @@ def cpu_baseline_t5(enc, cfg, ids, mask):
 
 
 def side_workload(args):
-    """`--workload vae|t5`: tools/vae_bench.py / tools/t5_bench.py (HIP path, roofline) + the CPU baseline leg, which
-    lives here because only bench.py may run the oracle outside tests."""
+    """`--workload vae|t5`: tools/vae_bench.py / tools/t5_bench.py (HIP path, roofline) + with --full the CPU baseline leg,
+    which lives here because only bench.py may run the oracle outside tests."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the product path has no CPU fallback")
     if args.workload == "vae":
         import vae_bench
         rec, vae, lat = vae_bench.run(9, 2)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline_vae(vae, lat)
     else:
         import t5_bench
         rec, enc, cfg, ids, mask = t5_bench.run(5)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline_t5(enc, cfg, ids, mask)
     print(json.dumps(rec), flush=True)
 
@@ -662,8 +669,11 @@ def run_replica(args, rank, world, local_rank, sync):
         pipe.overlap_context = os.environ["LL_OVERLAP"] == "1"
     if os.environ.get("LL_NOMEMO") == "1":                             # A/B only: untagged timestep tensors = sigma, time embedding and
         pipe._timestep = lambda value, b, f, device: torch.full([b, f], value, dtype=torch.float32, device=device)   # modulation table every forward
-    extra_blocks = 0 if (args.no_extras or rank != 0) else 1           # one more steady-state block for the kernels table
-    nblocks = args.warmup + args.steps + extra_blocks
+    # rank 0 sizes its stream for one more steady-state block (the kernels table's) unless --no-extras, whether or not --full then
+    # runs that block: the timed blocks see the same inputs and the same allocations in a plain run and in a --full one
+    spare_block = 0 if (args.no_extras or rank != 0) else 1
+    kernels_block = args.full and spare_block == 1
+    nblocks = args.warmup + args.steps + spare_block
     T = 3 * nblocks
     assert T <= 1024, "RoPE frame table has 1024 entries"
     # one independent stream per replica (inference.py:49,146: seed + rank, prompts sharded by rank)
@@ -762,7 +772,7 @@ def run_replica(args, rank, world, local_rank, sync):
                                     "taken on one stream")
                                    if pipe.overlap_context else
                                    "one HIP stream: `share_of_step` = wall time with a self-attention launch in flight / elapsed"}
-    if extra_blocks:
+    if kernels_block:
         try:
             pipe.overlap_context = False                               # one stream: per-kernel times without a co-running forward
             ops.timer = ops.KernelTimer()                              # every tagged launch of one more steady-state block
@@ -787,7 +797,7 @@ def run_replica(args, rank, world, local_rank, sync):
                 res["extras"] = run_extras(gen, CausalInferencePipeline, InteractiveCausalInferencePipeline, cfg, dev)
             except Exception as exc:
                 res["extras"] = {"error": repr(exc)}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             del gen                                                    # (the GPU model is no longer needed: the host copy of the weights is the oracle's)
             torch.cuda.empty_cache()

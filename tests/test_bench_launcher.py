@@ -116,3 +116,14 @@ def test_dump_outputs_option(tmp_path):
     got = np.load(tmp_path / "d" / "latents.npy")
     assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
     assert np.load(tmp_path / "d" / "start_frame.npy").dtype == np.float64
+
+
+def test_full_option():
+    """A plain run measures the headline only; --full adds the kernels table, the side numbers and the CPU baseline, and
+    --kernels-only (which narrows what --full adds) is refused without it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full"]).full and bench.parse(["--full", "--kernels-only"]).kernels_only
+    out = subprocess.run([sys.executable, BENCH, "--kernels-only"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--full" in out.stderr

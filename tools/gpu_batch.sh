@@ -42,7 +42,7 @@ for step in "$@"; do
       if [ -n "$k" ]; then timeout -k 10 900 python -m pytest $f -m gpu -q -x -s -k "$k" > $O/test_$(basename $f .py).log 2>&1; else timeout -k 10 900 python -m pytest $f -m gpu -q -x -s > $O/test_$(basename $f .py).log 2>&1; fi
       rc=$?; echo "pytest rc=$rc"; tail -6 $O/test_$(basename $f .py).log ;;
     bench)
-      timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; rc=$?; echo "bench rc=$rc"; benchline $O/bench.json ;;
+      timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; rc=$?; echo "bench rc=$rc"; benchline $O/bench.json ;;
     bench_short)
       timeout -k 10 400 python3 bench.py --steps 14 --warmup 4 --no-extras --no-cpu-baseline --no-kernel-timer > $O/bench_short.json 2> $O/bench_short.err; rc=$?; benchline $O/bench_short.json ;;
     trace)
@@ -154,7 +154,7 @@ PY
       a=$(echo "$arg" | cut -d/ -f1); b=$(echo "$arg" | cut -d/ -f2); n=$(echo "$arg" | cut -d/ -f3); n=${n:-2}; rc=0
       for i in $(seq 1 $n); do for t in "$a" "$b"; do
         tag=$(echo "$t" | tr -c 'A-Za-z0-9\n' '_')
-        LL_TUNING=$t timeout -k 10 400 python3 bench.py --quant int8 --steps 12 --warmup 4 --no-cpu-baseline --kernels-only > $O/benchq_${tag}_$i.json 2> $O/benchq_${tag}_$i.err; rc=$?; dead $rc && break 2
+        LL_TUNING=$t timeout -k 10 400 python3 bench.py --quant int8 --steps 12 --warmup 4 --full --no-cpu-baseline --kernels-only > $O/benchq_${tag}_$i.json 2> $O/benchq_${tag}_$i.err; rc=$?; dead $rc && break 2
         echo -n "[int8 $t] "; benchline $O/benchq_${tag}_$i.json
       done; done > >(tee -a $O/benchq.txt); wait ;;
     clockmatrix)   # clockmatrix[=<variant>,<variant>...]: one kernel looped alone per load with clock / power / energy (tools/clock_matrix.py); the shipped

@@ -1,5 +1,5 @@
 """Times the HIP umT5-xxl encoder (24 layers, 512 positions, synthetic weights; 4096-entry vocabulary to keep the
-embedding table small).  usage: python tools/t5_bench.py [iters=5]   (one JSON line; `python bench.py --workload t5` adds the CPU baseline)"""
+embedding table small).  usage: python tools/t5_bench.py [iters=5]   (one JSON line; `python bench.py --workload t5 --full` adds the CPU baseline)"""
 import json
 import os
 import sys

@@ -1,7 +1,7 @@
 """Times the HIP VAE decoder at the real geometry (60x104 latents -> 480x832 pixels), synthetic weights.
 usage: python tools/vae_bench.py [latent_frames=9] [chunk=2]   (prints one JSON line)
 roofline: all ll_conv_cl launches of the timed region (HIP events on the launch stream), algorithmic FLOPs / time against
-the 2.5 PFLOP/s bf16 MFMA peak.  `python bench.py --workload vae` prints the same record plus the CPU baseline."""
+the 2.5 PFLOP/s bf16 MFMA peak.  `python bench.py --workload vae --full` prints the same record plus the CPU baseline."""
 import json
 import os
 import sys
