@@ -49,7 +49,9 @@ enum ll_epilogue {
  * ll_layernorm_affine_f8, ll_gemm_plan_f8);
  * 110 = MXFP6 block linears (ll_quantize_mx6, ll_gemm_mx6, ll_gemm_mx6_qkv, ll_ln_modulate_mx6, ll_ln_modulate_tab_mx6,
  * ll_layernorm_affine_mx6, ll_gemm_plan_mx6);
- * 111 = MXFP4 weights over MXFP6 activations (ll_quantize_mx4, ll_gemm_mx4w6, ll_gemm_mx4w6_qkv, ll_gemm_plan_mx4w6). */
+ * 111 = MXFP4 weights over MXFP6 activations (ll_quantize_mx4, ll_gemm_mx4w6, ll_gemm_mx4w6_qkv, ll_gemm_plan_mx4w6); W4A4 block
+ * linears (ll_gemm_mx4, ll_gemm_mx4_qkv, ll_ln_modulate_mx4, ll_ln_modulate_tab_mx4, ll_layernorm_affine_mx4, ll_gemm_plan_mx4) only
+ * add entry points, so they keep 111. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -277,6 +279,30 @@ int ll_gemm_mx4w6_qkv(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, c
                       int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset,
                       int write_len, ll_stream stream);
 int ll_gemm_plan_mx4w6(int M, int N, int K, char* out, int cap);
+
+/* W4A4 mode of the block linears (set_quant("mxfp4_a4"): v_mfma_scale_f32_16x16x128_f8f6f4 with both operands OCP FP4 E2M1, the FP4
+ * rate).  Activations use the weights' scheme and layout above (ll_quantize_mx4: codes [rows, K / 2], scales [rows, K / 32]).
+ *   ll_gemm_mx4:      ll_gemm_mx4w6 with E2M1 activations (xq / sx from ll_quantize_mx4 or the MXFP4 producers): the same epilogues
+ *                     and rounding points.  With the GELU epilogue, q_out / s_out (instead of out) receive the MXFP4 codes + scales of
+ *                     the bf16 GELU output (N % 256 == 0, ldo == N), bit-identical to ll_quantize_mx4 of the bf16 result.  Exactly
+ *                     one form is given.
+ *   ll_gemm_mx4_qkv:  ll_gemm_mx6_qkv on E2M1 operands (V third into cache_v).
+ *   ll_ln_modulate_mx4 / ll_ln_modulate_tab_mx4 / ll_layernorm_affine_mx4: the producers of the same names emitting MXFP4 codes +
+ *                     scales of their bf16 output (bit-identical to ll_quantize_mx4 of it); C % 256 == 0.
+ *   ll_gemm_plan_mx4: kernel instance, tile and grid of an ll_gemm_mx4 / ll_gemm_mx4_qkv call (host only). */
+int ll_gemm_mx4(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                uint8_t* q_out, uint8_t* s_out, int M, int N, int K, int ldo, int epilogue, const ll_bf16* res, const ll_bf16* e,
+                const ll_bf16* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len, ll_stream stream);
+int ll_gemm_mx4_qkv(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias, ll_bf16* out,
+                    int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset,
+                    int write_len, ll_stream stream);
+int ll_ln_modulate_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod, int shift_idx,
+                       int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_ln_modulate_tab_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx, int scale_idx,
+                           int B, int L, int C, int F, float eps, ll_stream stream);
+int ll_layernorm_affine_mx4(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows, int C,
+                            float eps, ll_stream stream);
+int ll_gemm_plan_mx4(int M, int N, int K, char* out, int cap);
 
 /* FP8 rowwise mode of the block linears (set_quant("fp8_rowwise")): ll_gemm_w8a8's per-token / per-output-channel scheme with OCP e4m3fn
  * codes instead of int8.  Per row (a token of the activations, an output channel of a [N, K] weight): amax = max |x| over its bf16

@@ -93,6 +93,12 @@ SIGNATURES = {
     "ll_gemm_mx4w6": [_p] * 8 + [_i] * 5 + [_p] * 3 + [_i] * 4 + [_p],
     "ll_gemm_mx4w6_qkv": [_p] * 6 + [_i] * 4 + [_p] + [_i] * 6 + [_p],
     "ll_gemm_plan_mx4w6": [_i, _i, _i, C.c_char_p, _i],
+    "ll_gemm_mx4": [_p] * 8 + [_i] * 5 + [_p] * 3 + [_i] * 4 + [_p],
+    "ll_gemm_mx4_qkv": [_p] * 6 + [_i] * 4 + [_p] + [_i] * 6 + [_p],
+    "ll_ln_modulate_mx4": [_p] * 5 + [_i] * 7 + [_f, _p],
+    "ll_ln_modulate_tab_mx4": [_p] * 4 + [_i] * 7 + [_f, _p],
+    "ll_layernorm_affine_mx4": [_p] * 5 + [_i, _i, _f, _p],
+    "ll_gemm_plan_mx4": [_i, _i, _i, C.c_char_p, _i],
 }
 _RESTYPES = {"ll_last_error": C.c_char_p, "ll_gemm_ksplit_workspace_bytes": C.c_longlong}
 

@@ -294,12 +294,12 @@ def build_models(config, device, synthetic: bool):
     return wcfg, gen, vae, enc, lora_enabled
 
 
-QUANT_MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6")
+QUANT_MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4")
 
 
 def quant_mode(value) -> Optional[str]:
-    """The yaml's `quant:` key (none | int8 | mxfp8 | fp8_rowwise | mxfp6 | mxfp4_a6, default none) as CausalWanModelHIP.set_quant's
-    argument."""
+    """The yaml's `quant:` key (none | int8 | mxfp8 | fp8_rowwise | mxfp6 | mxfp4_a6 | mxfp4_a4, default none) as
+    CausalWanModelHIP.set_quant's argument."""
     v = "none" if value is None else str(value).strip().lower()
     if v not in QUANT_MODES:
         raise ValueError(f"quant: {value!r} is not one of {', '.join(QUANT_MODES)}")
@@ -335,7 +335,7 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     torch.manual_seed(replica_seed(int(config.seed), local_rank))                 # set_seed(config.seed + local_rank)
     synthetic = synthetic or bool(config.get("synthetic", False))
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
-    gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6 or W4A6
+    gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6, W4A6 or W4A4
     gen.model.set_attn_quant(attn_quant_mode(config.get("attn_quant", "none")))   # self-attention: bf16 or MXFP8
     interactive = mode == "interactive"
     cls = InteractiveCausalInferencePipeline if interactive else CausalInferencePipeline

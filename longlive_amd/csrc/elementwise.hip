@@ -6,6 +6,7 @@
 // reduced with wave shuffles only (no LDS, no barrier).  4 waves (rows) per 256-thread workgroup.
 #include "common.h"
 #include "mx.h"
+#include "mx4.h"
 #include "mx6.h"
 
 #define MAXCH 4  // 4 * 64 lanes * 8 elements = 2048 columns max
@@ -518,6 +519,136 @@ __global__ __launch_bounds__(256) void layernorm_affine_mx6_kernel(const bf16* _
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
   emit_row_mx6<NCH, FULL>(o, C, lane, row, q, qs);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// MXFP4 forms of the same three producers: E2M1 codes packed per mx4.h [rows, C/2] + E8M0 scales [rows, C / 32], bit-identical to
+// ll_quantize_mx4 of the bf16 output.  A lane's 8 values are one dword of the packed row, a 32-k block is 4 consecutive lanes.
+template <int NCH, bool FULL>
+__device__ __forceinline__ void emit_row_mx4(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
+                                             uint8_t* __restrict__ qs) {
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    int c = (lane + 64 * i) * 8;
+    bool in = in_row<FULL>(c, C);
+    float f[8];
+    float mx = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x2 v = unpack2(y.w[i][j]);
+      f[2 * j] = v.x, f[2 * j + 1] = v.y;
+      mx = fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y)));
+    }
+    if (!in) mx = 0.f;
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    int e = mx4_scale_exp(mx);
+    if (in) {
+      *reinterpret_cast<uint32_t*>(q + (size_t)row * (C / 2) + mx4_chunk_off(c)) = mx4_pack8(f, e);
+      if ((lane & 3) == 0) qs[(size_t)row * (C / MX4_BLOCK) + c / MX4_BLOCK] = (uint8_t)(e + 127);
+    }
+  }
+}
+
+template <int NCH, bool FULL, bool PRE>
+__global__ __launch_bounds__(256) void ln_modulate_mx4_kernel(const bf16* __restrict__ x, const bf16* __restrict__ e,
+                                                              const bf16* __restrict__ mod, int nmod, int shift_idx, int scale_idx,
+                                                              int rows, int L, int C, int frame_len, int F, float eps,
+                                                              uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
+  int lane = threadIdx.x & 63;
+  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (row >= rows) return;
+  RowRegs r;
+  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
+  int b = row / L, f = (row % L) / frame_len;
+  const bf16* eb = e + ((size_t)(b * F + f) * nmod) * C;
+  RowWords es, et, ms, mt;
+  load_words<NCH, FULL>(eb + (size_t)scale_idx * C, C, lane, es);
+  load_words<NCH, FULL>(eb + (size_t)shift_idx * C, C, lane, et);
+  if (!PRE) {
+    load_words<NCH, FULL>(mod + (size_t)scale_idx * C, C, lane, ms);
+    load_words<NCH, FULL>(mod + (size_t)shift_idx * C, C, lane, mt);
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  float rstd;
+  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
+  const f32x2 r2 = splat2(rstd), one = splat2(1.0f);
+  RowWords o;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x2 y = rbf2(r.p[i][j] * r2);
+      f32x2 sc = PRE ? unpack2(es.w[i][j]) : rbf2(unpack2(ms.w[i][j]) + unpack2(es.w[i][j]));
+      f32x2 t = PRE ? unpack2(et.w[i][j]) : rbf2(unpack2(mt.w[i][j]) + unpack2(et.w[i][j]));
+      f32x2 s1 = rbf2(one + sc);
+      o.w[i][j] = pack2(rbf2(y * s1) + t);
+    }
+  emit_row_mx4<NCH, FULL>(o, C, lane, row, q, qs);
+}
+
+template <int NCH, bool FULL>
+__global__ __launch_bounds__(256) void ln_modulate_tab_mx4_kernel(const bf16* __restrict__ x, const float* __restrict__ tab, int nmod,
+                                                                  int shift_idx, int scale_idx, int rows, int L, int C, int frame_len,
+                                                                  int F, float eps, uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
+  int lane = threadIdx.x & 63;
+  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (row >= rows) return;
+  RowRegs r;
+  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
+  int b = row / L, f = (row % L) / frame_len;
+  const float* tb = tab + ((size_t)(b * F + f) * nmod) * C;
+  f32x2 s1[NCH][4], t[NCH][4];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    int c = (lane + 64 * i) * 8;
+    if (in_row<FULL>(c, C)) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        f32x4 a = *reinterpret_cast<const f32x4*>(tb + (size_t)scale_idx * C + c + 4 * h);
+        f32x4 d = *reinterpret_cast<const f32x4*>(tb + (size_t)shift_idx * C + c + 4 * h);
+        s1[i][2 * h].x = a[0], s1[i][2 * h].y = a[1], s1[i][2 * h + 1].x = a[2], s1[i][2 * h + 1].y = a[3];
+        t[i][2 * h].x = d[0], t[i][2 * h].y = d[1], t[i][2 * h + 1].x = d[2], t[i][2 * h + 1].y = d[3];
+      }
+    }
+  }
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  float rstd;
+  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
+  const f32x2 r2 = splat2(rstd);
+  RowWords o;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(rbf2(rbf2(r.p[i][j] * r2) * s1[i][j]) + t[i][j]);
+  emit_row_mx4<NCH, FULL>(o, C, lane, row, q, qs);
+}
+
+template <int NCH, bool FULL>
+__global__ __launch_bounds__(256) void layernorm_affine_mx4_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
+                                                                   const bf16* __restrict__ bb, int rows, int C, float eps,
+                                                                   uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
+  int lane = threadIdx.x & 63;
+  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (row >= rows) return;
+  RowRegs r;
+  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
+  RowWords wv, bv;
+  load_words<NCH, FULL>(w, C, lane, wv);
+  load_words<NCH, FULL>(bb, C, lane, bv);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  float rstd;
+  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
+  const f32x2 r2 = splat2(rstd);
+  RowWords o;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
+  emit_row_mx4<NCH, FULL>(o, C, lane, row, q, qs);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1098,6 +1229,67 @@ extern "C" int ll_layernorm_affine_mx6(const ll_bf16* x, const ll_bf16* w, const
   DISPATCH_NCH(C, CALL);
 #undef CALL
   return ll_check_launch("ll_layernorm_affine_mx6");
+}
+
+// ---- MXFP4 producers (codes [rows, C/2] packed E2M1, scales [rows, C / 32] E8M0)
+static int mx4_row_ok(const char* fn, int C, const void* q, const void* qs) {
+  LL_REQUIRE(C > 0 && C <= 2048 && C % MX4_SUPER == 0, "%s: C=%d must be a multiple of 256 and <= 2048", fn, C);
+  LL_REQUIRE(q != nullptr && qs != nullptr, "%s: codes and scales are required", fn);
+  return LL_OK;
+}
+
+extern "C" int ll_ln_modulate_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod,
+                                  int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
+  if (int rc = mx4_row_ok("ll_ln_modulate_mx4", C, q, qs)) return rc;
+  LL_REQUIRE(x != nullptr && e != nullptr, "ll_ln_modulate_mx4: x and e are required");
+  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_mx4: L=%d not divisible by F=%d", L, F);
+  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_mx4: bad mod index");
+  int rows = B * L;
+  if (rows == 0) return LL_OK;
+  dim3 grid((rows + 3) / 4);
+#define CALL(N, FL)                                                                                                           \
+  do {                                                                                                                    \
+    if (mod)                                                                                                              \
+      hipLaunchKernelGGL((ln_modulate_mx4_kernel<N, FL, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, \
+                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs);  \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((ln_modulate_mx4_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,  \
+                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs);  \
+  } while (0)
+  DISPATCH_NCH(C, CALL);
+#undef CALL
+  return ll_check_launch("ll_ln_modulate_mx4");
+}
+
+extern "C" int ll_ln_modulate_tab_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx,
+                                      int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
+  if (int rc = mx4_row_ok("ll_ln_modulate_tab_mx4", C, q, qs)) return rc;
+  LL_REQUIRE(x != nullptr && tab != nullptr, "ll_ln_modulate_tab_mx4: x and tab are required");
+  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab_mx4: L=%d not divisible by F=%d", L, F);
+  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab_mx4: bad mod index");
+  int rows = B * L;
+  if (rows == 0) return LL_OK;
+  dim3 grid((rows + 3) / 4);
+#define CALL(N, FL)                                                                                                       \
+  hipLaunchKernelGGL((ln_modulate_tab_mx4_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, tab, \
+                     nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs)
+  DISPATCH_NCH(C, CALL);
+#undef CALL
+  return ll_check_launch("ll_ln_modulate_tab_mx4");
+}
+
+extern "C" int ll_layernorm_affine_mx4(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows,
+                                       int C, float eps, ll_stream stream) {
+  if (int rc = mx4_row_ok("ll_layernorm_affine_mx4", C, q, qs)) return rc;
+  LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "ll_layernorm_affine_mx4: x, w and b are required");
+  if (rows == 0) return LL_OK;
+  dim3 grid((rows + 3) / 4);
+#define CALL(N, FL)                                                                                                  \
+  hipLaunchKernelGGL((layernorm_affine_mx4_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,   \
+                     (const bf16*)w, (const bf16*)b, rows, C, eps, q, qs)
+  DISPATCH_NCH(C, CALL);
+#undef CALL
+  return ll_check_launch("ll_layernorm_affine_mx4");
 }
 
 extern "C" int ll_rmsnorm(const ll_bf16* x, const ll_bf16* w, ll_bf16* out, int rows, int C, int ldx, int ldo,

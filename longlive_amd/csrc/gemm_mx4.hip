@@ -275,3 +275,249 @@ extern "C" int ll_gemm_mx4w6_qkv(const uint8_t* xq, const uint8_t* sx, const uin
   if (int lrc = mx4w6_launch(xq, sx, wq, sw, (bf16*)out, nullptr, nullptr, M, N, K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_mx4w6_qkv");
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// W4A4: both operands OCP FP4 E2M1 (cbsz = 4, blgp = 4), activations in the weights' format (ll_quantize_mx4 or the MXFP4
+// producers).  gemm_mx4w6_kernel's structure with X in the W layout: X rows are 128 bytes per stage and staged exactly like W rows
+// (unit u of LDS row r holds the row's unit u ^ m4_wsw(r), so the conflict-free argument above holds for the X reads too), and a
+// lane's X fragment of K-step s is 16-byte unit 2 g + s.  One stage = 48 KiB of codes, 4 + 2 LDS-DMA instructions per wave; both
+// 8-dword MFMA operands carry 4 live dwords.  Same 256 x 128 tile, two code stages, 3-slot scale ring two stages ahead and counted
+// vmcnt(2) across the raw s_barrier.  The FFN1 form writes MXFP4 codes + scales (gemm_epilogue_gelu_mx4), FFN2's input.
+#define M4A_ROW 128                                  // LDS row of either operand: 256 k of E2M1 codes
+#define M4A_TILE ((M4_BM + M4_BN) * M4A_ROW)         // 48 KiB
+#define M4A_LDS (2 * M4A_TILE + 3 * M4_SC)           // 105 KiB (the LDS epilogue's 72 KiB fits)
+
+// FFN1 with MXFP4 output: the GELU epilogue's bf16 values, quantised in place (operands swapped: a lane's acc[a][b] holds 4
+// consecutive N of one row M).  A 32-column block of row m is the two n-subtiles 2p, 2p + 1 of the four lanes fg = 0..3 with this
+// lane's row; lane fg holds codes 4 fg .. 4 fg + 3 (h = 0) and 16 + 4 fg .. (h = 1) of the block, 16 bits each.  Its 16-byte word is
+// four dwords: lane fg even stores dword fg / 2 (its h = 0 codes under lane fg + 1's), lane fg odd dword 2 + fg / 2 (lane fg - 1's
+// h = 1 codes under its own).
+__device__ __forceinline__ void gemm_epilogue_gelu_mx4(f32x4 (&acc)[4][4], uint8_t* __restrict__ q, uint8_t* __restrict__ qs, int M,
+                                                       int N, int mw, int nw, int lane, int fr, int fg, const bf16* __restrict__ bias) {
+  bf16x4 bv[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    int n = nw + a * 16 + fg * 4;
+    bv[a] = *reinterpret_cast<const bf16x4*>(bias + (n < N ? n : N - 4));
+  }
+  const size_t rowb = (size_t)N / 2;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int m = mw + b * 16 + fr;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      float g[2][4];
+      float mx = 0.f;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float v = rbf(acc[2 * p + h][b][j] + (float)bv[2 * p + h][j]);
+          g[h][j] = rbf(gelu_tanh(v));
+          mx = fmaxf(mx, fabsf(g[h][j]));
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const int e = mx4_scale_exp(mx);
+      const int nb = nw + p * 32;                         // first column of the block (N % 256 == 0: wholly inside or outside)
+      const uint32_t c0 = mx4_pack4(g[0][0], g[0][1], g[0][2], g[0][3], e);
+      const uint32_t c1 = mx4_pack4(g[1][0], g[1][1], g[1][2], g[1][3], e);
+      const uint32_t o0 = (uint32_t)__shfl_xor((int)c0, 16, 64), o1 = (uint32_t)__shfl_xor((int)c1, 16, 64);
+      const uint32_t word = (fg & 1) ? (o1 | (c1 << 16)) : (c0 | (o0 << 16));
+      const int dw = (fg & 1) ? 2 + (fg >> 1) : (fg >> 1);
+      if (m < M && nb < N) {
+        *reinterpret_cast<uint32_t*>(q + (size_t)m * rowb + mx4_chunk_off(nb) + 4 * dw) = word;
+        if (fg == 0) qs[(size_t)m * (N / MX4_BLOCK) + nb / MX4_BLOCK] = (uint8_t)(e + 127);
+      }
+    }
+  }
+}
+
+template <int EPI, bool MXOUT>
+__global__ __launch_bounds__(512, 1) void gemm_mx4_kernel(const uint8_t* __restrict__ X, const uint8_t* __restrict__ SX,
+                                                          const uint8_t* __restrict__ Wt, const uint8_t* __restrict__ SW,
+                                                          bf16* __restrict__ Y, uint8_t* __restrict__ QO, uint8_t* __restrict__ SO,
+                                                          int M, int N, int K, int ldo, int ntm, int ntn, EpiArgs ea) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  int lid = xcd_remap(blockIdx.x, ntm * ntn), mt_, nt_;
+  tile_of(lid, ntm, ntn, M4_GROUP_M, mt_, nt_);
+  const int m0 = mt_ * M4_BM, n0 = nt_ * M4_BN;
+  const int nk = K / MX4_SUPER, kb = K / MX4_BLOCK;
+  const size_t row = (size_t)K / 2;
+  const int fr = lane & 15, fg = lane >> 4;
+  char* const scl = smem + 2 * M4A_TILE;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = acc_zero<GQ_BF16>();
+
+  // codes of stage kt: 2048 X units + 1024 W units of 16 bytes, 4 + 2 LDS-DMA instructions per wave; LDS unit p of row r (either
+  // operand) holds the row's unit p ^ m4_wsw(r).  Rows past the edge re-read the last row (never stored).
+  auto stage_tile = [&](int kt, int slot) {
+    char* base = smem + slot * M4A_TILE;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      const bool isx = i < 4;
+      const int inst = isx ? wave * 4 + i : wave * 2 + (i - 4), idx = inst * 64 + lane, r = idx >> 3, u = (idx & 7) ^ m4_wsw(r);
+      const uint8_t* g;
+      int off;
+      if (isx) {
+        const int gr = m0 + r < M ? m0 + r : M - 1;
+        g = X + (size_t)gr * row + (size_t)kt * M4A_ROW + u * 16;
+        off = inst * 1024;
+      } else {
+        const int gr = n0 + r < N ? n0 + r : N - 1;
+        g = Wt + (size_t)gr * row + (size_t)kt * M4A_ROW + u * 16;
+        off = M4_BM * M4A_ROW + inst * 1024;
+      }
+      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(base + off), 16, 0, 0);
+    }
+  };
+  // scale bytes of stage kt: gemm_mx4w6_kernel's
+  auto stage_sc = [&](int kt, int slot) {
+    char* base = scl + slot * M4_SC;
+    {
+      const int j = wave * 64 + lane, r = j >> 1;
+      const int gr = m0 + r < M ? m0 + r : M - 1;
+      const uint8_t* g = SX + (size_t)gr * kb + kt * 8 + (j & 1) * 4;
+      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(base + wave * 256), 4, 0, 0);
+    }
+    {
+      const int w4 = wave & 3, j = w4 * 64 + lane, r = j >> 1;
+      const int gr = n0 + r < N ? n0 + r : N - 1;
+      const uint8_t* g = SW + (size_t)gr * kb + kt * 8 + (j & 1) * 4;
+      __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(base + M4_BM * 8 + w4 * 256), 4, 0, 0);
+    }
+  };
+  stage_tile(0, 0);
+  stage_sc(0, 0);
+  if (nk > 1) stage_sc(1, 1);
+
+  const bool live = m0 + wm * 64 < M;       // wave-uniform
+  for (int kt = 0; kt < nk; ++kt) {
+    // issued so far, oldest first: ... tile kt, scales kt + 1 (if any).  Tile kt and scales kt must have landed.
+    if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();           // stage kt is in LDS for every wave; tile slot (kt + 1) & 1, scale slot (kt + 2) % 3 are free
+    if (kt + 1 < nk) stage_tile(kt + 1, (kt + 1) & 1);
+    if (kt + 2 < nk) stage_sc(kt + 2, (kt + 2) % 3);
+    const char* xs = smem + (kt & 1) * M4A_TILE;
+    const char* ws = xs + M4_BM * M4A_ROW;
+    const uint8_t* ss = (const uint8_t*)(scl + (kt % 3) * M4_SC);
+    if (live) {
+      __builtin_amdgcn_s_setprio(1);
+      i32x4 wf[4][2], xf[4][2];
+      int sw[4][2], sx[4][2];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int rw = wn * 64 + t * 16 + fr, rx = wm * 64 + t * 16 + fr;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          wf[t][j] = *reinterpret_cast<const i32x4*>(ws + rw * M4A_ROW + ((2 * fg + j) ^ m4_wsw(rw)) * 16);
+          xf[t][j] = *reinterpret_cast<const i32x4*>(xs + rx * M4A_ROW + ((2 * fg + j) ^ m4_wsw(rx)) * 16);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          sw[t][s] = ss[M4_BM * 8 + rw * 8 + 4 * s + fg];
+          sx[t][s] = ss[rx * 8 + 4 * s + fg];
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        i32x8 wa[4], xb[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          // K-step s: unit 2 g + s of either operand (4 dwords; the top four of the 8-dword operand are not read with E2M1)
+          const i32x4 w = wf[t][s], x = xf[t][s];
+          wa[t] = (i32x8){w[0], w[1], w[2], w[3], 0, 0, 0, 0};
+          xb[t] = (i32x8){x[0], x[1], x[2], x[3], 0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wa[a], xb[b], acc[a][b], 4, 4, 0, sw[a][s], 0, sx[b][s]);
+      }
+      __builtin_amdgcn_s_setprio(0);
+    }
+  }
+  if (MXOUT) {
+    gemm_epilogue_gelu_mx4(acc, QO, SO, M, N, m0 + wm * 64, n0 + wn * 64, lane, fr, fg, ea.bias);
+  } else if (EPI == LL_EPI_BIAS_GELU) {     // (register form, as gemm_mx6_kernel's)
+    gemm_epilogue<EPI, GQ_BF16, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, fr, fg, ea);
+  } else {
+    __builtin_amdgcn_s_barrier();           // every wave has read its last stage's fragments: the ring is free
+    gemm_epilogue_lds<EPI, GQ_BF16, 4, 4>(acc, Y, M, N, ldo, m0 + wm * 64, n0 + wn * 64, lane, smem + wave * (64 * EPI_ROW_BYTES(4)), ea);
+  }
+}
+
+extern "C" int ll_gemm_plan_mx4(int M, int N, int K, char* out, int cap) {
+  LL_REQUIRE(out != nullptr && cap > 0, "ll_gemm_plan_mx4: needs an output buffer");
+  (void)K;
+  int ntm = (M + M4_BM - 1) / M4_BM, ntn = (N + M4_BN - 1) / M4_BN;
+  snprintf(out, (size_t)cap, "gemm_mx4_kernel tile %dx%d, 256 k per stage, %d workgroups, groups of %d m-tiles", M4_BM, M4_BN,
+           ntm * ntn, M4_GROUP_M);
+  return LL_OK;
+}
+
+static int mx4_launch(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, bf16* out, uint8_t* qo, uint8_t* so,
+                      int M, int N, int K, int ldo, int epilogue, const EpiArgs& ea, hipStream_t s) {
+  const int ntm = (M + M4_BM - 1) / M4_BM, ntn = (N + M4_BN - 1) / M4_BN;
+  const dim3 grid(ntm * ntn), block(512);
+#define LAUNCH(E, Q)                                                                                                            \
+  do {                                                                                                                          \
+    if (int rc_ = ll_lds_attr((const void*)gemm_mx4_kernel<E, Q>, M4A_LDS)) return rc_;                                        \
+    hipLaunchKernelGGL((gemm_mx4_kernel<E, Q>), grid, block, M4A_LDS, s, xq, sx, wq, sw, out, qo, so, M, N, K, ldo, ntm, ntn, ea); \
+  } while (0)
+  if (qo != nullptr) LAUNCH(LL_EPI_BIAS_GELU, true);
+  else if (epilogue == LL_EPI_BIAS) LAUNCH(LL_EPI_BIAS, false);
+  else if (epilogue == LL_EPI_BIAS_GELU) LAUNCH(LL_EPI_BIAS_GELU, false);
+  else if (epilogue == LL_EPI_BIAS_GATE_RES) LAUNCH(LL_EPI_BIAS_GATE_RES, false);
+  else LAUNCH(LL_EPI_BIAS_RES, false);
+#undef LAUNCH
+  return LL_OK;
+}
+
+extern "C" int ll_gemm_mx4(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias,
+                           ll_bf16* out, uint8_t* q_out, uint8_t* s_out, int M, int N, int K, int ldo, int epilogue, const ll_bf16* res,
+                           const ll_bf16* e, const ll_bf16* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len,
+                           ll_stream stream) {
+  int rc = mx6_check("ll_gemm_mx4", xq, sx, wq, sw, M, N, K, ldo, epilogue, bias, res, e, nmod, gate_idx, rows_per_batch, frame_len);
+  if (rc) return rc;
+  LL_REQUIRE((q_out == nullptr) == (s_out == nullptr), "ll_gemm_mx4: the MXFP4 output needs both codes and scales");
+  LL_REQUIRE((out != nullptr) != (q_out != nullptr), "ll_gemm_mx4: exactly one of out (bf16) and q_out / s_out (MXFP4) is required");
+  if (q_out != nullptr) {
+    LL_REQUIRE(epilogue == LL_EPI_BIAS_GELU, "ll_gemm_mx4: the MXFP4 output exists for the GELU epilogue only (epilogue %d)", epilogue);
+    LL_REQUIRE(N % MX4_SUPER == 0 && ldo == N, "ll_gemm_mx4: the MXFP4 output needs N=%d a multiple of 256 and ldo == N", N);
+  }
+  if (M == 0) return LL_OK;
+  EpiArgs ea{(const bf16*)bias, (const bf16*)res, (const bf16*)e, (const bf16*)mod, nullptr, nullptr, nmod, gate_idx,
+             rows_per_batch, frame_len, frame_len > 0 && rows_per_batch > 0 ? rows_per_batch / frame_len : 0};
+  if (int lrc = mx4_launch(xq, sx, wq, sw, (bf16*)out, q_out, s_out, M, N, K, ldo, epilogue, ea, (hipStream_t)stream)) return lrc;
+  return ll_check_launch("ll_gemm_mx4");
+}
+
+extern "C" int ll_gemm_mx4_qkv(const uint8_t* xq, const uint8_t* sx, const uint8_t* wq, const uint8_t* sw, const ll_bf16* bias,
+                               ll_bf16* out, int M, int N, int K, int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start,
+                               int roped_offset, int write_len, ll_stream stream) {
+  int rc = mx6_check("ll_gemm_mx4_qkv", xq, sx, wq, sw, M, N, K, ldo, LL_EPI_BIAS, bias, nullptr, nullptr, 0, 0, 0, 0);
+  if (rc) return rc;
+  LL_REQUIRE(out != nullptr, "ll_gemm_mx4_qkv: out is required");
+  LL_REQUIRE(cache_v != nullptr, "ll_gemm_mx4_qkv: cache_v is required");
+  LL_REQUIRE(N % 3 == 0 && (N / 3) % 8 == 0, "ll_gemm_mx4_qkv: N=%d must be 3 C with C a multiple of 8", N);
+  LL_REQUIRE(B > 0 && L > 0 && M == B * L, "ll_gemm_mx4_qkv: M=%d is not B=%d x L=%d", M, B, L);
+  LL_REQUIRE(write_len >= 0 && roped_offset >= 0 && (write_len == 0 || roped_offset + write_len <= L),
+             "ll_gemm_mx4_qkv: write window outside the new tokens");
+  LL_REQUIRE(write_len == 0 || (write_start >= 0 && write_start + write_len <= S),
+             "ll_gemm_mx4_qkv: write [%d,+%d) outside cache of %d slots", write_start, write_len, S);
+  EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
+  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
+  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+  if (int lrc = mx4_launch(xq, sx, wq, sw, (bf16*)out, nullptr, nullptr, M, N, K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
+  return ll_check_launch("ll_gemm_mx4_qkv");
+}

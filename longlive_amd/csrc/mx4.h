@@ -53,6 +53,11 @@ __host__ __device__ __forceinline__ uint32_t mx4_pack8(const float (&f)[8], int 
   return w;
 }
 
+// four codes packed into bits 4j .. 4j + 3 of a 16-bit value
+__host__ __device__ __forceinline__ uint32_t mx4_pack4(float x0, float x1, float x2, float x3, int e) {
+  return mx4_code(x0, e) | (mx4_code(x1, e) << 4) | (mx4_code(x2, e) << 8) | (mx4_code(x3, e) << 12);
+}
+
 // byte offset inside a packed row of the 4 bytes holding k = c8 .. c8 + 7 (c8 % 8 == 0): quarter c8 / 8 % 4 of 32-k block j
 __host__ __device__ __forceinline__ int mx4_chunk_off(int c8) {
   int j = (c8 >> 5) & 7;

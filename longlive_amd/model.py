@@ -146,7 +146,8 @@ class CausalWanModelHIP(nn.Module):
         # six on the block-scaled e4m3 MFMA (one power-of-two scale per 32 elements of K for activations and weights alike).
         # "fp8_rowwise": int8's per-token / per-output-channel scales with e4m3 codes, on the W8A8 kernels' structure.  "mxfp6": mxfp8's
         # per-32 block scales with E2M3 (FP6) codes packed 6 bits each, on the MFMA's FP4-rate form.  "mxfp4_a6": mxfp6's activations
-        # with E2M1 (FP4) weights packed 4 bits each (W4A6).
+        # with E2M1 (FP4) weights packed 4 bits each (W4A6).  "mxfp4_a4": those E2M1 weights over E2M1 activations in the same scheme
+        # and layout (W4A4).
         self.quant: Optional[str] = None
         # None: bf16 self-attention.  "mxfp8": self-attention on the block-scaled e4m3 MFMA over an MX shadow of each layer's KV cache
         # (kept in the cache dict under _MX_SHADOW, re-derived after every write; orthogonal to `quant`).
@@ -203,7 +204,7 @@ class CausalWanModelHIP(nn.Module):
         for blk in self.blocks:
             sa = blk.self_attn
             ts = [sa.q.weight, sa.k.weight, sa.v.weight, sa.q.bias, sa.k.bias, sa.v.bias, blk.modulation]
-            if self.quant in ("int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6"):
+            if self.quant in ("int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4"):
                 ts += [sa.o.weight, blk.cross_attn.q.weight, blk.cross_attn.o.weight, blk.ffn[0].weight, blk.ffn[2].weight]
             key.extend((t.data_ptr(), t._version) for t in ts)
         return tuple(key)
@@ -223,7 +224,7 @@ class CausalWanModelHIP(nn.Module):
             )
             if self.quant is not None:
                 quantize = {"int8": ops.quantize_rows, "mxfp8": ops.quantize_mx, "fp8_rowwise": ops.quantize_rows_f8,
-                            "mxfp6": ops.quantize_mx6, "mxfp4_a6": ops.quantize_mx4}[self.quant]
+                            "mxfp6": ops.quantize_mx6, "mxfp4_a6": ops.quantize_mx4, "mxfp4_a4": ops.quantize_mx4}[self.quant]
                 for name, w in (("qkv", d["wqkv"]), ("o", sa.o.weight), ("cq", ca.q.weight), ("co", ca.o.weight),
                                 ("f1", blk.ffn[0].weight), ("f2", blk.ffn[2].weight)):
                     d["q_" + name], d["s_" + name] = quantize(w.detach().contiguous())
@@ -235,13 +236,13 @@ class CausalWanModelHIP(nn.Module):
 
     def set_quant(self, mode: Optional[str]):
         """None (bf16), "int8" (W8A8 block linears), "mxfp8" (MXFP8 block linears), "fp8_rowwise" (e4m3 codes with per-token /
-        per-output-channel scales), "mxfp6" (MXFP6 E2M3 block linears) or "mxfp4_a6" (MXFP4 E2M1 weights over MXFP6 activations).
-        Weights are (re)quantised lazily at the next forward."""
-        if mode not in (None, "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6"):
+        per-output-channel scales), "mxfp6" (MXFP6 E2M3 block linears), "mxfp4_a6" (MXFP4 E2M1 weights over MXFP6 activations) or
+        "mxfp4_a4" (MXFP4 E2M1 weights and activations).  Weights are (re)quantised lazily at the next forward."""
+        if mode not in (None, "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4"):
             raise ValueError(f"unknown quantisation mode {mode!r}")
         if mode is not None and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
             raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 128")
-        if mode in ("mxfp6", "mxfp4_a6") and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
+        if mode in ("mxfp6", "mxfp4_a6", "mxfp4_a4") and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
             raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 256 (packed 256-k super-blocks)")
         self.quant = mode
         self._packed = None
@@ -273,7 +274,11 @@ class CausalWanModelHIP(nn.Module):
         """One block linear: bf16 MFMA GEMM, or W8A8 GEMM in int8 mode (same fused epilogues).  In int8 mode `x` is either
         a bf16 tensor (quantised here, per token) or an already quantised (int8, scale) pair from a fused producer; in mxfp8 mode
         likewise a bf16 tensor or an (e4m3 codes, block scales) pair, and in fp8_rowwise mode an (e4m3 codes, row scale) pair; mxfp6 and
-        mxfp4_a6 take a bf16 tensor or an MXFP6 (packed E2M3 codes, block scales) pair."""
+        mxfp4_a6 take a bf16 tensor or an MXFP6 (packed E2M3 codes, block scales) pair, and mxfp4_a4 a bf16 tensor or an MXFP4 (packed
+        E2M1 codes, block scales) pair."""
+        if self.quant == "mxfp4_a4":
+            xm = x if isinstance(x, tuple) else ops.quantize_mx4(x)
+            return ops.gemm_mx4(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
         if self.quant == "mxfp4_a6":
             xm = x if isinstance(x, tuple) else ops.quantize_mx6(x)
             return ops.gemm_mx4w6(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
@@ -386,6 +391,7 @@ class CausalWanModelHIP(nn.Module):
         mx = self.quant == "mxfp8"
         f8 = self.quant == "fp8_rowwise"
         m6 = self.quant in ("mxfp6", "mxfp4_a6")          # MXFP6 activations (E2M3 or E2M1 weights)
+        m4 = self.quant == "mxfp4_a4"                     # MXFP4 activations
         G, E = _kv_state(kvc)
         S = kvc["k"].shape[1]
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
@@ -401,6 +407,8 @@ class CausalWanModelHIP(nn.Module):
             h1 = ops.ln_modulate_tab_mx(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 0, 1, F, c.eps)
         elif m6:
             h1 = ops.ln_modulate_tab_mx6(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx6(xs, e0, mod, 0, 1, F, c.eps)
+        elif m4:
+            h1 = ops.ln_modulate_tab_mx4(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx4(xs, e0, mod, 0, 1, F, c.eps)
         elif f8:
             h1 = ops.ln_modulate_tab_f8(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_f8(xs, e0, mod, 0, 1, F, c.eps)
         elif tab32 is not None:
@@ -415,6 +423,9 @@ class CausalWanModelHIP(nn.Module):
                 qkv_m6 = ops.gemm_mx4w6_qkv_v_insert if self.quant == "mxfp4_a6" else ops.gemm_mx6_qkv_v_insert
                 qkv = qkv_m6(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start, plan.roped_offset, plan.write_len,
                              B, L)
+            elif m4:
+                qkv = ops.gemm_mx4_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
+                                                plan.roped_offset, plan.write_len, B, L)
             elif f8:
                 qkv = ops.gemm_f8_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
                                                plan.roped_offset, plan.write_len, B, L)
@@ -450,7 +461,7 @@ class CausalWanModelHIP(nn.Module):
         self._lin(att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=2, rows_per_batch=L, frame_len=fs)
         # --- cross attention (causal_model.py:460; model.py:159-194) ---
-        xn = (ops.layernorm_affine_mx if mx else ops.layernorm_affine_mx6 if m6 else ops.layernorm_affine_f8 if f8 else ops.layernorm_affine_q8 if q8 else
+        xn = (ops.layernorm_affine_mx if mx else ops.layernorm_affine_mx6 if m6 else ops.layernorm_affine_mx4 if m4 else ops.layernorm_affine_f8 if f8 else ops.layernorm_affine_q8 if q8 else
               ops.layernorm_affine)(xs, blk.norm3.weight, blk.norm3.bias, c.eps)
         fuse_qn = (self.fuse_cross_qnorm and self.quant is None and ops.gemm_ssq_planes(B * L, C, C) == Hh and ops.flash_attn_qnorm_ok(Hh, c.text_len))
         if fuse_qn:
@@ -475,14 +486,17 @@ class CausalWanModelHIP(nn.Module):
             h2 = ops.ln_modulate_tab_mx(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 3, 4, F, c.eps)
         elif m6:
             h2 = ops.ln_modulate_tab_mx6(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx6(xs, e0, mod, 3, 4, F, c.eps)
+        elif m4:
+            h2 = ops.ln_modulate_tab_mx4(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx4(xs, e0, mod, 3, 4, F, c.eps)
         elif f8:
             h2 = ops.ln_modulate_tab_f8(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_f8(xs, e0, mod, 3, 4, F, c.eps)
         elif tab32 is not None:
             h2 = ops.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps, q8=q8)
         else:
             h2 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 3, 4, F, c.eps)
-        # (mxfp8 / mxfp6 / mxfp4_a6: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
-        ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU, **(dict(mx_out=True) if mx or m6 else {}))
+        # (mxfp8 / mxfp6 / mxfp4_a6 / mxfp4_a4: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
+        ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU,
+                       **(dict(mx_out=True) if mx or m6 or m4 else {}))
         self._lin(ff, pk, "f2", blk.ffn[2].weight, blk.ffn[2].bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=5, rows_per_batch=L, frame_len=fs)
         return plan

@@ -1310,6 +1310,126 @@ def gemm_plan_mx4w6(M: int, N: int, K: int) -> str:
     return buf.value.decode()
 
 
+# ---- W4A4: MXFP4 activations and weights (both as from quantize_mx4: packed E2M1 [rows, K/2] + E8M0 scales [rows, K / 32]) ----------
+def _mx4_empty(shape, device):
+    K = shape[-1]
+    assert K % 256 == 0, f"MXFP4 rows need K % 256 == 0, got {K}"
+    rows = math.prod(shape) // K
+    return torch.empty(*shape[:-1], K // 2, dtype=u8, device=device), torch.empty(rows, K // 32, dtype=u8, device=device)
+
+
+def gemm_mx4(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
+             rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
+    """gemm_mx4w6 with MXFP4 activations: xm = (packed E2M1 codes [..., K/2], scales) as from quantize_mx4 or an MXFP4 producer,
+    wm = (packed E2M1 codes [N, K/2], scales).  mx_out (GELU only): returns the MXFP4 codes + scales of the bf16 result instead of it."""
+    xq, sx, M, K = _mx4_pair(xm, "xq")
+    wq, sw, N, Kw = _mx4_pair(wm, "wq")
+    _chk(bias, "bias")
+    assert Kw == K and wq.dim() == 2 and bias.numel() == N, (wq.shape, K, bias.shape)
+    nmod = 0
+    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
+        _chk(res, "res")
+        assert res.numel() == M * N
+    if epilogue == EPI_BIAS_GATE_RES:
+        _chk(e, "e")
+        nmod = e.shape[-2]
+        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
+        if mod is not None:
+            _chk(mod, "mod")
+            assert mod.numel() == nmod * N
+    if mx_out:
+        assert epilogue == EPI_BIAS_GELU and out is None
+        qo, so = _mx4_empty((*xq.shape[:-1], N), xq.device)
+    else:
+        qo = so = None
+        if out is None:
+            out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
+        _chk(out, "out")
+        assert out.numel() == M * N
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_gemm_mx4(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), _ptr(out), _ptr(qo), _ptr(so),
+                               M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
+               "ll_gemm_mx4")
+    _t1(tag, t0, 2.0 * M * N * K)
+    return (qo, so) if mx_out else out
+
+
+def gemm_mx4_qkv_v_insert(xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int,
+                          tag: str = "gemm_qkv"):
+    """gemm_mx6_qkv_v_insert on MXFP4 operands.  Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v
+    [B, S, H, D]."""
+    xq, sx, M, K = _mx4_pair(xm, "xq")
+    wq, sw, N, Kw = _mx4_pair(wm, "wq")
+    _chk(bias, "bias"); _chk(cache_v, "cache_v")
+    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
+    S = cache_v.shape[1]
+    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
+    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_gemm_mx4_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                   M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
+               "ll_gemm_mx4_qkv")
+    _t1(tag, t0, 2.0 * M * N * K)
+    return out
+
+
+def ln_modulate_mx4(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate emitting the MXFP4 codes + scales of its bf16 output."""
+    _chk(x, "x"); _chk(e, "e")
+    B, L, Cc = x.shape
+    nmod = e.shape[-2]
+    assert e.shape == (B, num_frames, nmod, Cc)
+    if mod is not None:
+        _chk(mod, "mod")
+        assert mod.numel() == nmod * Cc
+    q, s = _mx4_empty((B, L, Cc), x.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_ln_modulate_mx4(x.data_ptr(), q.data_ptr(), s.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
+                                      B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_mx4")
+    _t1(tag, t0, 2.53 * x.numel())
+    return q, s
+
+
+def ln_modulate_tab_mx4(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate_tab emitting the MXFP4 codes + scales of its bf16 output."""
+    _chk(x, "x"); _chk(tab, "tab", torch.float32)
+    B, L, Cc = x.shape
+    nmod = tab.shape[2]
+    assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
+    q, s = _mx4_empty((B, L, Cc), x.device)
+    lib = _lib.load()
+    t0 = _t0(tag)
+    _lib.check(lib.ll_ln_modulate_tab_mx4(x.data_ptr(), q.data_ptr(), s.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
+                                          B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab_mx4")
+    _t1(tag, t0, 2.53 * B * L * Cc)
+    return q, s
+
+
+def layernorm_affine_mx4(x, w, b, eps: float):
+    """layernorm_affine emitting the MXFP4 codes + scales of its bf16 output."""
+    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
+    Cc = x.shape[-1]
+    assert w.numel() == Cc and b.numel() == Cc
+    q, s = _mx4_empty(tuple(x.shape), x.device)
+    lib = _lib.load()
+    t0 = _t0("layernorm_affine")
+    _lib.check(lib.ll_layernorm_affine_mx4(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // Cc, Cc,
+                                           eps, _stream()), "ll_layernorm_affine_mx4")
+    _t1("layernorm_affine", t0, 2.53 * x.numel())
+    return q, s
+
+
+def gemm_plan_mx4(M: int, N: int, K: int) -> str:
+    """Kernel instance, tile and grid of a gemm_mx4 / gemm_mx4_qkv_v_insert call (host only)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().ll_gemm_plan_mx4(M, N, K, buf, 256), "ll_gemm_plan_mx4")
+    return buf.value.decode()
+
+
 # ---- MXFP8 self-attention over a block-scaled shadow of the KV cache (attention_mx.hip) ------------------------------------------
 def kv_shadow_mx_alloc(cache_k) -> dict:
     """Uninitialised MX shadow of one layer's cache k (or v) [B, S, H, 128]: K^ codes [B, S32, H, 128] + scales [B, S32, H, 4],

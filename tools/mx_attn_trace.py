@@ -13,7 +13,7 @@ self-attention kernel of bf16 mode; cross-attention keeps flash_attn_asm_qn_kern
     rocprofv3 --kernel-trace --stats -d <dir> -o run -- python tools/mx_attn_trace.py --quant fp8_rowwise --attn-quant none
 
 and the MXFP6 trace: --quant mxfp6 --attn-quant none; the W4A6 trace: --quant mxfp4_a6
---attn-quant none."""
+--attn-quant none; the W4A4 trace: --quant mxfp4_a4 --attn-quant none."""
 from __future__ import annotations
 
 import argparse
@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--quant", default="none", help="block linears: none | int8 | mxfp8 | fp8_rowwise | mxfp6 | mxfp4_a6")
+    ap.add_argument("--quant", default="none", help="block linears: none | int8 | mxfp8 | fp8_rowwise | mxfp6 | mxfp4_a6 | mxfp4_a4")
     ap.add_argument("--attn-quant", default="mxfp8", help="self-attention: none | mxfp8")
     args = ap.parse_args(argv)
     import torch

@@ -1,13 +1,14 @@
 """Frames/s of the block-linear precisions (none = bf16, int8 = W8A8, mxfp8 = MXFP8, fp8_rowwise = e4m3 with per-token / per-channel
-scales, mxfp6 = MXFP6 E2M3, mxfp4_a6 = E2M1 weights over MXFP6 activations), each with bf16 self-attention or with MXFP8
+scales, mxfp6 = MXFP6 E2M3, mxfp4_a6 = E2M1 weights over MXFP6 activations,
+mxfp4_a4 = E2M1 weights and activations), each with bf16 self-attention or with MXFP8
 self-attention over the shadow of the KV cache ("+attn": set_attn_quant("mxfp8")), alternated in one process.
 
 Workload = bench.py's fps_of: the LongLive-1.3B random-init generator, config 2's steady state (4 warm-up blocks, then timed blocks
 through pipe.stream).  The modes run in turn for --rounds rounds, so a clock drift of the device lands on all of them alike; the
 record holds the median frames/s, ms per block and average GPU clock per mode, and per-kernel tables of one extra (timed-launch)
-block of mxfp8, fp8_rowwise, mxfp6, mxfp4_a6 and none+attn (those among --modes), with the MX / FP8 / MXFP6 / W4A6 GEMM and MX
-attention plan strings.  With both mxfp6 and mxfp4_a6 among --modes, the record also compares each GEMM shape's launch in the two
-(median over --rounds timed blocks of each, alternated).
+block of mxfp8, fp8_rowwise, mxfp6, mxfp4_a6, mxfp4_a4 and none+attn (those among --modes), with the MX / FP8 / MXFP6 / W4A6 /
+W4A4 GEMM and MX attention plan strings.  With both mxfp6 and mxfp4_a6 among --modes, the record also compares each GEMM shape's
+launch in the two (median over --rounds timed blocks of each, alternated); likewise mxfp4_a4 against mxfp4_a6.
 
     python tools/quant_fps.py --rounds 3 --blocks 4 --out profiles/quant_fps.json
 """
@@ -23,8 +24,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "none+attn", "int8+attn", "mxfp8+attn", "fp8_rowwise+attn",
-         "mxfp6+attn", "mxfp4_a6+attn")
+MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4", "none+attn", "int8+attn", "mxfp8+attn", "fp8_rowwise+attn",
+         "mxfp6+attn", "mxfp4_a6+attn", "mxfp4_a4+attn")
 
 
 def main(argv=None):
@@ -94,19 +95,24 @@ def main(argv=None):
         return {t: dict(launches=v["launches"], avg_us=1e3 * v["avg_ms"], total_ms=v["total_ms"])
                 for t, v in sorted(summ.items(), key=lambda kv: -kv[1]["total_ms"])}
 
-    tables = {m: kernel_table(m) for m in ("mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "none+attn") if m in modes}
-    gemm_vs = None
-    if "mxfp6" in modes and "mxfp4_a6" in modes:
-        per = {"mxfp6": [], "mxfp4_a6": []}
+    tables = {m: kernel_table(m) for m in ("mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4", "none+attn") if m in modes}
+
+    def gemm_launch_vs(new, old):
+        """Each GEMM shape's launch time in `new` against `old` (median over --rounds timed blocks of each, alternated)."""
+        per = {new: [], old: []}
         for _ in range(args.rounds):
             for m in per:
                 per[m].append(kernel_table(m))
-        gemm_vs = {}
+        vs = {}
         for t in ("gemm_f1", "gemm_f2", "gemm_qkv", "gemm_o", "gemm_co", "gemm_cq"):
             if not all(t in tb for m in per for tb in per[m]):
                 continue
             us = {m: statistics.median(tb[t]["avg_us"] for tb in per[m]) for m in per}
-            gemm_vs[t] = dict(mxfp4_a6_us=us["mxfp4_a6"], mxfp6_us=us["mxfp6"], ratio=us["mxfp4_a6"] / us["mxfp6"])
+            vs[t] = {f"{new}_us": us[new], f"{old}_us": us[old], "ratio": us[new] / us[old]}
+        return vs
+
+    gemm_vs = gemm_launch_vs("mxfp4_a6", "mxfp6") if "mxfp6" in modes and "mxfp4_a6" in modes else None
+    gemm_vs4 = gemm_launch_vs("mxfp4_a4", "mxfp4_a6") if "mxfp4_a6" in modes and "mxfp4_a4" in modes else None
     M = 3 * cfg.frame_seqlen
     S = cfg.local_attn_size * cfg.frame_seqlen
     shapes = (("gemm_qkv", 3 * cfg.dim, cfg.dim), ("gemm_o / gemm_cq / gemm_co", cfg.dim, cfg.dim), ("gemm_f1", cfg.ffn_dim, cfg.dim),
@@ -115,6 +121,7 @@ def main(argv=None):
     plans_f8 = {name: ops.gemm_plan_f8(M, n, k) for name, n, k in shapes}
     plans_mx6 = {name: ops.gemm_plan_mx6(M, n, k) for name, n, k in shapes}
     plans_mx4 = {name: ops.gemm_plan_mx4w6(M, n, k) for name, n, k in shapes}
+    plans_mx4a4 = {name: ops.gemm_plan_mx4(M, n, k) for name, n, k in shapes}
     sink = cfg.sink_size * cfg.frame_seqlen
     attn_plan = ops.flash_attn_mx_plan(M, cfg.num_heads, 1, [(0, sink), (sink, S)])
     gen.model.set_quant(None)
@@ -122,9 +129,11 @@ def main(argv=None):
     rec = dict(tool="tools/quant_fps.py", device=torch.cuda.get_device_name(0), rounds=args.rounds, blocks=args.blocks,
                workload="bench.py fps_of: LongLive-1.3B random-init, config 2 steady state, 4 warm-up blocks, timed blocks via pipe.stream",
                median=med, runs=rows, mxfp8_gemm_plans=plans, fp8_rowwise_gemm_plans=plans_f8, mxfp6_gemm_plans=plans_mx6,
-               mxfp4_a6_gemm_plans=plans_mx4, flash_attn_mx_plan=attn_plan)
+               mxfp4_a6_gemm_plans=plans_mx4, mxfp4_a4_gemm_plans=plans_mx4a4, flash_attn_mx_plan=attn_plan)
     if gemm_vs is not None:
         rec["mxfp4_a6_vs_mxfp6_gemm_launch_us"] = gemm_vs
+    if gemm_vs4 is not None:
+        rec["mxfp4_a4_vs_mxfp4_a6_gemm_launch_us"] = gemm_vs4
     for m, kern in tables.items():
         rec[m.replace("+", "_") + "_kernels_one_block"] = kern
     print(json.dumps(dict(median=med)), flush=True)
@@ -144,6 +153,12 @@ def main(argv=None):
     if gemm_vs is not None:
         for t, v in gemm_vs.items():
             print(f"  {t:9s} mxfp4_a6 {v['mxfp4_a6_us']:7.1f} us vs mxfp6 {v['mxfp6_us']:7.1f} us ({v['ratio']:.3f})")
+    if "mxfp4_a4" in tables:
+        for name, p in plans_mx4a4.items():
+            print(f"mxfp4_a4 {name}: {p}")
+    if gemm_vs4 is not None:
+        for t, v in gemm_vs4.items():
+            print(f"  {t:9s} mxfp4_a4 {v['mxfp4_a4_us']:7.1f} us vs mxfp4_a6 {v['mxfp4_a6_us']:7.1f} us ({v['ratio']:.3f})")
     if "none+attn" in tables:
         print(f"flash_attn_mx: {attn_plan}")
         for t in ("flash_attn_self_mx", "kv_shadow_mx"):
