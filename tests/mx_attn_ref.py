@@ -93,9 +93,10 @@ def tiles(segments) -> List[Tuple[int, int, int]]:
     return out
 
 
-def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = None, dtype=torch.float32) -> Tensor:
+def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = None, dtype=torch.float32, rcp: bool = False) -> Tensor:
     """The kernel's arithmetic on dequantised shadows kd, vd [B, S32, H, 128] (deq_k / deq_v): q [B, Lq, H, 128] bf16 -> fp32 O / l
-    [B, Lq, H, 128].  dtype: the accumulation type (float32 = the kernel's; float64 to measure the quantisation alone)."""
+    [B, Lq, H, 128].  dtype: the accumulation type (float32 = the kernel's; float64 to measure the quantisation alone).  rcp: the
+    kernel's normalisation, fp32(O) times the fp32 reciprocal of fp32(l), instead of one division (for data whose sums are exact)."""
     B, Lq, H, D = q.shape
     S32 = kd.shape[1]
     if scale is None:
@@ -123,14 +124,17 @@ def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = Non
         l = l * alpha.to(dtype) + ph.sum(-1, keepdim=True)
         O = O * alpha.to(dtype) + ph @ vdh[:, :, idx]
         M = Mn
+    if rcp:
+        return (O.float() * (1.0 / l.float())).permute(0, 2, 1, 3)
     return (O / l).permute(0, 2, 1, 3).float()
 
 
-def mx_attention_cache(q: Tensor, k: Tensor, v: Tensor, segments, scale: float = None, dtype=torch.float32) -> Tensor:
+def mx_attention_cache(q: Tensor, k: Tensor, v: Tensor, segments, scale: float = None, dtype=torch.float32,
+                       rcp: bool = False) -> Tensor:
     """mx_attention straight from the bf16 cache k, v [B, S, H, 128] (shadows derived here)."""
     kd = deq_k(*shadow_k(k), dtype=dtype)
     vd = deq_v(*shadow_v(v), dtype=dtype)
-    return mx_attention(q, kd, vd, segments, scale, dtype)
+    return mx_attention(q, kd, vd, segments, scale, dtype, rcp)
 
 
 class MXAttnRefModel(mx_ref.MXRefModel):

@@ -9,6 +9,9 @@ import torch
 import fp8_ref
 from conftest import load_golden
 from longlive_amd import synth
+from quant_exact import epi_tail as _epi_ref
+from quant_exact import exact_operands as _exact_operands
+from quant_exact import hard_x_f8 as _hard_x
 from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
 from util import assert_bf16_close, bf, bf16_ulp_distance, cosine, rel_l2
 
@@ -30,20 +33,6 @@ def ops():
 
 def hn(name, shape, scale=1.0):
     return (scale * synth.hash_normal(113, name, shape)).to(bf)
-
-
-def _hard_x(rows, K, seed):
-    """Gaussian rows with x100 outlier channels, all-zero rows, rows of values in the e4m3 subnormal range beside one large value,
-    tiny rows, negative zeros."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(rows, K, generator=g)
-    x[:, torch.randperm(K, generator=g)[:4]] *= 100
-    x[::97] = 0
-    x[1::89] *= 2.0 ** -14
-    x[1::89, 5] = 300.0
-    x[2::83] *= 2.0 ** -40
-    x[3::79, :64] = -0.0
-    return x.to(bf)
 
 
 def _same(got, ref, what):
@@ -77,31 +66,6 @@ def test_producers_emit_the_quantiser_bytes(ops):
 
 
 # ---- 3. exact data: every epilogue and every kernel instance ------------------------------------------------------------------
-def _exact_operands(M, N, K, seed):
-    """Small-integer codes (exact in e4m3 and in int8) and power-of-two scales: every product and every fp32 sum is exact."""
-    g = torch.Generator().manual_seed(seed)
-    cx = torch.randint(-4, 5, (M, K), generator=g).float()
-    cw = torch.randint(-4, 5, (N, K), generator=g).float()
-    cw[:, 0] += torch.arange(N) % 3
-    sx = torch.pow(2.0, torch.randint(-9, -3, (M,), generator=g).float())
-    sw = torch.pow(2.0, torch.randint(-9, -3, (N,), generator=g).float())
-    return cx, cw, sx, sw
-
-
-def _epi_ref(v, epi, res=None, e=None, mod=None, gate_idx=0, fs=1):
-    """The epilogue tails (include/longlive_hip.h LL_EPI_*) on the bf16 bias output v."""
-    if epi == 0:
-        return v
-    if epi == 1:
-        return torch.nn.functional.gelu(v, approximate="tanh")
-    if epi == 3:
-        return (res.float() + v.float()).to(bf)
-    B, F = e.shape[:2]
-    gate = e[:, :, gate_idx] if mod is None else (mod[gate_idx].float() + e[:, :, gate_idx].float()).to(bf)
-    gv = (v.view(B, F, fs, -1).float() * gate.float().unsqueeze(2)).to(bf).reshape(v.shape)
-    return (res.float() + gv.float()).to(bf)
-
-
 def _plan(ops, M, N, K):
     return ops.gemm_plan_f8(M, N, K).split(",")[0]
 

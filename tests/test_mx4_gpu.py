@@ -11,6 +11,7 @@ import mx4_ref
 import mx6_ref
 from conftest import load_golden
 from longlive_amd import synth
+from quant_exact import codes_and_scales as _codes_and_scales
 from test_mx_gpu import _epi_ref, _hard_x
 from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
 from util import assert_bf16_close, bf, bf16_ulp_distance, cosine, rel_l2
@@ -33,17 +34,6 @@ def ops():
 
 def hn(name, shape, scale=1.0):
     return (scale * synth.hash_normal(137, name, shape)).to(bf)
-
-
-def _codes_and_scales(rows, K, seed, asym):
-    """Small-integer code values (-2 .. 2, exact in E2M1 and E2M3) and a distinct power-of-two exponent per (row, K-block)."""
-    g = torch.Generator().manual_seed(seed)
-    c = torch.randint(-2, 3, (rows, K), generator=g).double()
-    if asym:
-        c[:, 0] = (torch.arange(rows) % 3).double()                     # W is not X's pattern transposed
-    r, b = torch.arange(rows).view(rows, 1), torch.arange(K // 32).view(1, -1)
-    ex = ((r * (5 if asym else 3) + b * (3 if asym else 5)) % 7) - 3
-    return c, ex, c * torch.pow(2.0, ex.double()).repeat_interleave(32, 1)
 
 
 def _exact_x(rows, K, seed):

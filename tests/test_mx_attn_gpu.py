@@ -4,13 +4,13 @@ products' lane maps with exact data; the kernel against the restatement on the p
 the bf16 kernel fails; the model with and without MX linears against the oracle and the reference's goldens; the switch back to bf16."""
 import math
 
-import numpy as np
 import pytest
 import torch
 
 import mx_attn_ref as MA
 from conftest import load_golden
 from longlive_amd import synth
+from quant_exact import unit_c_scale as _unit_c_scale
 from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
 from util import bf, cosine, rel_l2
 
@@ -63,16 +63,6 @@ def test_shadow_bytes_after_unaligned_insert_and_roll(ops):
     sh3 = ops.kv_shadow_mx_alloc(k3)
     ops.kv_shadow_mx(k3, v3, sh3, 0, 4690)
     _check_shadow(sh3, k3, v3)
-
-
-def _unit_c_scale():
-    """A softmax scale with float32(scale * log2 e) == 1 exactly (the kernel's c), so integer scores give P = 2^integer."""
-    s = np.float32(1.0 / 1.4426950408889634)
-    for _ in range(8):
-        if np.float32(s) * np.float32(1.4426950408889634) == np.float32(1.0):
-            return float(s)
-        s = np.nextafter(s, np.float32(1.0))
-    raise AssertionError("no unit scale")
 
 
 def test_lane_maps_with_exact_data(ops):

@@ -8,6 +8,7 @@ import torch
 import mx_ref
 from conftest import load_golden
 from longlive_amd import synth
+from quant_exact import hard_x_mx as _hard_x
 from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
 from util import assert_bf16_close, bf, cosine, rel_l2
 
@@ -28,19 +29,6 @@ def hn(name, shape, scale=1.0):
 
 def _bytes(q):
     return q.view(U8).cpu()
-
-
-def _hard_x(rows, K, seed):
-    """Gaussian rows with x100 outlier channels, a few all-zero blocks, and blocks of tiny values next to a large one (codes in the
-    e4m3 subnormal range) or entirely tiny (bf16 subnormals, exponent clamped)."""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(rows, K, generator=g)
-    x[:, torch.randperm(K, generator=g)[:4]] *= 100
-    x[::97, 32:64] = 0
-    x[1::89, 64:96] *= 2.0 ** -14
-    x[1::89, 64] = 300.0
-    x[2::83, 96:128] = 2.0 ** -132 * torch.randint(-3, 4, (len(range(2, rows, 83)), 32), generator=g)
-    return x.to(bf)
 
 
 @pytest.mark.parametrize("K", [1536, 8960])
