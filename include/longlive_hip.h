@@ -148,6 +148,8 @@ int ll_kv_roll(ll_bf16* cache_k, ll_bf16* cache_v, int B, int S, int C, int dst,
 /* ---- dense contractions (MFMA) -------------------------------------------------------------------------------- */
 
 /* out[M,N] = epilogue(x[M,K] @ w[N,K]^T + bias[N]); bf16 in/out, fp32 accumulate.  K % 64 == 0, N % 8 == 0.
+ * x [M, ldx], out [M, ldo]: row strides in elements, ldx >= K, ldo >= N, both multiples of 8 (rows start on 16 bytes: the
+ * widest loads and stores are 16-byte vectors; anything else is LL_ERR_INVALID_ARG).  The same holds for every ll_gemm_* entry point.
  * Replaces nn.Linear q/k/v/o, ffn.0/ffn.2, text_embedding, patch_embedding (as GEMM), head.head
  * (wan/modules/causal_model.py:90-93,406-408,599-603; wan/modules/model.py:172-193).
  * res [M, ldo] may alias out.  For LL_EPI_BIAS_GATE_RES: gate = bf16(mod[gate_idx,:] + e[b, f, gate_idx, :]) with

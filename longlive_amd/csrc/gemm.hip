@@ -604,7 +604,9 @@ static int launch_gemm(const void* x, const void* w, bf16* out, int M, int N, in
 static int check_epilogue(const char* fn, int M, int N, int ldo, int epilogue, const void* bias, const void* res,
                           const void* e, const void* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len) {
   LL_REQUIRE(N > 0 && N % 8 == 0, "%s: N=%d must be a positive multiple of 8", fn, N);
-  LL_REQUIRE(ldo >= N && ldo % 4 == 0, "%s: ldo=%d must be >= N and a multiple of 4", fn, ldo);
+  // the generated epilogues, the LDS-staged HIP epilogues and the split-K reduce kernels store (and load the residual as) 16-byte
+  // vectors at row * ldo + n: rows must start on 16 bytes (the direct HIP epilogue alone stores 8-byte vectors)
+  LL_REQUIRE(ldo >= N && ldo % 8 == 0, "%s: ldo=%d must be >= N and a multiple of 8", fn, ldo);
   LL_REQUIRE(bias != nullptr, "%s: bias is required", fn);
   LL_REQUIRE(epilogue >= 0 && epilogue <= 3, "%s: unknown epilogue %d", fn, epilogue);
   if (epilogue == LL_EPI_BIAS_GATE_RES) {
@@ -678,7 +680,7 @@ extern "C" int ll_gemm_bf16_ksplit(const ll_bf16* x, const ll_bf16* w, const ll_
   LL_REQUIRE(workspace_bytes >= 0 && (workspace != nullptr || workspace_bytes == 0), "ll_gemm_bf16_ksplit: workspace_bytes without a workspace");
   if (M == 0) return LL_OK;
   const int S = ll_gemm_ksplit_plan(M, N, K);
-  if (S >= 2 && workspace != nullptr && ldo % 8 == 0) {
+  if (S >= 2 && workspace != nullptr) {
     LL_REQUIRE(workspace_bytes >= (long long)S * M * N * 4 && ((size_t)workspace & 15) == 0,
                "ll_gemm_bf16_ksplit: workspace of %lld bytes, need %lld (16-byte aligned)", workspace_bytes, (long long)S * M * N * 4);
     const int r = gemm_asm_ksplit_launch((const bf16*)x, (const bf16*)w, (const bf16*)bias, (bf16*)out, M, N, K, ldx, ldo, epilogue,

@@ -351,7 +351,7 @@ int gemm_ksplit_splits(int M, int N, int K, int cus) {
 int gemm_asm_ksplit_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* out, int M, int N, int K, int ldx, int ldo,
                            int epilogue, const bf16* res, float* workspace, int splits, int gm, hipStream_t s, const bf16* norm_w,
                            float eps, bf16* h_out) {
-  if (splits < 2 || (epilogue != LL_EPI_BIAS && epilogue != LL_EPI_BIAS_RES) || (ldx % 8) != 0 || (ldo % 8) != 0) return 0;
+  if (splits < 2 || (epilogue != LL_EPI_BIAS && epilogue != LL_EPI_BIAS_RES) || (ldx % 8) != 0) return 0;      // (ldo % 8 == 0: check_epilogue)
   if ((long long)256 * ldx * 2 >= 0x7fffffffLL || (long long)256 * K * 2 >= 0x7fffffffLL) return 0;
   const int lds = 3 * 128 * 128 + 4 * 2 * 8192;
   if (int rc = ll_lds_attr((const void*)gemm_asm_128_partial, lds)) return rc;
