@@ -51,7 +51,7 @@ enum ll_epilogue {
  * ll_layernorm_affine_mx6, ll_gemm_plan_mx6);
  * 111 = MXFP4 weights over MXFP6 activations (ll_quantize_mx4, ll_gemm_mx4w6, ll_gemm_mx4w6_qkv, ll_gemm_plan_mx4w6); W4A4 block
  * linears (ll_gemm_mx4, ll_gemm_mx4_qkv, ll_ln_modulate_mx4, ll_ln_modulate_tab_mx4, ll_layernorm_affine_mx4, ll_gemm_plan_mx4) only
- * add entry points, so they keep 111. */
+ * add entry points, so they keep 111; so does ll_conv_plan. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -83,6 +83,10 @@ int ll_gemm_plan(int M, int N, int K, int int8, char* out, int cap);
  * modulation vector. */
 int ll_gemm_plan_epi(int M, int N, int K, int int8, int epilogue, int plain, char* out, int cap);
 int ll_flash_attn_plan(int Lq, int H, int B, int seg0_len, int seg1_len, int seg_adjacent, char* out, int cap);
+/* The same for ll_conv_cl (rms = 0) / ll_conv_cl_rms (rms = 1): "conv_halo_kernel<epilogue, NCB n, UP u, RMS r> tile ..., grid" or
+ * "conv_cl_kernel<epilogue, NT n, MODE m> tile ..., grid, k-steps", from the predicate and arithmetic the launch itself uses (tuning
+ * key "conv_halo" included).  Shapes ll_conv_cl rejects are rejected here; rms = 1 where ll_conv_cl_rms_ok is 0 is rejected too. */
+int ll_conv_plan(int T, int H, int W, int Cin, int Cout, int KT, int KH, int upsample, int with_res, int rms, char* out, int cap);
 
 /* ---- norms / modulation ------------------------------------------------------------------------------------- */
 
@@ -429,7 +433,9 @@ int ll_synth_hash(float* out, long long lo, long long n, unsigned long long stre
  * elements) must hold the previous two input frames of the stream -- the reference's feat_cache (vae.py:29-34) -- or
  * zeros at the start of a stream.  zero16 = 16 zero bytes on the device (source of spatial / K padding);
  * w [Cout, Kpad] bf16 with k = ((kt*KH + kh)*KH + kw)*Cin + ci, zero padded to Kpad = ceil(KT*KH*KH*Cin / 64) * 64;
- * out/res rows of ldo elements, output spatial size (H<<up, W<<up). */
+ * out/res rows of ldo elements (ldo >= Cout, ldo % 4 == 0: every store is one aligned 8-byte group of 4 channels), output spatial
+ * size (H<<up, W<<up).  res may alias out (a lane reads exactly the residual elements it overwrites, before it stores); x may not.
+ * Reads of x stay inside the T (+ 2 history) frames; columns >= Cout of a row and rows beyond the last pixel are never written. */
 int ll_conv_cl(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, const ll_bf16* res,
                ll_bf16* out, int T, int H, int W, int Cin, int Cout, int Kpad, int KT, int KH, int upsample, int ldo,
                ll_stream stream);
@@ -444,7 +450,8 @@ int ll_conv_cl_rms(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, co
                    int KH, int upsample, int ldo, ll_stream stream);
 
 /* RMS_norm over channels (+ SiLU) (wan/modules/vae.py:39-55,193-197) on channels-last rows with the reference's bf16
- * rounding points: n = bf16(||x||); y = bf16(bf16(bf16(x / max(n, 1e-12)) * sqrt(C)) * gamma); out = silu(y) if do_silu. */
+ * rounding points: n = bf16(||x||); y = bf16(bf16(bf16(x / max(n, bf16(1e-12))) * sqrt(C)) * gamma); out = silu(y) if do_silu
+ * (F.normalize's clamp_min on a bf16 norm rounds its eps to bf16). */
 int ll_rms_silu_cl(const ll_bf16* x, const ll_bf16* gamma, ll_bf16* out, long long pixels, int C, int do_silu,
                    ll_stream stream);
 

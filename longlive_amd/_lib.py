@@ -54,6 +54,7 @@ SIGNATURES = {
     "ll_gemm_bf16_ssq": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ll_flash_attn_qnorm_ok": [_i, _i],
     "ll_flash_attn_qnorm": [_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _i, _i, _ll, _i, _i, _f, _p],
+    "ll_conv_plan": [_i] * 10 + [C.c_char_p, _i],
     "ll_conv_cl": [_p] * 6 + [_i] * 10 + [_p],
     "ll_conv_cl_rms_ok": [_i] * 7,
     "ll_conv_cl_rms": [_p] * 8 + [_i] * 11 + [_p],

@@ -255,6 +255,11 @@ __device__ __forceinline__ void hl_wait_vm() {
 // x / n for a pair with ONE reciprocal per lane: the steps of the IEEE-correct fp32 division the compiler emits (Newton step on the
 // reciprocal -- done by the caller, once --, q0 = x r, two residual corrections) without its operand pre-scaling, which only acts when
 // an exponent is beyond 2^+-96: the caller takes this path for n in [2^-60, 2^60] (and |x| <= n by construction), else the plain `/`.
+// F.normalize's eps = 1e-12 as the reference applies it: clamp_min on the bf16 norm converts the scalar to bf16 (1.1015625 x 2^-40 =
+// 1.00187e-12).  With the fp32 constant a row of norm below 1e-12 was divided by a value 0.19 % smaller than the reference's: 25 % of
+// such a row's elements came out one bf16 ulp off (tests/test_vae_edges_gpu.py).  The clamp also keeps n >= 2^-40: `tame` below only
+// ever fails on its upper limit.
+#define RMS_EPS_BF16 0x1.1ap-40f
 __device__ __forceinline__ f32x2 div_by_shared(f32x2 x, float n, float r1) {
   const f32x2 nn = splat2(-n), rr = splat2(r1);
   f32x2 q = x * rr;
@@ -306,7 +311,7 @@ __device__ __forceinline__ void conv_epilogue_rms(f32x4 (&acc)[NCB][2], bf16* __
       }
     ss += __shfl_xor(ss, 16, 64);
     ss += __shfl_xor(ss, 32, 64);
-    const float n = fmaxf(rbf(sqrtf(ss)), 1e-12f);
+    const float n = fmaxf(rbf(sqrtf(ss)), RMS_EPS_BF16);
     const bool tame = n >= 0x1p-60f && n <= 0x1p60f;
     const float r0 = __builtin_amdgcn_rcpf(n);
     const float r1 = __builtin_fmaf(__builtin_fmaf(-n, r0, 1.0f), r0, r0);
@@ -513,7 +518,7 @@ __global__ __launch_bounds__(256) void rms_silu_cl_kernel(const bf16* __restrict
   }
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
-  float n = fmaxf(rbf(sqrtf(ss)), 1e-12f);
+  float n = fmaxf(rbf(sqrtf(ss)), RMS_EPS_BF16);
   if (c < C) {
     const bool tame = n >= 0x1p-60f && n <= 0x1p60f;
     float r0 = __builtin_amdgcn_rcpf(n);
@@ -633,6 +638,73 @@ extern "C" int ll_conv_cl_rms_ok(int H, int W, int Cin, int Cout, int KT, int KH
   return (Cout == 96 && conv_halo_takes(H, W, Cin, Cout, KT, KH, upsample)) ? 1 : 0;
 }
 
+// What conv_cl_launch runs for a shape under the current tuning: the one place that decides kernel, template instance, tile and grid
+// (ll_conv_plan prints it; the launcher dispatches on it).
+struct ConvPlan {
+  int Ho, Wo, M;
+  bool halo;                        // conv_halo_kernel, else conv_cl_kernel
+  // conv_halo_kernel<EPI, ncb, up, RMS>
+  int ncb, up, tiles_w, tiles_h, ntn_h;
+  long long nwg;
+  // conv_cl_kernel<EPI, nt, mode>
+  int nt, mode, nk, ntm, ntn;
+};
+
+// The shape preconditions of ll_conv_cl / ll_conv_cl_rms / ll_conv_plan.
+static int conv_check_shape(int T, int H, int W, int Cin, int Cout, int KT, int KH, int upsample) {
+  LL_REQUIRE(Cin > 0 && Cin % 8 == 0, "ll_conv_cl: Cin=%d must be a multiple of 8", Cin);
+  LL_REQUIRE(Cout > 0 && Cout % 8 == 0, "ll_conv_cl: Cout=%d must be a multiple of 8 (pad the weights)", Cout);
+  LL_REQUIRE((KT == 1 || KT == 3) && (KH == 1 || KH == 3), "ll_conv_cl: taps must be 1 or 3 (got %d x %d x %d)", KT, KH, KH);
+  LL_REQUIRE(upsample == 0 || (upsample == 1 && KT == 1 && KH == 3), "ll_conv_cl: upsample is 0, or 1 with a 1x3x3 kernel");
+  LL_REQUIRE(T > 0 && H > 0 && W > 0, "ll_conv_cl: empty input %d x %d x %d", T, H, W);
+  LL_REQUIRE(KT * KH * KH * (Cin / 8) < 4096, "ll_conv_cl: K too large for the chunk decoder");
+  const long long fb = (long long)H * W * Cin * 2;
+  LL_REQUIRE(3 * fb + 4ll * (W + 2) * Cin < (1ll << 31), "ll_conv_cl: frame of %lld bytes too large for 32-bit tap offsets", fb);
+  const long long Mll = (long long)T * (upsample ? 2 * H : H) * (upsample ? 2 * W : W);
+  LL_REQUIRE(Mll > 0 && Mll < (1ll << 31), "ll_conv_cl: too many output pixels");
+  return LL_OK;
+}
+
+static ConvPlan conv_plan(int T, int H, int W, int Cin, int Cout, int KT, int KH, int upsample) {
+  ConvPlan p{};
+  p.Ho = upsample ? 2 * H : H, p.Wo = upsample ? 2 * W : W;
+  p.M = T * p.Ho * p.Wo;
+  p.halo = conv_halo_takes(H, W, Cin, Cout, KT, KH, upsample);
+  // halo-tile kernel: 3x3x3 (96-channel tiles, or the <= 16-channel head) and the upsampled 1x3x3 (96-channel tiles)
+  const bool head = KT == 3 && Cout <= 16;
+  p.up = upsample ? 1 : 0;
+  p.ncb = head ? 1 : 6;
+  p.tiles_w = (p.Wo + HL_TW - 1) / HL_TW, p.tiles_h = (p.Ho + HL_TH - 1) / HL_TH;
+  p.ntn_h = head ? 1 : Cout / 96;
+  p.nwg = (long long)T * p.tiles_h * p.tiles_w * p.ntn_h;
+  // implicit GEMM
+  const bool nt3 = (Cout % 96 == 0) && (Cout % 128 != 0), nt1 = Cout <= 32;
+  p.nt = nt1 ? 1 : nt3 ? 3 : 4;
+  p.mode = Cin < 64 ? 0 : upsample ? 2 : 1;
+  p.nk = (KT * KH * KH * Cin + 63) / 64;
+  p.ntm = (p.M + CV_BM - 1) / CV_BM, p.ntn = (Cout + 32 * p.nt - 1) / (32 * p.nt);
+  return p;
+}
+
+// Host only: the kernel instance, tile and grid ll_conv_cl (rms = 0) / ll_conv_cl_rms (rms = 1) launch for this shape under the
+// current tuning, as text.
+extern "C" int ll_conv_plan(int T, int H, int W, int Cin, int Cout, int KT, int KH, int upsample, int with_res, int rms, char* out,
+                            int cap) {
+  LL_REQUIRE(out != nullptr && cap > 0, "ll_conv_plan: needs an output buffer");
+  if (int rc = conv_check_shape(T, H, W, Cin, Cout, KT, KH, upsample)) return rc;
+  LL_REQUIRE(!rms || ll_conv_cl_rms_ok(H, W, Cin, Cout, KT, KH, upsample), "ll_conv_plan: ll_conv_cl_rms does not cover this convolution");
+  const ConvPlan p = conv_plan(T, H, W, Cin, Cout, KT, KH, upsample);
+  const char* epi = with_res ? "bias_res" : "bias";
+  if (p.halo)
+    snprintf(out, (size_t)cap, "conv_halo_kernel<%s, NCB %d, UP %d, RMS %d> tile %dx%d pixels x %d channels, %lld workgroups (%d frames x %d x %d tiles x %d n-tiles), %d units",
+             epi, p.ncb, p.up, rms ? 1 : 0, HL_TH, HL_TW, 16 * p.ncb, p.nwg, T, p.tiles_h, p.tiles_w, p.ntn_h,
+             (p.up ? 3 : 9) * (Cin / 32));
+  else
+    snprintf(out, (size_t)cap, "conv_cl_kernel<%s, NT %d, MODE %d> tile %dx%d, %d workgroups (%d m-tiles x %d n-tiles), %d k-steps",
+             epi, p.nt, p.mode, CV_BM, 32 * p.nt, p.ntm * p.ntn, p.ntm, p.ntn, p.nk);
+  return LL_OK;
+}
+
 static int conv_cl_launch(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, const ll_bf16* res,
                           ll_bf16* out, int T, int H, int W, int Cin, int Cout, int Kpad, int KT, int KH, int upsample, int ldo,
                           ll_stream stream, const ll_bf16* rms_gamma, ll_bf16* out_rms, int rms_silu);
@@ -657,22 +729,14 @@ extern "C" int ll_conv_cl_rms(const ll_bf16* x, const ll_bf16* zero16, const ll_
 static int conv_cl_launch(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, const ll_bf16* res,
                           ll_bf16* out, int T, int H, int W, int Cin, int Cout, int Kpad, int KT, int KH, int upsample, int ldo,
                           ll_stream stream, const ll_bf16* rms_gamma, ll_bf16* out_rms, int rms_silu) {
-  LL_REQUIRE(Cin > 0 && Cin % 8 == 0, "ll_conv_cl: Cin=%d must be a multiple of 8", Cin);
-  LL_REQUIRE(Cout > 0 && Cout % 8 == 0, "ll_conv_cl: Cout=%d must be a multiple of 8 (pad the weights)", Cout);
-  LL_REQUIRE((KT == 1 || KT == 3) && (KH == 1 || KH == 3), "ll_conv_cl: taps must be 1 or 3 (got %d x %d x %d)", KT, KH, KH);
-  LL_REQUIRE(upsample == 0 || (upsample == 1 && KT == 1 && KH == 3), "ll_conv_cl: upsample is 0, or 1 with a 1x3x3 kernel");
   LL_REQUIRE(x && zero16 && w && bias && (out || out_rms), "ll_conv_cl: null operand");
+  if (int rc = conv_check_shape(T, H, W, Cin, Cout, KT, KH, upsample)) return rc;
   const int taps = KT * KH * KH;
   const int nchunks = taps * (Cin / 8);
   LL_REQUIRE(Kpad % 64 == 0 && Kpad >= nchunks * 8 && Kpad < nchunks * 8 + 64, "ll_conv_cl: Kpad=%d does not match taps*Cin=%d", Kpad, nchunks * 8);
-  LL_REQUIRE(nchunks < 4096, "ll_conv_cl: K too large for the chunk decoder");
   LL_REQUIRE(ldo >= Cout && ldo % 4 == 0, "ll_conv_cl: ldo=%d must be >= Cout and a multiple of 4", ldo);
-  const long long fb = (long long)H * W * Cin * 2;
-  LL_REQUIRE(3 * fb + 4ll * (W + 2) * Cin < (1ll << 31), "ll_conv_cl: frame of %lld bytes too large for 32-bit tap offsets", fb);
-  const int Ho = upsample ? 2 * H : H, Wo = upsample ? 2 * W : W;
-  const long long Mll = (long long)T * Ho * Wo;
-  LL_REQUIRE(Mll > 0 && Mll < (1ll << 31), "ll_conv_cl: too many output pixels");
-  const int M = (int)Mll;
+  const ConvPlan p = conv_plan(T, H, W, Cin, Cout, KT, KH, upsample);
+  const int Ho = p.Ho, Wo = p.Wo, M = p.M;
   ConvGeo g;
   g.x = (const char*)x; g.zero = (const char*)zero16;
   g.T = T; g.H = H; g.W = W; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.KT = KT; g.KH = KH; g.up = upsample;
@@ -680,13 +744,11 @@ static int conv_cl_launch(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16
   EpiArgs ea{(const bf16*)bias, (const bf16*)res, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
   hipStream_t s = (hipStream_t)stream;
   {
-    // halo-tile kernel: 3x3x3 (96-channel tiles, or the <= 16-channel head) and the upsampled 1x3x3 (96-channel tiles)
-    const bool shape3 = KT == 3 && KH == 3 && !upsample, shape_up = KT == 1 && KH == 3 && upsample == 1;
-    const bool head = shape3 && Cout <= 16;
-    const int tiles_w = (Wo + HL_TW - 1) / HL_TW, tiles_h = (Ho + HL_TH - 1) / HL_TH;
-    if (conv_halo_takes(H, W, Cin, Cout, KT, KH, upsample)) {
-      const int ntn_h = head ? 1 : Cout / 96;
-      const long long nwg = (long long)T * tiles_h * tiles_w * ntn_h;
+    const bool shape_up = p.up == 1, head = p.ncb == 1;
+    const int tiles_w = p.tiles_w, tiles_h = p.tiles_h;
+    if (p.halo) {
+      const int ntn_h = p.ntn_h;
+      const long long nwg = p.nwg;
       LL_REQUIRE(nwg < (1ll << 31), "ll_conv_cl: too many tiles");
       dim3 hgrid((unsigned)nwg), hblock(512);
 #define HL_LAUNCH(E, NCBV, UPV)                                                                                        \
@@ -725,11 +787,8 @@ static int conv_cl_launch(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16
     }
   }
   LL_REQUIRE(rms_gamma == nullptr, "ll_conv_cl_rms: only the halo-tile kernel has the fused RMS_norm epilogue");
-  const int nk = Kpad / 64;
-  const bool nt3 = (Cout % 96 == 0) && (Cout % 128 != 0), nt1 = Cout <= 32;
-  const int bn = nt1 ? 32 : nt3 ? 96 : 128;
-  const int mode = Cin < 64 ? 0 : upsample ? 2 : 1;
-  int ntm = (M + CV_BM - 1) / CV_BM, ntn = (Cout + bn - 1) / bn;
+  const int nk = p.nk, mode = p.mode, ntm = p.ntm, ntn = p.ntn;
+  const bool nt3 = p.nt == 3, nt1 = p.nt == 1;
   dim3 grid(ntm * ntn), block(512);
   size_t lds = 3 * CV_STAGE;
 #define CV_LAUNCH(E, NTV, MD)                                                                                          \

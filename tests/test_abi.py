@@ -70,6 +70,9 @@ def test_no_torch_types_in_the_abi():
     (lambda L: L.ll_ln_modulate_tab(0, 1, 1, 1, 0, 6, 0, 1, 1, 9, 1536, 3, 1e-6, None), "exactly one"),
     (lambda L: L.ll_ln_modulate_tab(0, 1, 0, 0, 0, 6, 0, 7, 1, 9, 1536, 3, 1e-6, None), "bad mod index"),
     (lambda L: L.ll_conv_cl(0, 1, 1, 1, 0, 1, 2, 16, 32, 96, 96, 2624, 3, 3, 0, 96, None), "null operand"),
+    (lambda L: L.ll_conv_plan(2, 16, 32, 96, 96, 3, 3, 1, 0, 0, C.create_string_buffer(64), 64), "upsample"),
+    (lambda L: L.ll_conv_plan(2, 16, 32, 96, 192, 3, 3, 0, 0, 1, C.create_string_buffer(64), 64), "does not cover"),
+    (lambda L: L.ll_conv_plan(2, 16, 32, 96, 96, 3, 3, 0, 0, 0, None, 0), "output buffer"),
     (lambda L: L.ll_gemm_bf16_ksplit(0, 0, 1, 0, 512, 4096, 4096, 4096, 4096, 1, 0, None, 0, None), "bias or bias + residual"),
     (lambda L: L.ll_gemm_bf16_ksplit(0, 0, 1, 0, 512, 4096, 4096, 4096, 4096, 3, 0, None, 0, None), "needs res"),
     (lambda L: L.ll_gemm_bf16_ksplit(0, 0, 1, 0, 512, 4096, 4096, 4096, 4096, 0, 0, None, 64, None), "without a workspace"),
@@ -136,6 +139,31 @@ def test_gemm_plan_names_the_kernel_family_a_call_takes():
         assert lib.ll_set_tuning(key, {b"attn_asm": 1, b"attn_asm_min_keys": 512, b"gemm_asm": 35}[key]) == 0, key
     for gone in (b"no_such_key", b"attn_mfma16", b"attn_sk_wgs", b"gemm_ws", b"gemm_splitk_l2"):      # pruned in round 4: experiments/
         assert lib.ll_set_tuning(gone, 1) == -1, gone
+
+
+def test_conv_plan_names_kernel_instance_tile_and_grid():
+    """ll_conv_plan (host only) prints what conv_cl_launch dispatches on: the halo-tile kernel where conv_halo_takes, else the
+    implicit GEMM with its n-tiling and decode mode; tuning key conv_halo = 0 moves every shape to the implicit GEMM."""
+    lib = _lib.load()
+    buf = C.create_string_buffer(256)
+
+    def plan(*a):
+        _lib.check(lib.ll_conv_plan(*a, buf, 256), "plan")
+        return buf.value.decode()
+
+    assert plan(2, 30, 52, 384, 384, 3, 3, 0, 0, 0) == ("conv_halo_kernel<bias, NCB 6, UP 0, RMS 0> tile 16x32 pixels x 96 channels, "
+                                                      "32 workgroups (2 frames x 2 x 2 tiles x 4 n-tiles), 108 units")
+    assert plan(1, 15, 26, 192, 96, 1, 3, 1, 1, 1).startswith("conv_halo_kernel<bias_res, NCB 6, UP 1, RMS 1>")
+    assert plan(2, 32, 32, 96, 8, 3, 3, 0, 0, 0).startswith("conv_halo_kernel<bias, NCB 1, UP 0, RMS 0> tile 16x32 pixels x 16 channels")
+    assert plan(1, 8, 12, 16, 384, 3, 3, 0, 0, 0) == "conv_cl_kernel<bias, NT 4, MODE 0> tile 256x128, 3 workgroups (1 m-tiles x 3 n-tiles), 7 k-steps"
+    assert plan(2, 9, 7, 96, 96, 3, 3, 0, 1, 0).startswith("conv_cl_kernel<bias_res, NT 3, MODE 1> tile 256x96")
+    assert plan(2, 6, 5, 384, 192, 1, 3, 1, 0, 0).startswith("conv_cl_kernel<bias, NT 3, MODE 2>")
+    assert plan(1, 9, 24, 96, 8, 3, 3, 0, 0, 0).startswith("conv_cl_kernel<bias, NT 1, MODE 1> tile 256x32")      # odd height: never the halo kernel
+    try:
+        assert lib.ll_set_tuning(b"conv_halo", 0) == 0
+        assert plan(2, 30, 52, 384, 384, 3, 3, 0, 0, 0).startswith("conv_cl_kernel<bias, NT 4, MODE 1> tile 256x128, 39 workgroups")
+    finally:
+        assert lib.ll_set_tuning(b"conv_halo", 1) == 0
 
 
 def test_ops_refuse_cpu_tensors():
