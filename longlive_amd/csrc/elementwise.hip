@@ -149,16 +149,146 @@ __device__ __forceinline__ void emit_row(const RowWords& y, int C, int lane, int
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// MXFP8 row output: the same bf16 row, emitted as e4m3fn codes [rows, C] + E8M0 scales [rows, C / 32] (mx.h) instead of bf16.
+// A 32-column block is the chunk i of four consecutive lanes (4q .. 4q + 3), so its maximum is two shuffles inside the wave; the
+// values quantised are the packed bf16 words the bf16 form stores, so the bytes equal ll_quantize_mx of the bf16 output.
+// C % 32 == 0: a block is wholly inside or wholly outside the row.
+template <int NCH, bool FULL>
+__device__ __forceinline__ void emit_row_mx(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
+                                            uint8_t* __restrict__ qs) {
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    int c = (lane + 64 * i) * 8;
+    bool in = in_row<FULL>(c, C);
+    f32x2 v[4];
+    float mx = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = unpack2(y.w[i][j]);
+      mx = fmaxf(mx, fmaxf(fabsf(v[j].x), fabsf(v[j].y)));
+    }
+    if (!in) mx = 0.f;
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    int e = mx_scale_exp(mx);
+    if (in) {
+      uint32_t lo = mx_code4(v[0].x, v[0].y, v[1].x, v[1].y, e), hi = mx_code4(v[2].x, v[2].y, v[3].x, v[3].y, e);
+      *reinterpret_cast<uint2*>(q + (size_t)row * C + c) = make_uint2(lo, hi);
+      if ((lane & 3) == 0) qs[(size_t)row * (C / MX_BLOCK) + c / MX_BLOCK] = (uint8_t)(e + 127);
+    }
+  }
+}
+
+// MXFP6 row output: E2M3 codes packed per mx6.h [rows, 3C/4] + E8M0 scales [rows, C / 32], bit-identical to ll_quantize_mx6 of the
+// bf16 output.  A 16-k chunk of the packed row is lanes (2q, 2q + 1); C % 256 == 0.
+template <int NCH, bool FULL>
+__device__ __forceinline__ void emit_row_mx6(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
+                                             uint8_t* __restrict__ qs) {
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    int c = (lane + 64 * i) * 8;
+    bool in = in_row<FULL>(c, C);
+    float f[8];
+    float mx = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x2 v = unpack2(y.w[i][j]);
+      f[2 * j] = v.x, f[2 * j + 1] = v.y;
+      mx = fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y)));
+    }
+    if (!in) mx = 0.f;
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    int e = mx6_scale_exp(mx);
+    mx6_store_pair(mx6_pack8(f, e), q + (size_t)row * (C / 4 * 3) + mx6_chunk_off(in ? c & ~15 : 0), lane, in);
+    if (in && (lane & 3) == 0) qs[(size_t)row * (C / MX6_BLOCK) + c / MX6_BLOCK] = (uint8_t)(e + 127);
+  }
+}
+
+// MXFP4 row output: E2M1 codes packed per mx4.h [rows, C/2] + E8M0 scales [rows, C / 32], bit-identical to ll_quantize_mx4 of the
+// bf16 output.  A lane's 8 values are one dword of the packed row, a 32-k block is 4 consecutive lanes.
+template <int NCH, bool FULL>
+__device__ __forceinline__ void emit_row_mx4(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
+                                             uint8_t* __restrict__ qs) {
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    int c = (lane + 64 * i) * 8;
+    bool in = in_row<FULL>(c, C);
+    float f[8];
+    float mx = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x2 v = unpack2(y.w[i][j]);
+      f[2 * j] = v.x, f[2 * j + 1] = v.y;
+      mx = fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y)));
+    }
+    if (!in) mx = 0.f;
+    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
+    int e = mx4_scale_exp(mx);
+    if (in) {
+      *reinterpret_cast<uint32_t*>(q + (size_t)row * (C / 2) + mx4_chunk_off(c)) = mx4_pack8(f, e);
+      if ((lane & 3) == 0) qs[(size_t)row * (C / MX4_BLOCK) + c / MX4_BLOCK] = (uint8_t)(e + 127);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// How a producer's row leaves the kernel: one emitter per output format, holding the output pointers (a kernel argument) and the
+// column granule GRAN its rows need.  The three producers below are written once against emit<NCH, FULL>(y, C, lane, row).
+struct EmitBf16Q8 {      // bf16 as it is, or (q != nullptr, a run-time branch: one kernel serves both) int8 codes + per-row scale
+  static constexpr int GRAN = 8;
+  bf16* out;
+  int8_t* q;
+  float* qscale;
+  template <int NCH, bool FULL>
+  __device__ __forceinline__ void emit(const RowWords& y, int C, int lane, int row) const {
+    emit_row<NCH, FULL>(y, C, lane, row, out, q, qscale);
+  }
+};
+struct EmitF8 {          // FP8 rowwise: e4m3fn codes [rows, C] + per-row fp32 scale
+  static constexpr int GRAN = 8;
+  uint8_t* q;
+  float* qscale;
+  template <int NCH, bool FULL>
+  __device__ __forceinline__ void emit(const RowWords& y, int C, int lane, int row) const {
+    emit_row<NCH, FULL, true>(y, C, lane, row, nullptr, (int8_t*)q, qscale);
+  }
+};
+struct EmitMx {          // MXFP8: e4m3fn codes [rows, C] + E8M0 scales [rows, C / 32]
+  static constexpr int GRAN = MX_BLOCK;
+  uint8_t *q, *qs;
+  template <int NCH, bool FULL>
+  __device__ __forceinline__ void emit(const RowWords& y, int C, int lane, int row) const {
+    emit_row_mx<NCH, FULL>(y, C, lane, row, q, qs);
+  }
+};
+struct EmitMx6 {         // MXFP6: packed E2M3 codes [rows, 3C/4] + E8M0 scales [rows, C / 32]
+  static constexpr int GRAN = MX6_SUPER;
+  uint8_t *q, *qs;
+  template <int NCH, bool FULL>
+  __device__ __forceinline__ void emit(const RowWords& y, int C, int lane, int row) const {
+    emit_row_mx6<NCH, FULL>(y, C, lane, row, q, qs);
+  }
+};
+struct EmitMx4 {         // MXFP4: packed E2M1 codes [rows, C/2] + E8M0 scales [rows, C / 32]
+  static constexpr int GRAN = MX4_SUPER;
+  uint8_t *q, *qs;
+  template <int NCH, bool FULL>
+  __device__ __forceinline__ void emit(const RowWords& y, int C, int lane, int row) const {
+    emit_row_mx4<NCH, FULL>(y, C, lane, row, q, qs);
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // LN (no affine) + per-frame modulation.  Rounding points of the reference (bf16 tensors, causal_model.py:445):
 //   y = bf16(LN(x)); s1 = bf16(1 + bf16(mod_s + e_s)); out = bf16(bf16(y * s1) + bf16(mod_t + e_t))
 // PRE: `e` already holds bf16(mod + e) for every chunk (ll_modulation_table, once per forward for all layers): two vector
 // loads and three operations per element less; the values are the ones the unfused form computes, bit for bit.
-template <int NCH, bool FULL, bool PRE, bool F8 = false>
-__global__ __launch_bounds__(256) void ln_modulate_kernel(const bf16* __restrict__ x, bf16* __restrict__ out,
-                                                          const bf16* __restrict__ e, const bf16* __restrict__ mod,
-                                                          int nmod, int shift_idx, int scale_idx, int rows, int L,
-                                                          int C, int frame_len, int F, float eps,
-                                                          int8_t* __restrict__ q, float* __restrict__ qscale) {
+template <int NCH, bool FULL, bool PRE, class Emit>
+__global__ __launch_bounds__(256) void ln_modulate_kernel(const bf16* __restrict__ x, const bf16* __restrict__ e,
+                                                          const bf16* __restrict__ mod, int nmod, int shift_idx, int scale_idx,
+                                                          int rows, int L, int C, int frame_len, int F, float eps, Emit em) {
   int lane = threadIdx.x & 63;
   int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));      // one row per wave: the row decode runs on the scalar unit
   if (row >= rows) return;
@@ -189,17 +319,16 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const bf16* __restrict
       f32x2 s1 = rbf2(one + sc);
       o.w[i][j] = pack2(rbf2(y * s1) + t);
     }
-  emit_row<NCH, FULL, F8>(o, C, lane, row, out, q, qscale);
+  em.template emit<NCH, FULL>(o, C, lane, row);
 }
 
 // The same from an fp32 table (ll_modulation_table_f32): tab[b, f, scale_idx] = 1 + scale and tab[b, f, shift_idx] = shift, each already
 // rounded to bf16 where the reference rounds (s1 and t above, bit for bit) and widened to fp32 -- per pair of elements no unpacking
 // and no `1 +` / rounding of the scale: 10 vector instructions instead of 18 in a kernel bound by their count.
-template <int NCH, bool FULL, bool F8 = false>
-__global__ __launch_bounds__(256) void ln_modulate_tab_kernel(const bf16* __restrict__ x, bf16* __restrict__ out,
-                                                              const float* __restrict__ tab, int nmod, int shift_idx, int scale_idx,
-                                                              int rows, int L, int C, int frame_len, int F, float eps,
-                                                              int8_t* __restrict__ q, float* __restrict__ qscale) {
+template <int NCH, bool FULL, class Emit>
+__global__ __launch_bounds__(256) void ln_modulate_tab_kernel(const bf16* __restrict__ x, const float* __restrict__ tab, int nmod,
+                                                              int shift_idx, int scale_idx, int rows, int L, int C, int frame_len,
+                                                              int F, float eps, Emit em) {
   int lane = threadIdx.x & 63;
   int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
   if (row >= rows) return;
@@ -221,7 +350,7 @@ __global__ __launch_bounds__(256) void ln_modulate_tab_kernel(const bf16* __rest
       }
     }
   }
-  asm volatile("" ::: "memory");
+  asm volatile("" ::: "memory");           // every load of the row is in flight before the reductions (see ln_modulate_kernel)
   __builtin_amdgcn_sched_barrier(0);
   float rstd;
   layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
@@ -231,15 +360,13 @@ __global__ __launch_bounds__(256) void ln_modulate_tab_kernel(const bf16* __rest
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(rbf2(rbf2(r.p[i][j] * r2) * s1[i][j]) + t[i][j]);
-  emit_row<NCH, FULL, F8>(o, C, lane, row, out, q, qscale);
+  em.template emit<NCH, FULL>(o, C, lane, row);
 }
 
 // LN with affine (norm3): F.layer_norm computes (x-mean)*rstd*w + b in fp32 and rounds once.
-template <int NCH, bool FULL, bool F8 = false>
+template <int NCH, bool FULL, class Emit>
 __global__ __launch_bounds__(256) void layernorm_affine_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                               const bf16* __restrict__ bb, bf16* __restrict__ out,
-                                                               int rows, int C, float eps, int8_t* __restrict__ q,
-                                                               float* __restrict__ qscale) {
+                                                               const bf16* __restrict__ bb, int rows, int C, float eps, Emit em) {
   int lane = threadIdx.x & 63;
   int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));      // one row per wave: row arithmetic on the scalar unit
   if (row >= rows) return;
@@ -258,397 +385,7 @@ __global__ __launch_bounds__(256) void layernorm_affine_kernel(const bf16* __res
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
-  emit_row<NCH, FULL, F8>(o, C, lane, row, out, q, qscale);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// MXFP8 forms of the three producers above: the same bf16 row, emitted as e4m3fn codes [rows, C] + E8M0 scales [rows, C / 32]
-// (mx.h) instead of bf16.  A 32-column block is the chunk i of four consecutive lanes (4q .. 4q + 3), so its maximum is two
-// shuffles inside the wave; the values quantised are the packed bf16 words the bf16 form stores, so the bytes equal ll_quantize_mx
-// of the bf16 output.  C % 32 == 0: a block is wholly inside or wholly outside the row.
-template <int NCH, bool FULL>
-__device__ __forceinline__ void emit_row_mx(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
-                                            uint8_t* __restrict__ qs) {
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    int c = (lane + 64 * i) * 8;
-    bool in = in_row<FULL>(c, C);
-    f32x2 v[4];
-    float mx = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[j] = unpack2(y.w[i][j]);
-      mx = fmaxf(mx, fmaxf(fabsf(v[j].x), fabsf(v[j].y)));
-    }
-    if (!in) mx = 0.f;
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    int e = mx_scale_exp(mx);
-    if (in) {
-      uint32_t lo = mx_code4(v[0].x, v[0].y, v[1].x, v[1].y, e), hi = mx_code4(v[2].x, v[2].y, v[3].x, v[3].y, e);
-      *reinterpret_cast<uint2*>(q + (size_t)row * C + c) = make_uint2(lo, hi);
-      if ((lane & 3) == 0) qs[(size_t)row * (C / MX_BLOCK) + c / MX_BLOCK] = (uint8_t)(e + 127);
-    }
-  }
-}
-
-template <int NCH, bool FULL, bool PRE>
-__global__ __launch_bounds__(256) void ln_modulate_mx_kernel(const bf16* __restrict__ x, const bf16* __restrict__ e,
-                                                             const bf16* __restrict__ mod, int nmod, int shift_idx, int scale_idx,
-                                                             int rows, int L, int C, int frame_len, int F, float eps,
-                                                             uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  int b = row / L, f = (row % L) / frame_len;
-  const bf16* eb = e + ((size_t)(b * F + f) * nmod) * C;
-  RowWords es, et, ms, mt;
-  load_words<NCH, FULL>(eb + (size_t)scale_idx * C, C, lane, es);
-  load_words<NCH, FULL>(eb + (size_t)shift_idx * C, C, lane, et);
-  if (!PRE) {
-    load_words<NCH, FULL>(mod + (size_t)scale_idx * C, C, lane, ms);
-    load_words<NCH, FULL>(mod + (size_t)shift_idx * C, C, lane, mt);
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd), one = splat2(1.0f);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 y = rbf2(r.p[i][j] * r2);
-      f32x2 sc = PRE ? unpack2(es.w[i][j]) : rbf2(unpack2(ms.w[i][j]) + unpack2(es.w[i][j]));
-      f32x2 t = PRE ? unpack2(et.w[i][j]) : rbf2(unpack2(mt.w[i][j]) + unpack2(et.w[i][j]));
-      f32x2 s1 = rbf2(one + sc);
-      o.w[i][j] = pack2(rbf2(y * s1) + t);
-    }
-  emit_row_mx<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-template <int NCH, bool FULL>
-__global__ __launch_bounds__(256) void ln_modulate_tab_mx_kernel(const bf16* __restrict__ x, const float* __restrict__ tab, int nmod,
-                                                                 int shift_idx, int scale_idx, int rows, int L, int C, int frame_len,
-                                                                 int F, float eps, uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  int b = row / L, f = (row % L) / frame_len;
-  const float* tb = tab + ((size_t)(b * F + f) * nmod) * C;
-  f32x2 s1[NCH][4], t[NCH][4];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    int c = (lane + 64 * i) * 8;
-    if (in_row<FULL>(c, C)) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        f32x4 a = *reinterpret_cast<const f32x4*>(tb + (size_t)scale_idx * C + c + 4 * h);
-        f32x4 d = *reinterpret_cast<const f32x4*>(tb + (size_t)shift_idx * C + c + 4 * h);
-        s1[i][2 * h].x = a[0], s1[i][2 * h].y = a[1], s1[i][2 * h + 1].x = a[2], s1[i][2 * h + 1].y = a[3];
-        t[i][2 * h].x = d[0], t[i][2 * h].y = d[1], t[i][2 * h + 1].x = d[2], t[i][2 * h + 1].y = d[3];
-      }
-    }
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(rbf2(rbf2(r.p[i][j] * r2) * s1[i][j]) + t[i][j]);
-  emit_row_mx<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-template <int NCH, bool FULL>
-__global__ __launch_bounds__(256) void layernorm_affine_mx_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                                  const bf16* __restrict__ bb, int rows, int C, float eps,
-                                                                  uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  RowWords wv, bv;
-  load_words<NCH, FULL>(w, C, lane, wv);
-  load_words<NCH, FULL>(bb, C, lane, bv);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
-  emit_row_mx<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// MXFP6 forms of the same three producers: E2M3 codes packed per mx6.h [rows, 3C/4] + E8M0 scales [rows, C / 32], bit-identical to
-// ll_quantize_mx6 of the bf16 output.  A 16-k chunk of the packed row is lanes (2q, 2q + 1); C % 256 == 0.
-template <int NCH, bool FULL>
-__device__ __forceinline__ void emit_row_mx6(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
-                                             uint8_t* __restrict__ qs) {
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    int c = (lane + 64 * i) * 8;
-    bool in = in_row<FULL>(c, C);
-    float f[8];
-    float mx = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 v = unpack2(y.w[i][j]);
-      f[2 * j] = v.x, f[2 * j + 1] = v.y;
-      mx = fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y)));
-    }
-    if (!in) mx = 0.f;
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    int e = mx6_scale_exp(mx);
-    mx6_store_pair(mx6_pack8(f, e), q + (size_t)row * (C / 4 * 3) + mx6_chunk_off(in ? c & ~15 : 0), lane, in);
-    if (in && (lane & 3) == 0) qs[(size_t)row * (C / MX6_BLOCK) + c / MX6_BLOCK] = (uint8_t)(e + 127);
-  }
-}
-
-template <int NCH, bool FULL, bool PRE>
-__global__ __launch_bounds__(256) void ln_modulate_mx6_kernel(const bf16* __restrict__ x, const bf16* __restrict__ e,
-                                                              const bf16* __restrict__ mod, int nmod, int shift_idx, int scale_idx,
-                                                              int rows, int L, int C, int frame_len, int F, float eps,
-                                                              uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  int b = row / L, f = (row % L) / frame_len;
-  const bf16* eb = e + ((size_t)(b * F + f) * nmod) * C;
-  RowWords es, et, ms, mt;
-  load_words<NCH, FULL>(eb + (size_t)scale_idx * C, C, lane, es);
-  load_words<NCH, FULL>(eb + (size_t)shift_idx * C, C, lane, et);
-  if (!PRE) {
-    load_words<NCH, FULL>(mod + (size_t)scale_idx * C, C, lane, ms);
-    load_words<NCH, FULL>(mod + (size_t)shift_idx * C, C, lane, mt);
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd), one = splat2(1.0f);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 y = rbf2(r.p[i][j] * r2);
-      f32x2 sc = PRE ? unpack2(es.w[i][j]) : rbf2(unpack2(ms.w[i][j]) + unpack2(es.w[i][j]));
-      f32x2 t = PRE ? unpack2(et.w[i][j]) : rbf2(unpack2(mt.w[i][j]) + unpack2(et.w[i][j]));
-      f32x2 s1 = rbf2(one + sc);
-      o.w[i][j] = pack2(rbf2(y * s1) + t);
-    }
-  emit_row_mx6<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-template <int NCH, bool FULL>
-__global__ __launch_bounds__(256) void ln_modulate_tab_mx6_kernel(const bf16* __restrict__ x, const float* __restrict__ tab, int nmod,
-                                                                  int shift_idx, int scale_idx, int rows, int L, int C, int frame_len,
-                                                                  int F, float eps, uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  int b = row / L, f = (row % L) / frame_len;
-  const float* tb = tab + ((size_t)(b * F + f) * nmod) * C;
-  f32x2 s1[NCH][4], t[NCH][4];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    int c = (lane + 64 * i) * 8;
-    if (in_row<FULL>(c, C)) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        f32x4 a = *reinterpret_cast<const f32x4*>(tb + (size_t)scale_idx * C + c + 4 * h);
-        f32x4 d = *reinterpret_cast<const f32x4*>(tb + (size_t)shift_idx * C + c + 4 * h);
-        s1[i][2 * h].x = a[0], s1[i][2 * h].y = a[1], s1[i][2 * h + 1].x = a[2], s1[i][2 * h + 1].y = a[3];
-        t[i][2 * h].x = d[0], t[i][2 * h].y = d[1], t[i][2 * h + 1].x = d[2], t[i][2 * h + 1].y = d[3];
-      }
-    }
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(rbf2(rbf2(r.p[i][j] * r2) * s1[i][j]) + t[i][j]);
-  emit_row_mx6<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-template <int NCH, bool FULL>
-__global__ __launch_bounds__(256) void layernorm_affine_mx6_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                                   const bf16* __restrict__ bb, int rows, int C, float eps,
-                                                                   uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  RowWords wv, bv;
-  load_words<NCH, FULL>(w, C, lane, wv);
-  load_words<NCH, FULL>(bb, C, lane, bv);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
-  emit_row_mx6<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// MXFP4 forms of the same three producers: E2M1 codes packed per mx4.h [rows, C/2] + E8M0 scales [rows, C / 32], bit-identical to
-// ll_quantize_mx4 of the bf16 output.  A lane's 8 values are one dword of the packed row, a 32-k block is 4 consecutive lanes.
-template <int NCH, bool FULL>
-__device__ __forceinline__ void emit_row_mx4(const RowWords& y, int C, int lane, int row, uint8_t* __restrict__ q,
-                                             uint8_t* __restrict__ qs) {
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    int c = (lane + 64 * i) * 8;
-    bool in = in_row<FULL>(c, C);
-    float f[8];
-    float mx = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 v = unpack2(y.w[i][j]);
-      f[2 * j] = v.x, f[2 * j + 1] = v.y;
-      mx = fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y)));
-    }
-    if (!in) mx = 0.f;
-    mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-    int e = mx4_scale_exp(mx);
-    if (in) {
-      *reinterpret_cast<uint32_t*>(q + (size_t)row * (C / 2) + mx4_chunk_off(c)) = mx4_pack8(f, e);
-      if ((lane & 3) == 0) qs[(size_t)row * (C / MX4_BLOCK) + c / MX4_BLOCK] = (uint8_t)(e + 127);
-    }
-  }
-}
-
-template <int NCH, bool FULL, bool PRE>
-__global__ __launch_bounds__(256) void ln_modulate_mx4_kernel(const bf16* __restrict__ x, const bf16* __restrict__ e,
-                                                              const bf16* __restrict__ mod, int nmod, int shift_idx, int scale_idx,
-                                                              int rows, int L, int C, int frame_len, int F, float eps,
-                                                              uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  int b = row / L, f = (row % L) / frame_len;
-  const bf16* eb = e + ((size_t)(b * F + f) * nmod) * C;
-  RowWords es, et, ms, mt;
-  load_words<NCH, FULL>(eb + (size_t)scale_idx * C, C, lane, es);
-  load_words<NCH, FULL>(eb + (size_t)shift_idx * C, C, lane, et);
-  if (!PRE) {
-    load_words<NCH, FULL>(mod + (size_t)scale_idx * C, C, lane, ms);
-    load_words<NCH, FULL>(mod + (size_t)shift_idx * C, C, lane, mt);
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd), one = splat2(1.0f);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x2 y = rbf2(r.p[i][j] * r2);
-      f32x2 sc = PRE ? unpack2(es.w[i][j]) : rbf2(unpack2(ms.w[i][j]) + unpack2(es.w[i][j]));
-      f32x2 t = PRE ? unpack2(et.w[i][j]) : rbf2(unpack2(mt.w[i][j]) + unpack2(et.w[i][j]));
-      f32x2 s1 = rbf2(one + sc);
-      o.w[i][j] = pack2(rbf2(y * s1) + t);
-    }
-  emit_row_mx4<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-template <int NCH, bool FULL>
-__global__ __launch_bounds__(256) void ln_modulate_tab_mx4_kernel(const bf16* __restrict__ x, const float* __restrict__ tab, int nmod,
-                                                                  int shift_idx, int scale_idx, int rows, int L, int C, int frame_len,
-                                                                  int F, float eps, uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  int b = row / L, f = (row % L) / frame_len;
-  const float* tb = tab + ((size_t)(b * F + f) * nmod) * C;
-  f32x2 s1[NCH][4], t[NCH][4];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    int c = (lane + 64 * i) * 8;
-    if (in_row<FULL>(c, C)) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        f32x4 a = *reinterpret_cast<const f32x4*>(tb + (size_t)scale_idx * C + c + 4 * h);
-        f32x4 d = *reinterpret_cast<const f32x4*>(tb + (size_t)shift_idx * C + c + 4 * h);
-        s1[i][2 * h].x = a[0], s1[i][2 * h].y = a[1], s1[i][2 * h + 1].x = a[2], s1[i][2 * h + 1].y = a[3];
-        t[i][2 * h].x = d[0], t[i][2 * h].y = d[1], t[i][2 * h + 1].x = d[2], t[i][2 * h + 1].y = d[3];
-      }
-    }
-  }
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(rbf2(rbf2(r.p[i][j] * r2) * s1[i][j]) + t[i][j]);
-  emit_row_mx4<NCH, FULL>(o, C, lane, row, q, qs);
-}
-
-template <int NCH, bool FULL>
-__global__ __launch_bounds__(256) void layernorm_affine_mx4_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
-                                                                   const bf16* __restrict__ bb, int rows, int C, float eps,
-                                                                   uint8_t* __restrict__ q, uint8_t* __restrict__ qs) {
-  int lane = threadIdx.x & 63;
-  int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
-  if (row >= rows) return;
-  RowRegs r;
-  load_row<NCH, FULL>(x + (size_t)row * C, C, lane, r);
-  RowWords wv, bv;
-  load_words<NCH, FULL>(w, C, lane, wv);
-  load_words<NCH, FULL>(bb, C, lane, bv);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  float rstd;
-  layernorm_center<NCH, FULL>(r, C, lane, eps, rstd);
-  const f32x2 r2 = splat2(rstd);
-  RowWords o;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o.w[i][j] = pack2(r.p[i][j] * r2 * unpack2(wv.w[i][j]) + unpack2(bv.w[i][j]));
-  emit_row_mx4<NCH, FULL>(o, C, lane, row, q, qs);
+  em.template emit<NCH, FULL>(o, C, lane, row);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -965,36 +702,6 @@ __global__ __launch_bounds__(256) void modulation_table_f32_kernel(const bf16* _
     else { if (full_) CALL(4, true); else CALL(4, false); }                \
   } while (0)
 
-static inline bool row_ok(int C) { return C > 0 && C <= 2048 && (C % 8) == 0; }
-
-static int ln_modulate_launch(const ll_bf16* x, ll_bf16* out, int8_t* q, float* qscale, const ll_bf16* e,
-                              const ll_bf16* mod, int nmod, int shift_idx, int scale_idx, int B, int L, int C, int F,
-                              float eps, ll_stream stream, bool f8 = false) {
-  LL_REQUIRE(row_ok(C), "ll_ln_modulate: C=%d must be a multiple of 8 and <= 2048", C);
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL2(N, FL, F8)                                                                                                     \
-  do {                                                                                                                   \
-    if (mod)                                                                                                             \
-      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, false, F8>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out, \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qscale); \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, true, F8>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out,  \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qscale); \
-  } while (0)
-#define CALL(N, FL) CALL2(N, FL, false)
-#define CALL_F8(N, FL) CALL2(N, FL, true)
-  if (f8) DISPATCH_NCH(C, CALL_F8);
-  else DISPATCH_NCH(C, CALL);
-#undef CALL
-#undef CALL_F8
-#undef CALL2
-  return ll_check_launch("ll_ln_modulate");
-}
-
 extern "C" int ll_modulation_table(const ll_bf16* e, const ll_bf16* mods, ll_bf16* out, int num_layers, int BF, int nmod, int C,
                                    ll_stream stream) {
   LL_REQUIRE(C > 0 && C % 8 == 0 && nmod > 0 && num_layers >= 0 && BF >= 0, "ll_modulation_table: bad shape");
@@ -1004,25 +711,6 @@ extern "C" int ll_modulation_table(const ll_bf16* e, const ll_bf16* mods, ll_bf1
   hipLaunchKernelGGL(modulation_table_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)e, (const bf16*)mods, (bf16*)out, num_layers, BF, nmod * (C / 8));
   return ll_check_launch("ll_modulation_table");
-}
-
-extern "C" int ll_ln_modulate(const ll_bf16* x, ll_bf16* out, const ll_bf16* e, const ll_bf16* mod, int nmod,
-                              int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  return ln_modulate_launch(x, out, nullptr, nullptr, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream);
-}
-
-extern "C" int ll_ln_modulate_q8(const ll_bf16* x, int8_t* q, float* qscale, const ll_bf16* e, const ll_bf16* mod,
-                                 int nmod, int shift_idx, int scale_idx, int B, int L, int C, int F, float eps,
-                                 ll_stream stream) {
-  LL_REQUIRE(q && qscale, "ll_ln_modulate_q8: q and qscale are required");
-  return ln_modulate_launch(x, nullptr, q, qscale, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream);
-}
-
-extern "C" int ll_ln_modulate_f8(const ll_bf16* x, uint8_t* q, float* qscale, const ll_bf16* e, const ll_bf16* mod, int nmod,
-                                 int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  LL_REQUIRE(x != nullptr && e != nullptr, "ll_ln_modulate_f8: x and e are required");
-  LL_REQUIRE(q && qscale, "ll_ln_modulate_f8: codes and scales are required");
-  return ln_modulate_launch(x, nullptr, (int8_t*)q, qscale, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream, true);
 }
 
 extern "C" int ll_modulation_table_f32(const ll_bf16* e, const ll_bf16* mods, float* out, int num_layers, int BF, int nmod, int C,
@@ -1037,260 +725,127 @@ extern "C" int ll_modulation_table_f32(const ll_bf16* e, const ll_bf16* mods, fl
   return ll_check_launch("ll_modulation_table_f32");
 }
 
-extern "C" int ll_ln_modulate_tab(const ll_bf16* x, ll_bf16* out, int8_t* q, float* qscale, const float* tab, int nmod,
-                                  int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  LL_REQUIRE(row_ok(C), "ll_ln_modulate_tab: C=%d must be a multiple of 8 and <= 2048", C);
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab: bad mod index");
-  LL_REQUIRE((out != nullptr) != (q != nullptr), "ll_ln_modulate_tab: exactly one of out (bf16) and q (int8, with qscale) is required");
-  LL_REQUIRE(q == nullptr || qscale != nullptr, "ll_ln_modulate_tab: q needs qscale");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                      \
-  hipLaunchKernelGGL((ln_modulate_tab_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)out, tab, \
-                     nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qscale)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_tab");
-}
+// The three producers, launched for any emitter: fn is the entry point's own name (for ll_last_error), Emit::GRAN the multiple
+// its rows need.  The entry points below check the pointers they own and name the emitter.
+static inline bool row_ok(int C, int gran = 8) { return C > 0 && C <= 2048 && (C % gran) == 0; }
 
-extern "C" int ll_ln_modulate_tab_f8(const ll_bf16* x, uint8_t* q, float* qscale, const float* tab, int nmod, int shift_idx, int scale_idx,
-                                     int B, int L, int C, int F, float eps, ll_stream stream) {
-  LL_REQUIRE(x != nullptr && tab != nullptr, "ll_ln_modulate_tab_f8: x and tab are required");
-  LL_REQUIRE(q && qscale, "ll_ln_modulate_tab_f8: codes and scales are required");
-  LL_REQUIRE(row_ok(C), "ll_ln_modulate_tab_f8: C=%d must be a multiple of 8 and <= 2048", C);
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab_f8: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab_f8: bad mod index");
+template <class Emit>
+static int ln_modulate_launch(const char* fn, Emit em, const ll_bf16* x, const ll_bf16* e, const ll_bf16* mod, int nmod, int shift_idx,
+                              int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
+  LL_REQUIRE(row_ok(C, Emit::GRAN), "%s: C=%d must be a multiple of %d and <= 2048", fn, C, Emit::GRAN);
+  LL_REQUIRE(F > 0 && L % F == 0, "%s: L=%d not divisible by F=%d", fn, L, F);
+  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "%s: bad mod index", fn);
   int rows = B * L;
   if (rows == 0) return LL_OK;
   dim3 grid((rows + 3) / 4);
 #define CALL(N, FL)                                                                                                           \
-  hipLaunchKernelGGL((ln_modulate_tab_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, (bf16*)nullptr, \
-                     tab, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, (int8_t*)q, qscale)
+  do {                                                                                                                        \
+    if (mod)                                                                                                                  \
+      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, false, Emit>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,   \
+                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, em);        \
+    else                                                                                                                      \
+      hipLaunchKernelGGL((ln_modulate_kernel<N, FL, true, Emit>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,    \
+                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, em);        \
+  } while (0)
   DISPATCH_NCH(C, CALL);
 #undef CALL
-  return ll_check_launch("ll_ln_modulate_tab_f8");
+  return ll_check_launch(fn);
 }
 
-static int layernorm_affine_launch(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, ll_bf16* out, int8_t* q,
-                                   float* qscale, int rows, int C, float eps, ll_stream stream, bool f8 = false) {
-  LL_REQUIRE(row_ok(C), "ll_layernorm_affine: C=%d must be a multiple of 8 and <= 2048", C);
+template <class Emit>
+static int ln_modulate_tab_launch(const char* fn, Emit em, const ll_bf16* x, const float* tab, int nmod, int shift_idx, int scale_idx,
+                                  int B, int L, int C, int F, float eps, ll_stream stream) {
+  LL_REQUIRE(row_ok(C, Emit::GRAN), "%s: C=%d must be a multiple of %d and <= 2048", fn, C, Emit::GRAN);
+  LL_REQUIRE(F > 0 && L % F == 0, "%s: L=%d not divisible by F=%d", fn, L, F);
+  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "%s: bad mod index", fn);
+  int rows = B * L;
   if (rows == 0) return LL_OK;
   dim3 grid((rows + 3) / 4);
-#define CALL2(N, FL, F8)                                                                                         \
-  hipLaunchKernelGGL((layernorm_affine_kernel<N, FL, F8>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, \
-                     (const bf16*)w, (const bf16*)b, (bf16*)out, rows, C, eps, q, qscale)
-#define CALL(N, FL) CALL2(N, FL, false)
-#define CALL_F8(N, FL) CALL2(N, FL, true)
-  if (f8) DISPATCH_NCH(C, CALL_F8);
-  else DISPATCH_NCH(C, CALL);
+#define CALL(N, FL)                                                                                                          \
+  hipLaunchKernelGGL((ln_modulate_tab_kernel<N, FL, Emit>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, tab, nmod, \
+                     shift_idx, scale_idx, rows, L, C, L / F, F, eps, em)
+  DISPATCH_NCH(C, CALL);
 #undef CALL
-#undef CALL_F8
-#undef CALL2
-  return ll_check_launch("ll_layernorm_affine");
+  return ll_check_launch(fn);
+}
+
+template <class Emit>
+static int layernorm_affine_launch(const char* fn, Emit em, const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, int rows, int C,
+                                   float eps, ll_stream stream) {
+  LL_REQUIRE(row_ok(C, Emit::GRAN), "%s: C=%d must be a multiple of %d and <= 2048", fn, C, Emit::GRAN);
+  if (rows == 0) return LL_OK;
+  dim3 grid((rows + 3) / 4);
+#define CALL(N, FL)                                                                                                       \
+  hipLaunchKernelGGL((layernorm_affine_kernel<N, FL, Emit>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,     \
+                     (const bf16*)w, (const bf16*)b, rows, C, eps, em)
+  DISPATCH_NCH(C, CALL);
+#undef CALL
+  return ll_check_launch(fn);
+}
+
+// ---- bf16 / int8
+extern "C" int ll_ln_modulate(const ll_bf16* x, ll_bf16* out, const ll_bf16* e, const ll_bf16* mod, int nmod,
+                              int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
+  return ln_modulate_launch("ll_ln_modulate", EmitBf16Q8{(bf16*)out, nullptr, nullptr}, x, e, mod, nmod, shift_idx, scale_idx, B, L, C,
+                            F, eps, stream);
+}
+
+extern "C" int ll_ln_modulate_q8(const ll_bf16* x, int8_t* q, float* qscale, const ll_bf16* e, const ll_bf16* mod,
+                                 int nmod, int shift_idx, int scale_idx, int B, int L, int C, int F, float eps,
+                                 ll_stream stream) {
+  LL_REQUIRE(q && qscale, "ll_ln_modulate_q8: q and qscale are required");
+  return ln_modulate_launch("ll_ln_modulate_q8", EmitBf16Q8{nullptr, q, qscale}, x, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps,
+                            stream);
+}
+
+extern "C" int ll_ln_modulate_tab(const ll_bf16* x, ll_bf16* out, int8_t* q, float* qscale, const float* tab, int nmod,
+                                  int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
+  LL_REQUIRE((out != nullptr) != (q != nullptr), "ll_ln_modulate_tab: exactly one of out (bf16) and q (int8, with qscale) is required");
+  LL_REQUIRE(q == nullptr || qscale != nullptr, "ll_ln_modulate_tab: q needs qscale");
+  return ln_modulate_tab_launch("ll_ln_modulate_tab", EmitBf16Q8{(bf16*)out, q, qscale}, x, tab, nmod, shift_idx, scale_idx, B, L, C, F,
+                                eps, stream);
 }
 
 extern "C" int ll_layernorm_affine(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, ll_bf16* out, int rows, int C,
                                    float eps, ll_stream stream) {
-  return layernorm_affine_launch(x, w, b, out, nullptr, nullptr, rows, C, eps, stream);
+  return layernorm_affine_launch("ll_layernorm_affine", EmitBf16Q8{(bf16*)out, nullptr, nullptr}, x, w, b, rows, C, eps, stream);
 }
 
 extern "C" int ll_layernorm_affine_q8(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, int8_t* q, float* qscale,
                                       int rows, int C, float eps, ll_stream stream) {
   LL_REQUIRE(q && qscale, "ll_layernorm_affine_q8: q and qscale are required");
-  return layernorm_affine_launch(x, w, b, nullptr, q, qscale, rows, C, eps, stream);
+  return layernorm_affine_launch("ll_layernorm_affine_q8", EmitBf16Q8{nullptr, q, qscale}, x, w, b, rows, C, eps, stream);
 }
 
-extern "C" int ll_layernorm_affine_f8(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, float* qscale, int rows, int C,
-                                      float eps, ll_stream stream) {
-  LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "ll_layernorm_affine_f8: x, w and b are required");
-  LL_REQUIRE(q && qscale, "ll_layernorm_affine_f8: codes and scales are required");
-  return layernorm_affine_launch(x, w, b, nullptr, (int8_t*)q, qscale, rows, C, eps, stream, true);
-}
-
-// ---- MXFP8 producers (codes [rows, C] e4m3fn, scales [rows, C / 32] E8M0)
-static int mx_row_ok(const char* fn, int C, const void* q, const void* qs) {
-  LL_REQUIRE(C > 0 && C <= 2048 && C % MX_BLOCK == 0, "%s: C=%d must be a multiple of 32 and <= 2048", fn, C);
-  LL_REQUIRE(q != nullptr && qs != nullptr, "%s: codes and scales are required", fn);
-  return LL_OK;
-}
-
-extern "C" int ll_ln_modulate_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod,
-                                 int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  if (int rc = mx_row_ok("ll_ln_modulate_mx", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && e != nullptr, "ll_ln_modulate_mx: x and e are required");
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_mx: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_mx: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                          \
-  do {                                                                                                                   \
-    if (mod)                                                                                                             \
-      hipLaunchKernelGGL((ln_modulate_mx_kernel<N, FL, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs); \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((ln_modulate_mx_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,  \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs); \
-  } while (0)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_mx");
-}
-
-extern "C" int ll_ln_modulate_tab_mx(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx,
-                                     int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  if (int rc = mx_row_ok("ll_ln_modulate_tab_mx", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && tab != nullptr, "ll_ln_modulate_tab_mx: x and tab are required");
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab_mx: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab_mx: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                      \
-  hipLaunchKernelGGL((ln_modulate_tab_mx_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, tab, \
-                     nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_tab_mx");
-}
-
-extern "C" int ll_layernorm_affine_mx(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows,
-                                      int C, float eps, ll_stream stream) {
-  if (int rc = mx_row_ok("ll_layernorm_affine_mx", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "ll_layernorm_affine_mx: x, w and b are required");
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                 \
-  hipLaunchKernelGGL((layernorm_affine_mx_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,   \
-                     (const bf16*)w, (const bf16*)b, rows, C, eps, q, qs)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_layernorm_affine_mx");
-}
-
-// ---- MXFP6 producers (codes [rows, 3C/4] packed E2M3, scales [rows, C / 32] E8M0)
-static int mx6_row_ok(const char* fn, int C, const void* q, const void* qs) {
-  LL_REQUIRE(C > 0 && C <= 2048 && C % MX6_SUPER == 0, "%s: C=%d must be a multiple of 256 and <= 2048", fn, C);
-  LL_REQUIRE(q != nullptr && qs != nullptr, "%s: codes and scales are required", fn);
-  return LL_OK;
-}
-
-extern "C" int ll_ln_modulate_mx6(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod,
-                                  int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  if (int rc = mx6_row_ok("ll_ln_modulate_mx6", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && e != nullptr, "ll_ln_modulate_mx6: x and e are required");
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_mx6: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_mx6: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                           \
-  do {                                                                                                                    \
-    if (mod)                                                                                                              \
-      hipLaunchKernelGGL((ln_modulate_mx6_kernel<N, FL, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs);  \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((ln_modulate_mx6_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,  \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs);  \
-  } while (0)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_mx6");
-}
-
-extern "C" int ll_ln_modulate_tab_mx6(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx,
-                                      int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  if (int rc = mx6_row_ok("ll_ln_modulate_tab_mx6", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && tab != nullptr, "ll_ln_modulate_tab_mx6: x and tab are required");
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab_mx6: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab_mx6: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                       \
-  hipLaunchKernelGGL((ln_modulate_tab_mx6_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, tab, \
-                     nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_tab_mx6");
-}
-
-extern "C" int ll_layernorm_affine_mx6(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows,
-                                       int C, float eps, ll_stream stream) {
-  if (int rc = mx6_row_ok("ll_layernorm_affine_mx6", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "ll_layernorm_affine_mx6: x, w and b are required");
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                  \
-  hipLaunchKernelGGL((layernorm_affine_mx6_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,   \
-                     (const bf16*)w, (const bf16*)b, rows, C, eps, q, qs)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_layernorm_affine_mx6");
-}
-
-// ---- MXFP4 producers (codes [rows, C/2] packed E2M1, scales [rows, C / 32] E8M0)
-static int mx4_row_ok(const char* fn, int C, const void* q, const void* qs) {
-  LL_REQUIRE(C > 0 && C <= 2048 && C % MX4_SUPER == 0, "%s: C=%d must be a multiple of 256 and <= 2048", fn, C);
-  LL_REQUIRE(q != nullptr && qs != nullptr, "%s: codes and scales are required", fn);
-  return LL_OK;
-}
-
-extern "C" int ll_ln_modulate_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, const ll_bf16* e, const ll_bf16* mod, int nmod,
-                                  int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  if (int rc = mx4_row_ok("ll_ln_modulate_mx4", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && e != nullptr, "ll_ln_modulate_mx4: x and e are required");
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_mx4: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_mx4: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                           \
-  do {                                                                                                                    \
-    if (mod)                                                                                                              \
-      hipLaunchKernelGGL((ln_modulate_mx4_kernel<N, FL, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs);  \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((ln_modulate_mx4_kernel<N, FL, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,  \
-                         (const bf16*)e, (const bf16*)mod, nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs);  \
-  } while (0)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_mx4");
-}
-
-extern "C" int ll_ln_modulate_tab_mx4(const ll_bf16* x, uint8_t* q, uint8_t* qs, const float* tab, int nmod, int shift_idx,
-                                      int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {
-  if (int rc = mx4_row_ok("ll_ln_modulate_tab_mx4", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && tab != nullptr, "ll_ln_modulate_tab_mx4: x and tab are required");
-  LL_REQUIRE(F > 0 && L % F == 0, "ll_ln_modulate_tab_mx4: L=%d not divisible by F=%d", L, F);
-  LL_REQUIRE(shift_idx >= 0 && shift_idx < nmod && scale_idx >= 0 && scale_idx < nmod, "ll_ln_modulate_tab_mx4: bad mod index");
-  int rows = B * L;
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                       \
-  hipLaunchKernelGGL((ln_modulate_tab_mx4_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, tab, \
-                     nmod, shift_idx, scale_idx, rows, L, C, L / F, F, eps, q, qs)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_ln_modulate_tab_mx4");
-}
-
-extern "C" int ll_layernorm_affine_mx4(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, uint8_t* qs, int rows,
-                                       int C, float eps, ll_stream stream) {
-  if (int rc = mx4_row_ok("ll_layernorm_affine_mx4", C, q, qs)) return rc;
-  LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "ll_layernorm_affine_mx4: x, w and b are required");
-  if (rows == 0) return LL_OK;
-  dim3 grid((rows + 3) / 4);
-#define CALL(N, FL)                                                                                                  \
-  hipLaunchKernelGGL((layernorm_affine_mx4_kernel<N, FL>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x,   \
-                     (const bf16*)w, (const bf16*)b, rows, C, eps, q, qs)
-  DISPATCH_NCH(C, CALL);
-#undef CALL
-  return ll_check_launch("ll_layernorm_affine_mx4");
-}
+// ---- FP8 rowwise, MXFP8, MXFP6, MXFP4: the same three entry points per format, each with its emitter.  q2 is the second output:
+// per-row fp32 scales for f8, E8M0 block scales for the MX formats.
+#define LL_QUANT_PRODUCERS(SFX, EMIT, Q2T)                                                                                             \
+  extern "C" int ll_ln_modulate_##SFX(const ll_bf16* x, uint8_t* q, Q2T* q2, const ll_bf16* e, const ll_bf16* mod, int nmod,           \
+                                      int shift_idx, int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {         \
+    const char* fn = "ll_ln_modulate_" #SFX;                                                                                           \
+    LL_REQUIRE(x != nullptr && e != nullptr, "%s: x and e are required", fn);                                                          \
+    LL_REQUIRE(q != nullptr && q2 != nullptr, "%s: codes and scales are required", fn);                                                \
+    return ln_modulate_launch(fn, EMIT{q, q2}, x, e, mod, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream);                        \
+  }                                                                                                                                    \
+  extern "C" int ll_ln_modulate_tab_##SFX(const ll_bf16* x, uint8_t* q, Q2T* q2, const float* tab, int nmod, int shift_idx,            \
+                                          int scale_idx, int B, int L, int C, int F, float eps, ll_stream stream) {                    \
+    const char* fn = "ll_ln_modulate_tab_" #SFX;                                                                                       \
+    LL_REQUIRE(x != nullptr && tab != nullptr, "%s: x and tab are required", fn);                                                      \
+    LL_REQUIRE(q != nullptr && q2 != nullptr, "%s: codes and scales are required", fn);                                                \
+    return ln_modulate_tab_launch(fn, EMIT{q, q2}, x, tab, nmod, shift_idx, scale_idx, B, L, C, F, eps, stream);                       \
+  }                                                                                                                                    \
+  extern "C" int ll_layernorm_affine_##SFX(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b, uint8_t* q, Q2T* q2, int rows, int C, \
+                                           float eps, ll_stream stream) {                                                              \
+    const char* fn = "ll_layernorm_affine_" #SFX;                                                                                      \
+    LL_REQUIRE(x != nullptr && w != nullptr && b != nullptr, "%s: x, w and b are required", fn);                                       \
+    LL_REQUIRE(q != nullptr && q2 != nullptr, "%s: codes and scales are required", fn);                                                \
+    return layernorm_affine_launch(fn, EMIT{q, q2}, x, w, b, rows, C, eps, stream);                                                    \
+  }
+LL_QUANT_PRODUCERS(f8, EmitF8, float)
+LL_QUANT_PRODUCERS(mx, EmitMx, uint8_t)
+LL_QUANT_PRODUCERS(mx6, EmitMx6, uint8_t)
+LL_QUANT_PRODUCERS(mx4, EmitMx4, uint8_t)
+#undef LL_QUANT_PRODUCERS
 
 extern "C" int ll_rmsnorm(const ll_bf16* x, const ll_bf16* w, ll_bf16* out, int rows, int C, int ldx, int ldo,
                           float eps, ll_stream stream) {

@@ -770,16 +770,6 @@ extern "C" int ll_gemm_w8a8(const int8_t* xq, const float* sx, const int8_t* wq,
 // LL_EPI_BIAS, N = 3 C, plus the cache destination.  The q and k thirds land in `out` [M, ldo] as usual (they still need the
 // full-row RMSNorm + RoPE of ll_qk_norm_rope_kv_store, called with cache_v = NULL afterwards); the v third of `out` is left
 // unwritten.  M = B * L tokens.
-static int check_v_insert(const char* fn, int M, int N, int B, int L, int S, int write_start, int roped_offset, int write_len,
-                          const void* cache_v) {
-  LL_REQUIRE(cache_v != nullptr, "%s: cache_v is required", fn);
-  LL_REQUIRE(N % 3 == 0 && (N / 3) % 8 == 0, "%s: N=%d must be 3 C with C a multiple of 8", fn, N);
-  LL_REQUIRE(B > 0 && L > 0 && M == B * L, "%s: M=%d is not B=%d x L=%d", fn, M, B, L);
-  LL_REQUIRE(write_len >= 0 && roped_offset >= 0 && (write_len == 0 || roped_offset + write_len <= L), "%s: write window outside the new tokens", fn);
-  LL_REQUIRE(write_len == 0 || (write_start >= 0 && write_start + write_len <= S), "%s: write [%d,+%d) outside cache of %d slots", fn, write_start, write_len, S);
-  return LL_OK;
-}
-
 extern "C" int ll_gemm_bf16_qkv(const ll_bf16* x, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, int M, int N, int K, int ldx,
                                 int ldo, ll_bf16* cache_v, int B, int L, int S, int write_start, int roped_offset, int write_len,
                                 ll_stream stream) {
@@ -791,8 +781,7 @@ extern "C" int ll_gemm_bf16_qkv(const ll_bf16* x, const ll_bf16* w, const ll_bf1
   if (rc) return rc;
   if (M == 0) return LL_OK;
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
-  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+  set_v_insert(ea, cache_v, N, L, S, write_start, roped_offset, write_len);
   if (int lrc = launch_gemm<GQ_BF16>(x, w, (bf16*)out, M, N, K, (size_t)ldx * 2, (size_t)K * 2, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_bf16_qkv");
 }
@@ -808,8 +797,7 @@ extern "C" int ll_gemm_w8a8_qkv(const int8_t* xq, const float* sx, const int8_t*
   if (rc) return rc;
   if (M == 0) return LL_OK;
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, sx, sw, 0, 0, 0, 0, 0};
-  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
-  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+  set_v_insert(ea, cache_v, N, L, S, write_start, roped_offset, write_len);
   if (int lrc = launch_gemm<GQ_I8>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_w8a8_qkv");
 }
@@ -863,8 +851,7 @@ extern "C" int ll_gemm_f8_qkv(const uint8_t* xq, const float* sx, const uint8_t*
   if (rc) return rc;
   if (M == 0) return LL_OK;
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, sx, sw, 0, 0, 0, 0, 0};
-  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
-  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+  set_v_insert(ea, cache_v, N, L, S, write_start, roped_offset, write_len);
   if (int lrc = launch_gemm<GQ_F8>(xq, wq, (bf16*)out, M, N, K, (size_t)K, (size_t)K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_f8_qkv");
 }

@@ -34,6 +34,22 @@ __device__ __forceinline__ bf16* epi_dest(const EpiArgs& ea, bf16* __restrict__ 
   return ea.v_out + ((size_t)bb * ea.v_S + ea.v_write_start + wi) * (size_t)ea.v_C + (n - ea.v_col0);
 }
 
+// Host side of the V redirect, shared by every ll_gemm_*_qkv entry point: the checks of the insert window, and the fill of EpiArgs.
+static inline int check_v_insert(const char* fn, int M, int N, int B, int L, int S, int write_start, int roped_offset, int write_len,
+                          const void* cache_v) {
+  LL_REQUIRE(cache_v != nullptr, "%s: cache_v is required", fn);
+  LL_REQUIRE(N % 3 == 0 && (N / 3) % 8 == 0, "%s: N=%d must be 3 C with C a multiple of 8", fn, N);
+  LL_REQUIRE(B > 0 && L > 0 && M == B * L, "%s: M=%d is not B=%d x L=%d", fn, M, B, L);
+  LL_REQUIRE(write_len >= 0 && roped_offset >= 0 && (write_len == 0 || roped_offset + write_len <= L), "%s: write window outside the new tokens", fn);
+  LL_REQUIRE(write_len == 0 || (write_start >= 0 && write_start + write_len <= S), "%s: write [%d,+%d) outside cache of %d slots", fn, write_start, write_len, S);
+  return LL_OK;
+}
+
+static inline void set_v_insert(EpiArgs& ea, ll_bf16* cache_v, int N, int L, int S, int write_start, int roped_offset, int write_len) {
+  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
+  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+}
+
 template <int Q>
 struct Ty;
 template <>

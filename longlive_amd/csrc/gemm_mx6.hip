@@ -242,16 +242,9 @@ extern "C" int ll_gemm_mx6_qkv(const uint8_t* xq, const uint8_t* sx, const uint8
   int rc = mx6_check("ll_gemm_mx6_qkv", xq, sx, wq, sw, M, N, K, ldo, LL_EPI_BIAS, bias, nullptr, nullptr, 0, 0, 0, 0);
   if (rc) return rc;
   LL_REQUIRE(out != nullptr, "ll_gemm_mx6_qkv: out is required");
-  LL_REQUIRE(cache_v != nullptr, "ll_gemm_mx6_qkv: cache_v is required");
-  LL_REQUIRE(N % 3 == 0 && (N / 3) % 8 == 0, "ll_gemm_mx6_qkv: N=%d must be 3 C with C a multiple of 8", N);
-  LL_REQUIRE(B > 0 && L > 0 && M == B * L, "ll_gemm_mx6_qkv: M=%d is not B=%d x L=%d", M, B, L);
-  LL_REQUIRE(write_len >= 0 && roped_offset >= 0 && (write_len == 0 || roped_offset + write_len <= L),
-             "ll_gemm_mx6_qkv: write window outside the new tokens");
-  LL_REQUIRE(write_len == 0 || (write_start >= 0 && write_start + write_len <= S),
-             "ll_gemm_mx6_qkv: write [%d,+%d) outside cache of %d slots", write_start, write_len, S);
+  if (int vrc = check_v_insert("ll_gemm_mx6_qkv", M, N, B, L, S, write_start, roped_offset, write_len, cache_v)) return vrc;
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-  ea.v_out = (bf16*)cache_v; ea.v_col0 = 2 * (N / 3); ea.v_C = N / 3; ea.v_L = L; ea.v_S = S;
-  ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
+  set_v_insert(ea, cache_v, N, L, S, write_start, roped_offset, write_len);
   if (int lrc = mx6_launch(xq, sx, wq, sw, (bf16*)out, nullptr, nullptr, M, N, K, ldo, LL_EPI_BIAS, ea, (hipStream_t)stream)) return lrc;
   return ll_check_launch("ll_gemm_mx6_qkv");
 }

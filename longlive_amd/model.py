@@ -10,7 +10,7 @@ child is ever called.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -71,6 +71,51 @@ class _Conv(nn.Module):
         self.weight = nn.Parameter(torch.zeros(cfg.dim, cfg.in_dim, *cfg.patch_size, device=device, dtype=dtype),
                                    requires_grad=False)
         self.bias = nn.Parameter(torch.zeros(cfg.dim, device=device, dtype=dtype), requires_grad=False)
+
+
+class _QuantMode(NamedTuple):
+    """What one mode of the block linears launches.  Every entry is looked up on `ops` when it is called."""
+    quantize_w: Optional[Callable]     # weight [N, K] -> (codes, scales); None: bf16 weights as they are
+    quantize_x: Optional[Callable]     # an activation no fused producer emitted
+    ln_modulate: Callable              # the three producers, emitting what the GEMMs read
+    ln_modulate_tab: Callable
+    layernorm_affine: Callable
+    gemm: Callable                     # (x, w, bias, epilogue, **kw), x and w as the quantisers / producers return them
+    gemm_qkv: Callable                 # (x, w, bias, cache_v, write_start, roped_offset, write_len, B, L)
+    mx_out: bool                       # FFN1's GELU epilogue writes the codes + scales FFN2 reads, never the bf16 hidden
+    granule: int                       # dim and ffn_dim must be multiples of it
+
+
+def _op(name: str) -> Callable:
+    return lambda *a, **kw: getattr(ops, name)(*a, **kw)
+
+
+def _quant_mode(wq: str, xq: str, act: str, gemm: str, mx_out: bool, granule: int) -> _QuantMode:
+    """The regular naming: weights by ops.<wq>, activations by ops.<xq> or the ops.*_<act> producers, ops.gemm_<gemm>[_qkv_v_insert]."""
+    return _QuantMode(_op(wq), _op(xq), _op("ln_modulate_" + act), _op("ln_modulate_tab_" + act), _op("layernorm_affine_" + act),
+                      _op("gemm_" + gemm), _op(f"gemm_{gemm}_qkv_v_insert"), mx_out, granule)
+
+
+def _rowwise(gemm: str) -> Callable:       # the per-row-scale GEMMs take codes and scales as separate arguments
+    return lambda x, w, *a, **kw: getattr(ops, gemm)(*x, *w, *a, **kw)
+
+
+# None: bf16.  "int8": W8A8 (per-token activation scales, per-output-channel weight scales, int32 accumulation).  "mxfp8": e4m3 codes
+# with per-32 E8M0 block scales on the scaled MFMA.  "fp8_rowwise": int8's scales with e4m3 codes.  "mxfp6": mxfp8's block scales with
+# E2M3 codes packed 6 bits each.  "mxfp4_a6": mxfp6's activations with E2M1 weights packed 4 bits each (W4A6).  "mxfp4_a4": E2M1
+# weights and activations.  The packed formats need whole 256-k super-blocks.
+_QUANT_MODES = {
+    None: _QuantMode(None, None, _op("ln_modulate"), _op("ln_modulate_tab"), _op("layernorm_affine"), _op("gemm"),
+                     lambda x, w, b, cache_v, ws, ro, wl, B, L: ops.gemm_qkv_v_insert(x, w, b, cache_v, ws, ro, wl), False, 1),
+    "int8": _quant_mode("quantize_rows", "quantize_rows", "q8", "w8a8", False, 128)._replace(
+        ln_modulate_tab=lambda *a: ops.ln_modulate_tab(*a, q8=True), gemm=_rowwise("gemm_w8a8"),
+        gemm_qkv=lambda x, w, b, cache_v, ws, ro, wl, B, L: ops.gemm_qkv_v_insert(None, w, b, cache_v, ws, ro, wl, xq=x)),
+    "mxfp8": _quant_mode("quantize_mx", "quantize_mx", "mx", "mx", True, 128),
+    "fp8_rowwise": _quant_mode("quantize_rows_f8", "quantize_rows_f8", "f8", "f8", False, 128)._replace(gemm=_rowwise("gemm_f8")),
+    "mxfp6": _quant_mode("quantize_mx6", "quantize_mx6", "mx6", "mx6", True, 256),
+    "mxfp4_a6": _quant_mode("quantize_mx4", "quantize_mx6", "mx6", "mx4w6", True, 256),
+    "mxfp4_a4": _quant_mode("quantize_mx4", "quantize_mx4", "mx4", "mx4", True, 256),
+}
 
 
 _MX_SHADOW = "_ll_mx"      # a layer's cache dict in MX attention mode: the block-scaled shadow of k / v (ops.kv_shadow_mx_alloc)
@@ -204,7 +249,7 @@ class CausalWanModelHIP(nn.Module):
         for blk in self.blocks:
             sa = blk.self_attn
             ts = [sa.q.weight, sa.k.weight, sa.v.weight, sa.q.bias, sa.k.bias, sa.v.bias, blk.modulation]
-            if self.quant in ("int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4"):
+            if self.quant is not None:
                 ts += [sa.o.weight, blk.cross_attn.q.weight, blk.cross_attn.o.weight, blk.ffn[0].weight, blk.ffn[2].weight]
             key.extend((t.data_ptr(), t._version) for t in ts)
         return tuple(key)
@@ -222,9 +267,8 @@ class CausalWanModelHIP(nn.Module):
                 bqkv=torch.cat([sa.q.bias, sa.k.bias, sa.v.bias], 0).contiguous(),
                 mod=blk.modulation.detach().reshape(6, -1).contiguous(),
             )
-            if self.quant is not None:
-                quantize = {"int8": ops.quantize_rows, "mxfp8": ops.quantize_mx, "fp8_rowwise": ops.quantize_rows_f8,
-                            "mxfp6": ops.quantize_mx6, "mxfp4_a6": ops.quantize_mx4, "mxfp4_a4": ops.quantize_mx4}[self.quant]
+            quantize = _QUANT_MODES[self.quant].quantize_w
+            if quantize is not None:
                 for name, w in (("qkv", d["wqkv"]), ("o", sa.o.weight), ("cq", ca.q.weight), ("co", ca.o.weight),
                                 ("f1", blk.ffn[0].weight), ("f2", blk.ffn[2].weight)):
                     d["q_" + name], d["s_" + name] = quantize(w.detach().contiguous())
@@ -235,14 +279,14 @@ class CausalWanModelHIP(nn.Module):
         return P
 
     def set_quant(self, mode: Optional[str]):
-        """None (bf16), "int8" (W8A8 block linears), "mxfp8" (MXFP8 block linears), "fp8_rowwise" (e4m3 codes with per-token /
-        per-output-channel scales), "mxfp6" (MXFP6 E2M3 block linears), "mxfp4_a6" (MXFP4 E2M1 weights over MXFP6 activations) or
-        "mxfp4_a4" (MXFP4 E2M1 weights and activations).  Weights are (re)quantised lazily at the next forward."""
-        if mode not in (None, "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxfp4_a4"):
+        """A key of _QUANT_MODES: None (bf16), "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6" or "mxfp4_a4".  Weights are
+        (re)quantised lazily at the next forward."""
+        if mode not in _QUANT_MODES:
             raise ValueError(f"unknown quantisation mode {mode!r}")
-        if mode is not None and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
+        granule = _QUANT_MODES[mode].granule
+        if granule >= 128 and (self.cfg.dim % 128 or self.cfg.ffn_dim % 128):
             raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 128")
-        if mode in ("mxfp6", "mxfp4_a6", "mxfp4_a4") and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
+        if granule == 256 and (self.cfg.dim % 256 or self.cfg.ffn_dim % 256):
             raise ValueError(f"{mode} linears need dim and ffn_dim to be multiples of 256 (packed 256-k super-blocks)")
         self.quant = mode
         self._packed = None
@@ -271,30 +315,14 @@ class CausalWanModelHIP(nn.Module):
         return sh, sh["key"] != mx_shadow_key(k, kvc["v"])
 
     def _lin(self, x, pk, key, w, b, epilogue=0, **kw):
-        """One block linear: bf16 MFMA GEMM, or W8A8 GEMM in int8 mode (same fused epilogues).  In int8 mode `x` is either
-        a bf16 tensor (quantised here, per token) or an already quantised (int8, scale) pair from a fused producer; in mxfp8 mode
-        likewise a bf16 tensor or an (e4m3 codes, block scales) pair, and in fp8_rowwise mode an (e4m3 codes, row scale) pair; mxfp6 and
-        mxfp4_a6 take a bf16 tensor or an MXFP6 (packed E2M3 codes, block scales) pair, and mxfp4_a4 a bf16 tensor or an MXFP4 (packed
-        E2M1 codes, block scales) pair."""
-        if self.quant == "mxfp4_a4":
-            xm = x if isinstance(x, tuple) else ops.quantize_mx4(x)
-            return ops.gemm_mx4(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
-        if self.quant == "mxfp4_a6":
-            xm = x if isinstance(x, tuple) else ops.quantize_mx6(x)
-            return ops.gemm_mx4w6(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
-        if self.quant == "mxfp6":
-            xm = x if isinstance(x, tuple) else ops.quantize_mx6(x)
-            return ops.gemm_mx6(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
-        if self.quant == "fp8_rowwise":
-            xq, sx = x if isinstance(x, tuple) else ops.quantize_rows_f8(x)
-            return ops.gemm_f8(xq, sx, pk["q_" + key], pk["s_" + key], b, epilogue, tag="gemm_" + key, **kw)
-        if self.quant == "mxfp8":
-            xm = x if isinstance(x, tuple) else ops.quantize_mx(x)
-            return ops.gemm_mx(xm, (pk["q_" + key], pk["s_" + key]), b, epilogue, tag="gemm_" + key, **kw)
-        if self.quant == "int8":
-            xq, sx = x if isinstance(x, tuple) else ops.quantize_rows(x)
-            return ops.gemm_w8a8(xq, sx, pk["q_" + key], pk["s_" + key], b, epilogue, tag="gemm_" + key, **kw)
-        return ops.gemm(x, w, b, epilogue, tag="gemm_" + key, **kw)
+        """One block linear in the current mode (same fused epilogues in every mode).  `x` is a bf16 tensor, quantised here per the
+        mode, or the (codes, scales) pair a fused producer of the mode already emitted."""
+        m = _QUANT_MODES[self.quant]
+        if m.quantize_w is not None:
+            w = (pk["q_" + key], pk["s_" + key])
+            if not isinstance(x, tuple):
+                x = m.quantize_x(x)
+        return m.gemm(x, w, b, epilogue, tag="gemm_" + key, **kw)
 
     def _rope_tables(self, hp: int, wp: int, device):
         """fp32 (cos, sin) tables from the reference's fp64 angles (model.py:29-36; causal_model.py:622-629):
@@ -387,11 +415,7 @@ class CausalWanModelHIP(nn.Module):
         mod = None if premod else pk["mod"]
         sa, ca = blk.self_attn, blk.cross_attn
         # --- self attention (causal_model.py:444-456) ---
-        q8 = self.quant == "int8"
-        mx = self.quant == "mxfp8"
-        f8 = self.quant == "fp8_rowwise"
-        m6 = self.quant in ("mxfp6", "mxfp4_a6")          # MXFP6 activations (E2M3 or E2M1 weights)
-        m4 = self.quant == "mxfp4_a4"                     # MXFP4 activations
+        m = _QUANT_MODES[self.quant]
         G, E = _kv_state(kvc)
         S = kvc["k"].shape[1]
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
@@ -403,38 +427,10 @@ class CausalWanModelHIP(nn.Module):
             kvc.pop(_MX_SHADOW, None)      # bf16 writes from here on are not mirrored: a later MX forward starts from a new shadow
         if plan.roll is not None:          # before the projection: its epilogue writes V into the rolled window
             ops.kv_roll(kvc["k"], kvc["v"], *plan.roll)
-        if mx:
-            h1 = ops.ln_modulate_tab_mx(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 0, 1, F, c.eps)
-        elif m6:
-            h1 = ops.ln_modulate_tab_mx6(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx6(xs, e0, mod, 0, 1, F, c.eps)
-        elif m4:
-            h1 = ops.ln_modulate_tab_mx4(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_mx4(xs, e0, mod, 0, 1, F, c.eps)
-        elif f8:
-            h1 = ops.ln_modulate_tab_f8(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else ops.ln_modulate_f8(xs, e0, mod, 0, 1, F, c.eps)
-        elif tab32 is not None:
-            h1 = ops.ln_modulate_tab(xs, tab32, 0, 1, F, c.eps, q8=q8)
-        else:
-            h1 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 0, 1, F, c.eps)
+        h1 = m.ln_modulate_tab(xs, tab32, 0, 1, F, c.eps) if tab32 is not None else m.ln_modulate(xs, e0, mod, 0, 1, F, c.eps)
         if self.fuse_v_insert:             # V third of the projection goes straight into its cache slots (GEMM epilogue)
-            if mx:
-                qkv = ops.gemm_mx_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
-                                               plan.roped_offset, plan.write_len, B, L)
-            elif m6:
-                qkv_m6 = ops.gemm_mx4w6_qkv_v_insert if self.quant == "mxfp4_a6" else ops.gemm_mx6_qkv_v_insert
-                qkv = qkv_m6(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start, plan.roped_offset, plan.write_len,
-                             B, L)
-            elif m4:
-                qkv = ops.gemm_mx4_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
-                                                plan.roped_offset, plan.write_len, B, L)
-            elif f8:
-                qkv = ops.gemm_f8_qkv_v_insert(h1, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
-                                               plan.roped_offset, plan.write_len, B, L)
-            elif q8:
-                qkv = ops.gemm_qkv_v_insert(None, (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"], plan.write_start,
-                                            plan.roped_offset, plan.write_len, xq=h1)
-            else:
-                qkv = ops.gemm_qkv_v_insert(h1, pk["wqkv"], pk["bqkv"], kvc["v"], plan.write_start, plan.roped_offset,
-                                            plan.write_len)
+            qkv = m.gemm_qkv(h1, pk["wqkv"] if m.quantize_w is None else (pk["q_qkv"], pk["s_qkv"]), pk["bqkv"], kvc["v"],
+                             plan.write_start, plan.roped_offset, plan.write_len, B, L)
             v_dst = None
         else:
             qkv = self._lin(h1, pk, "qkv", pk["wqkv"], pk["bqkv"])
@@ -461,8 +457,7 @@ class CausalWanModelHIP(nn.Module):
         self._lin(att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=2, rows_per_batch=L, frame_len=fs)
         # --- cross attention (causal_model.py:460; model.py:159-194) ---
-        xn = (ops.layernorm_affine_mx if mx else ops.layernorm_affine_mx6 if m6 else ops.layernorm_affine_mx4 if m4 else ops.layernorm_affine_f8 if f8 else ops.layernorm_affine_q8 if q8 else
-              ops.layernorm_affine)(xs, blk.norm3.weight, blk.norm3.bias, c.eps)
+        xn = m.layernorm_affine(xs, blk.norm3.weight, blk.norm3.bias, c.eps)
         fuse_qn = (self.fuse_cross_qnorm and self.quant is None and ops.gemm_ssq_planes(B * L, C, C) == Hh and ops.flash_attn_qnorm_ok(Hh, c.text_len))
         if fuse_qn:
             qraw, ssq = ops.gemm_ssq(xn, ca.q.weight, ca.q.bias, tag="gemm_cq_ssq")
@@ -482,21 +477,9 @@ class CausalWanModelHIP(nn.Module):
             atc = ops.flash_attn(qc.view(B, L, Hh, D), cac["k"], cac["v"], [(0, c.text_len)], tag="flash_attn_cross")
         self._lin(atc.view(B, L, C), pk, "co", ca.o.weight, ca.o.bias, ops.EPI_BIAS_RES, out=xs, res=xs)
         # --- FFN (causal_model.py:462-468) ---
-        if mx:
-            h2 = ops.ln_modulate_tab_mx(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx(xs, e0, mod, 3, 4, F, c.eps)
-        elif m6:
-            h2 = ops.ln_modulate_tab_mx6(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx6(xs, e0, mod, 3, 4, F, c.eps)
-        elif m4:
-            h2 = ops.ln_modulate_tab_mx4(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_mx4(xs, e0, mod, 3, 4, F, c.eps)
-        elif f8:
-            h2 = ops.ln_modulate_tab_f8(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else ops.ln_modulate_f8(xs, e0, mod, 3, 4, F, c.eps)
-        elif tab32 is not None:
-            h2 = ops.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps, q8=q8)
-        else:
-            h2 = (ops.ln_modulate_q8 if q8 else ops.ln_modulate)(xs, e0, mod, 3, 4, F, c.eps)
-        # (mxfp8 / mxfp6 / mxfp4_a6 / mxfp4_a4: the GELU epilogue writes the MX codes + scales FFN2 reads, never the bf16 hidden)
+        h2 = m.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else m.ln_modulate(xs, e0, mod, 3, 4, F, c.eps)
         ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU,
-                       **(dict(mx_out=True) if mx or m6 or m4 else {}))
+                       **(dict(mx_out=True) if m.mx_out else {}))
         self._lin(ff, pk, "f2", blk.ffn[2].weight, blk.ffn[2].bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=5, rows_per_batch=L, frame_len=fs)
         return plan

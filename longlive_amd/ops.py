@@ -4,7 +4,9 @@ a kernel that faults can take the whole 8-GPU host down.
 """
 from __future__ import annotations
 
+import functools
 import math
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
 import torch
@@ -116,25 +118,6 @@ def ln_modulate(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps:
     return out
 
 
-def ln_modulate_q8(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate emitting (int8 [B,L,C], float32 scale [B*L]) for a following W8A8 GEMM."""
-    _chk(x, "x"); _chk(e, "e")
-    B, L, Cc = x.shape
-    nmod = e.shape[-2]
-    assert e.shape == (B, num_frames, nmod, Cc)
-    if mod is not None:
-        _chk(mod, "mod")
-        assert mod.numel() == nmod * Cc
-    q = torch.empty(x.shape, dtype=torch.int8, device=x.device)
-    sc = torch.empty(B * L, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_q8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), e.data_ptr(), _ptr(mod), nmod,
-                                     shift_idx, scale_idx, B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_q8")
-    _t1(tag, t0, 3.0 * x.numel())                    # read bf16, write int8
-    return q, sc
-
-
 def modulation_table_f32(e, mods, one_plus_mask: int):
     """The fp32 form for ln_modulate_tab: [NL,B,F,nmod,C] float32 = float(bf16(mods[l] + e)), chunks in one_plus_mask
     float(bf16(1 + bf16(mods[l] + e))) -- the `1 + e[1]` of causal_model.py:445,463 once per (layer, frame)."""
@@ -183,20 +166,6 @@ def modulation_table(e, mods):
     _lib.check(lib.ll_modulation_table(e.data_ptr(), mods.data_ptr(), out.data_ptr(), NL, B * F, nmod, Cc, _stream()),
                "ll_modulation_table")
     return out
-
-
-def layernorm_affine_q8(x, w, b, eps: float):
-    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
-    Cc = x.shape[-1]
-    rows = x.numel() // Cc
-    q = torch.empty(x.shape, dtype=torch.int8, device=x.device)
-    sc = torch.empty(rows, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    t0 = _t0("layernorm_affine")
-    _lib.check(lib.ll_layernorm_affine_q8(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, Cc,
-                                          eps, _stream()), "ll_layernorm_affine_q8")
-    _t1("layernorm_affine", t0, 3.0 * x.numel())
-    return q, sc
 
 
 def layernorm_affine(x, w, b, eps: float, out=None):
@@ -426,39 +395,6 @@ def quantize_rows(x, q=None, scale=None):
     _lib.check(lib.ll_quantize_rows(x.data_ptr(), q.data_ptr(), scale.data_ptr(), rows, K, K, _stream()), "ll_quantize_rows")
     _t1("quantize_rows", t0, 3.0 * x.numel())
     return q, scale
-
-
-def gemm_w8a8(xq, sx, wq, sw, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-              rows_per_batch: int = 0, frame_len: int = 0, tag: str = "gemm"):
-    """out[M,N] = epilogue(sx[m] sw[n] (xq[M,K] @ wq[N,K]^T) + bias): int8 operands, int32 accumulation, bf16 out."""
-    _chk(xq, "xq", torch.int8); _chk(wq, "wq", torch.int8); _chk(sx, "sx", torch.float32); _chk(sw, "sw", torch.float32)
-    _chk(bias, "bias")
-    K = xq.shape[-1]
-    M = xq.numel() // K
-    N = wq.shape[0]
-    assert wq.shape == (N, K) and bias.numel() == N and sx.numel() == M and sw.numel() == N
-    if out is None:
-        out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
-    _chk(out, "out")
-    assert out.numel() == M * N
-    nmod = 0
-    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
-        _chk(res, "res")
-        assert res.numel() == M * N
-    if epilogue == EPI_BIAS_GATE_RES:
-        _chk(e, "e")
-        nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
-        if mod is not None:
-            _chk(mod, "mod")
-            assert mod.numel() == nmod * N
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_w8a8(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(),
-                                out.data_ptr(), M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx,
-                                rows_per_batch, frame_len, _stream()), "ll_gemm_w8a8")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return out
 
 
 def linear_small(x, w, bias, act_in: int = 0, act_out: int = 0):
@@ -794,324 +730,79 @@ def t5_attention(qk, vt, bias_tab, num_heads: int, seq_len: int):
     return out
 
 
-# ---- MXFP8 (e4m3fn codes [rows, K] + E8M0 scale bytes [rows, K / 32]; include/longlive_hip.h ll_quantize_mx) ----------------
+# ---- quantisation formats of the block linears: what a format is, stated once (include/longlive_hip.h ll_quantize_*) --------------
 fp8 = torch.float8_e4m3fn
 u8 = torch.uint8
 
 
-def _mx_pair(xm, name: str):
-    q, s = xm
-    _chk(q, name, fp8); _chk(s, name + " scales", u8)
-    K = q.shape[-1]
-    rows = q.numel() // K
-    assert K % 32 == 0 and s.numel() == rows * (K // 32), (q.shape, s.shape)
-    return q, s, rows, K
+@dataclass(frozen=True)
+class QFormat:
+    """A row [.., K] of bf16 as codes + scales.  Codes are `bits` wide, packed along K into `code` elements [.., K * bits / 8];
+    scales are E8M0 bytes [rows, K / 32] (block) or one float32 per row.  K must be a multiple of `granule`; `label` is set where
+    the wrappers refuse another K themselves (the packed formats: a wrong K would size the code tensor wrongly)."""
+    name: str              # suffix of the producers' and GEMMs' C entry points
+    code: torch.dtype
+    bits: int
+    block: bool
+    granule: int
+    quantizer: str         # the quantiser's C entry point
+    quant_bytes: float     # bytes per element moved by the quantiser / by a producer, as the KernelTimer tags report them
+    prod_bytes: float
+    label: Optional[str] = None
+
+    def empty(self, shape, device):
+        K = shape[-1]
+        if self.label:
+            assert K % self.granule == 0, f"{self.label} rows need K % {self.granule} == 0, got {K}"
+        rows = math.prod(shape) // K
+        scales = torch.empty(rows, K // 32, dtype=u8, device=device) if self.block else torch.empty(rows, dtype=torch.float32, device=device)
+        return torch.empty(*shape[:-1], K * self.bits // 8, dtype=self.code, device=device), scales
+
+    def pair(self, xm, name: str):
+        """(codes, scales, rows, K) of an operand (codes, scales), checked."""
+        q, s = xm
+        _chk(q, name, self.code); _chk(s, name + " scales", u8 if self.block else torch.float32)
+        width = q.shape[-1]
+        assert width % (self.granule * self.bits // 8) == 0, q.shape
+        K = width * 8 // self.bits
+        rows = q.numel() // width
+        assert s.numel() == (rows * (K // 32) if self.block else rows), (q.shape, s.shape)
+        return q, s, rows, K
 
 
-def _mx_empty(shape, device):
-    K = shape[-1]
-    rows = math.prod(shape) // K
-    return torch.empty(shape, dtype=fp8, device=device), torch.empty(rows, K // 32, dtype=u8, device=device)
+Q8 = QFormat("q8", torch.int8, 8, False, 1, "ll_quantize_rows", 3.0, 3.0)
+F8 = QFormat("f8", u8, 8, False, 1, "ll_quantize_rows_f8", 3.0, 3.0)
+MX = QFormat("mx", fp8, 8, True, 32, "ll_quantize_mx", 3.0, 3.0)
+MX6 = QFormat("mx6", u8, 6, True, 256, "ll_quantize_mx6", 2.75, 3.0, "MXFP6")
+MX4 = QFormat("mx4", u8, 4, True, 256, "ll_quantize_mx4", 2.53, 2.53, "MXFP4")
 
 
-def quantize_mx(x, tag: str = "quantize_mx"):
-    """MXFP8 quantisation of a [..., K] bf16 tensor along K (blocks of 32) -> (e4m3fn [..., K], uint8 scales [rows, K / 32])."""
+def _bind(fn, *fixed):
+    """A public name for a shared implementation with its leading arguments (C entry point, formats) fixed."""
+    f = functools.partial(fn, *fixed)
+    f.__doc__ = fn.__doc__
+    return f
+
+
+def _quantize(fmt: QFormat, x, tag: Optional[str] = None):
+    """Quantise a [..., K] bf16 tensor along K -> (codes [..., K packed], scales) in fmt."""
     _chk(x, "x")
     K = x.shape[-1]
-    rows = x.numel() // K
-    q, s = _mx_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
+    q, s = fmt.empty(tuple(x.shape), x.device)
+    tag = tag or fmt.quantizer[3:]
     t0 = _t0(tag)
-    _lib.check(lib.ll_quantize_mx(x.data_ptr(), q.data_ptr(), s.data_ptr(), rows, K, K, _stream()), "ll_quantize_mx")
-    _t1(tag, t0, 3.0 * x.numel())
+    _lib.check(getattr(_lib.load(), fmt.quantizer)(x.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // K, K, K, _stream()), fmt.quantizer)
+    _t1(tag, t0, fmt.quant_bytes * x.numel())
     return q, s
 
 
-def gemm_mx(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-            rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
-    """out[M,N] = epilogue(sum_k (cx 2^ex)(cw 2^ew) + bias) for MX operands xm = (codes [..., K], scales), wm = (codes [N, K], scales),
-    with gemm()'s epilogues.  mx_out (GELU only): returns the MX codes + scales of the bf16 result instead of it."""
-    xq, sx, M, K = _mx_pair(xm, "xq")
-    wq, sw, N, Kw = _mx_pair(wm, "wq")
-    _chk(bias, "bias")
-    assert Kw == K and wq.shape == (N, K) and bias.numel() == N, (wq.shape, K, bias.shape)
-    nmod = 0
-    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
-        _chk(res, "res")
-        assert res.numel() == M * N
-    if epilogue == EPI_BIAS_GATE_RES:
-        _chk(e, "e")
-        nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
-        if mod is not None:
-            _chk(mod, "mod")
-            assert mod.numel() == nmod * N
-    if mx_out:
-        assert epilogue == EPI_BIAS_GELU and out is None
-        qo, so = _mx_empty((*xq.shape[:-1], N), xq.device)
-    else:
-        qo = so = None
-        if out is None:
-            out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
-        _chk(out, "out")
-        assert out.numel() == M * N
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), _ptr(out), _ptr(qo), _ptr(so),
-                              M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
-               "ll_gemm_mx")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return (qo, so) if mx_out else out
-
-
-def gemm_mx_qkv_v_insert(xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int, tag: str = "gemm_qkv"):
-    """gemm_qkv_v_insert on MX operands: xm = (codes [B*L or B,L, K], scales), wm = (codes [3C, K], scales).  Returns [B, L, 3C]
-    with the q and k thirds valid; the V third went into cache_v [B, S, H, D]."""
-    xq, sx, M, K = _mx_pair(xm, "xq")
-    wq, sw, N, Kw = _mx_pair(wm, "wq")
-    _chk(bias, "bias"); _chk(cache_v, "cache_v")
-    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
-    S = cache_v.shape[1]
-    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
-    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                  M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-               "ll_gemm_mx_qkv")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return out
-
-
-def ln_modulate_mx(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate emitting the MX codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(e, "e")
-    B, L, Cc = x.shape
-    nmod = e.shape[-2]
-    assert e.shape == (B, num_frames, nmod, Cc)
-    if mod is not None:
-        _chk(mod, "mod")
-        assert mod.numel() == nmod * Cc
-    q, s = _mx_empty((B, L, Cc), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_mx(x.data_ptr(), q.data_ptr(), s.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
-                                     B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_mx")
-    _t1(tag, t0, 3.0 * x.numel())
-    return q, s
-
-
-def ln_modulate_tab_mx(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate_tab emitting the MX codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(tab, "tab", torch.float32)
-    B, L, Cc = x.shape
-    nmod = tab.shape[2]
-    assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
-    q, s = _mx_empty((B, L, Cc), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_tab_mx(x.data_ptr(), q.data_ptr(), s.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
-                                         B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab_mx")
-    _t1(tag, t0, 3.0 * B * L * Cc)
-    return q, s
-
-
-def layernorm_affine_mx(x, w, b, eps: float):
-    """layernorm_affine emitting the MX codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
-    Cc = x.shape[-1]
-    assert w.numel() == Cc and b.numel() == Cc
-    q, s = _mx_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
-    t0 = _t0("layernorm_affine")
-    _lib.check(lib.ll_layernorm_affine_mx(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // Cc, Cc,
-                                          eps, _stream()), "ll_layernorm_affine_mx")
-    _t1("layernorm_affine", t0, 3.0 * x.numel())
-    return q, s
-
-
-def gemm_plan_mx(M: int, N: int, K: int) -> str:
-    """Kernel instance, tile and grid of a gemm_mx / gemm_mx_qkv_v_insert call (host only)."""
-    import ctypes
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_gemm_plan_mx(M, N, K, buf, 256), "ll_gemm_plan_mx")
-    return buf.value.decode()
-
-
-# ---- FP8 rowwise (e4m3fn codes [rows, K] as uint8 + one float32 scale per row; include/longlive_hip.h ll_quantize_rows_f8) ---------
-def _f8_empty(shape, device):
-    K = shape[-1]
-    rows = math.prod(shape) // K
-    return torch.empty(shape, dtype=u8, device=device), torch.empty(rows, dtype=torch.float32, device=device)
-
-
-def quantize_rows_f8(x, tag: str = "quantize_rows_f8"):
-    """FP8 rowwise quantisation of a [..., K] bf16 tensor -> (e4m3fn codes as uint8 [..., K], float32 scale [rows]):
-    scale = max|x| / 448 per row, code = e4m3fn(clamp(x / scale, +-448))."""
-    _chk(x, "x")
-    K = x.shape[-1]
-    rows = x.numel() // K
-    q, sc = _f8_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_quantize_rows_f8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, K, K, _stream()), "ll_quantize_rows_f8")
-    _t1(tag, t0, 3.0 * x.numel())
-    return q, sc
-
-
-def _f8_operand(q, sc, name: str):
-    _chk(q, name, u8); _chk(sc, name + " scales", torch.float32)
-    K = q.shape[-1]
-    rows = q.numel() // K
-    assert sc.numel() == rows, (q.shape, sc.shape)
-    return rows, K
-
-
-def gemm_f8(xq, sx, wq, sw, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-            rows_per_batch: int = 0, frame_len: int = 0, tag: str = "gemm"):
-    """out[M,N] = epilogue(sx[m] sw[n] sum_k dec(xq[m,k]) dec(wq[n,k]) + bias): gemm_w8a8 with e4m3fn codes (uint8) and fp32
-    accumulation."""
-    M, K = _f8_operand(xq, sx, "xq")
-    N, Kw = _f8_operand(wq, sw, "wq")
-    _chk(bias, "bias")
-    assert Kw == K and wq.shape == (N, K) and bias.numel() == N, (wq.shape, K, bias.shape)
-    if out is None:
-        out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
-    _chk(out, "out")
-    assert out.numel() == M * N
-    nmod = 0
-    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
-        _chk(res, "res")
-        assert res.numel() == M * N
-    if epilogue == EPI_BIAS_GATE_RES:
-        _chk(e, "e")
-        nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
-        if mod is not None:
-            _chk(mod, "mod")
-            assert mod.numel() == nmod * N
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_f8(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, N,
-                              epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()), "ll_gemm_f8")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return out
-
-
-def gemm_f8_qkv_v_insert(xf, wf, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int, tag: str = "gemm_qkv"):
-    """gemm_qkv_v_insert on FP8 rowwise operands: xf = (codes [B*L or B,L, K], scales [B*L]), wf = (codes [3C, K], scales [3C]).
-    Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v [B, S, H, D]."""
-    xq, sx = xf
-    wq, sw = wf
-    M, K = _f8_operand(xq, sx, "xq")
-    N, Kw = _f8_operand(wq, sw, "wq")
-    _chk(bias, "bias"); _chk(cache_v, "cache_v")
-    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
-    S = cache_v.shape[1]
-    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
-    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_f8_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                  M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-               "ll_gemm_f8_qkv")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return out
-
-
-def ln_modulate_f8(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate emitting the FP8 rowwise codes + row scales of its bf16 output."""
-    _chk(x, "x"); _chk(e, "e")
-    B, L, Cc = x.shape
-    nmod = e.shape[-2]
-    assert e.shape == (B, num_frames, nmod, Cc)
-    if mod is not None:
-        _chk(mod, "mod")
-        assert mod.numel() == nmod * Cc
-    q, sc = _f8_empty((B, L, Cc), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_f8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
-                                     B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_f8")
-    _t1(tag, t0, 3.0 * x.numel())
-    return q, sc
-
-
-def ln_modulate_tab_f8(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate_tab emitting the FP8 rowwise codes + row scales of its bf16 output."""
-    _chk(x, "x"); _chk(tab, "tab", torch.float32)
-    B, L, Cc = x.shape
-    nmod = tab.shape[2]
-    assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
-    q, sc = _f8_empty((B, L, Cc), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_tab_f8(x.data_ptr(), q.data_ptr(), sc.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
-                                         B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab_f8")
-    _t1(tag, t0, 3.0 * B * L * Cc)
-    return q, sc
-
-
-def layernorm_affine_f8(x, w, b, eps: float):
-    """layernorm_affine emitting the FP8 rowwise codes + row scales of its bf16 output."""
-    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
-    Cc = x.shape[-1]
-    assert w.numel() == Cc and b.numel() == Cc
-    q, sc = _f8_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
-    t0 = _t0("layernorm_affine")
-    _lib.check(lib.ll_layernorm_affine_f8(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), sc.data_ptr(), x.numel() // Cc, Cc,
-                                          eps, _stream()), "ll_layernorm_affine_f8")
-    _t1("layernorm_affine", t0, 3.0 * x.numel())
-    return q, sc
-
-
-def gemm_plan_f8(M: int, N: int, K: int) -> str:
-    """Kernel instance, tile and grid of a gemm_f8 / gemm_f8_qkv_v_insert call (host only)."""
-    import ctypes
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_gemm_plan_f8(M, N, K, buf, 256), "ll_gemm_plan_f8")
-    return buf.value.decode()
-
-
-# ---- MXFP6 (E2M3 codes packed 6 bits each, uint8 [rows, 3K/4] + E8M0 scale bytes [rows, K / 32]; include/longlive_hip.h
-# ll_quantize_mx6: K % 256 == 0) ----------------------------------------------------------------------------------------------------
-def _mx6_pair(xm, name: str):
-    q, s = xm
-    _chk(q, name, u8); _chk(s, name + " scales", u8)
-    assert q.shape[-1] % 192 == 0, q.shape
-    K = q.shape[-1] // 3 * 4
-    rows = q.numel() // q.shape[-1]
-    assert s.numel() == rows * (K // 32), (q.shape, s.shape)
-    return q, s, rows, K
-
-
-def _mx6_empty(shape, device):
-    K = shape[-1]
-    assert K % 256 == 0, f"MXFP6 rows need K % 256 == 0, got {K}"
-    rows = math.prod(shape) // K
-    return torch.empty(*shape[:-1], K // 4 * 3, dtype=u8, device=device), torch.empty(rows, K // 32, dtype=u8, device=device)
-
-
-def quantize_mx6(x, tag: str = "quantize_mx6"):
-    """MXFP6 quantisation of a [..., K] bf16 tensor along K (blocks of 32) -> (packed E2M3 uint8 [..., 3K/4], uint8 scales [rows, K / 32])."""
-    _chk(x, "x")
-    K = x.shape[-1]
-    rows = x.numel() // K
-    q, s = _mx6_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_quantize_mx6(x.data_ptr(), q.data_ptr(), s.data_ptr(), rows, K, K, _stream()), "ll_quantize_mx6")
-    _t1(tag, t0, 2.75 * x.numel())
-    return q, s
-
-
-def gemm_mx6(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-             rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
-    """gemm_mx on MXFP6 operands xm = (packed codes [..., 3K/4], scales), wm = (packed codes [N, 3K/4], scales).  mx_out (GELU only):
-    returns the MXFP6 codes + scales of the bf16 result instead of it."""
-    xq, sx, M, K = _mx6_pair(xm, "xq")
-    wq, sw, N, Kw = _mx6_pair(wm, "wq")
+def _qgemm(entry: str, afmt: QFormat, wfmt: QFormat, xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None,
+           gate_idx: int = 0, rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
+    """out[M,N] = epilogue(x @ w^T + bias) with gemm()'s epilogues for operands xm = (codes [..., K packed], scales) in afmt and
+    wm = (codes [N, K packed], scales) in wfmt.  mx_out (block-scaled formats, GELU only): returns the afmt codes + scales of the
+    bf16 result instead of it."""
+    xq, sx, M, K = afmt.pair(xm, "xq")
+    wq, sw, N, Kw = wfmt.pair(wm, "wq")
     _chk(bias, "bias")
     assert Kw == K and wq.dim() == 2 and bias.numel() == N, (wq.shape, K, bias.shape)
     nmod = 0
@@ -1126,44 +817,51 @@ def gemm_mx6(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None,
             _chk(mod, "mod")
             assert mod.numel() == nmod * N
     if mx_out:
-        assert epilogue == EPI_BIAS_GELU and out is None
-        qo, so = _mx6_empty((*xq.shape[:-1], N), xq.device)
+        assert afmt.block and epilogue == EPI_BIAS_GELU and out is None
+        qo, so = afmt.empty((*xq.shape[:-1], N), xq.device)
     else:
         qo = so = None
         if out is None:
             out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
         _chk(out, "out")
         assert out.numel() == M * N
-    lib = _lib.load()
+    outs = (_ptr(out), _ptr(qo), _ptr(so)) if afmt.block else (out.data_ptr(),)      # only the block-scaled entries can write codes
     t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx6(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), _ptr(out), _ptr(qo), _ptr(so),
-                               M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
-               "ll_gemm_mx6")
+    _lib.check(getattr(_lib.load(), entry)(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), *outs, M, N, K, N,
+                                           epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
+               entry)
     _t1(tag, t0, 2.0 * M * N * K)
     return (qo, so) if mx_out else out
 
 
-def gemm_mx6_qkv_v_insert(xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int,
-                          tag: str = "gemm_qkv"):
-    """gemm_qkv_v_insert on MXFP6 operands.  Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v [B, S, H, D]."""
-    xq, sx, M, K = _mx6_pair(xm, "xq")
-    wq, sw, N, Kw = _mx6_pair(wm, "wq")
+def _qgemm_rowwise(entry: str, fmt: QFormat):
+    """The per-row-scale GEMMs take codes and scales as separate arguments."""
+    def f(xq, sx, wq, sw, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
+          rows_per_batch: int = 0, frame_len: int = 0, tag: str = "gemm"):
+        return _qgemm(entry, fmt, fmt, (xq, sx), (wq, sw), bias, epilogue, out, res, e, mod, gate_idx, rows_per_batch, frame_len, tag=tag)
+    return f
+
+
+def _qgemm_qkv(entry: str, afmt: QFormat, wfmt: QFormat, xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int,
+               B: int, L: int, tag: str = "gemm_qkv"):
+    """gemm_qkv_v_insert on quantised operands: xm = (codes [B*L or B,L, K packed], scales) in afmt, wm = (codes [3C, K packed],
+    scales) in wfmt.  Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v [B, S, H, D]."""
+    xq, sx, M, K = afmt.pair(xm, "xq")
+    wq, sw, N, Kw = wfmt.pair(wm, "wq")
     _chk(bias, "bias"); _chk(cache_v, "cache_v")
     assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
     S = cache_v.shape[1]
     assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
     out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
-    lib = _lib.load()
     t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx6_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                   M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-               "ll_gemm_mx6_qkv")
+    _lib.check(getattr(_lib.load(), entry)(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                           M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()), entry)
     _t1(tag, t0, 2.0 * M * N * K)
     return out
 
 
-def ln_modulate_mx6(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate emitting the MXFP6 codes + scales of its bf16 output."""
+def _ln_modulate_q(fmt: QFormat, x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate emitting the fmt codes + scales of its bf16 output."""
     _chk(x, "x"); _chk(e, "e")
     B, L, Cc = x.shape
     nmod = e.shape[-2]
@@ -1171,263 +869,74 @@ def ln_modulate_mx6(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, 
     if mod is not None:
         _chk(mod, "mod")
         assert mod.numel() == nmod * Cc
-    q, s = _mx6_empty((B, L, Cc), x.device)
-    lib = _lib.load()
+    q, s = fmt.empty((B, L, Cc), x.device)
+    entry = "ll_ln_modulate_" + fmt.name
     t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_mx6(x.data_ptr(), q.data_ptr(), s.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
-                                      B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_mx6")
-    _t1(tag, t0, 3.0 * x.numel())
+    _lib.check(getattr(_lib.load(), entry)(x.data_ptr(), q.data_ptr(), s.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
+                                           B, L, Cc, num_frames, eps, _stream()), entry)
+    _t1(tag, t0, fmt.prod_bytes * x.numel())
     return q, s
 
 
-def ln_modulate_tab_mx6(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate_tab emitting the MXFP6 codes + scales of its bf16 output."""
+def _ln_modulate_tab_q(fmt: QFormat, x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate_tab emitting the fmt codes + scales of its bf16 output."""
     _chk(x, "x"); _chk(tab, "tab", torch.float32)
     B, L, Cc = x.shape
     nmod = tab.shape[2]
     assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
-    q, s = _mx6_empty((B, L, Cc), x.device)
-    lib = _lib.load()
+    q, s = fmt.empty((B, L, Cc), x.device)
+    entry = "ll_ln_modulate_tab_" + fmt.name
     t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_tab_mx6(x.data_ptr(), q.data_ptr(), s.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
-                                          B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab_mx6")
-    _t1(tag, t0, 3.0 * B * L * Cc)
+    _lib.check(getattr(_lib.load(), entry)(x.data_ptr(), q.data_ptr(), s.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
+                                           B, L, Cc, num_frames, eps, _stream()), entry)
+    _t1(tag, t0, fmt.prod_bytes * B * L * Cc)
     return q, s
 
 
-def layernorm_affine_mx6(x, w, b, eps: float):
-    """layernorm_affine emitting the MXFP6 codes + scales of its bf16 output."""
+def _layernorm_affine_q(fmt: QFormat, x, w, b, eps: float):
+    """layernorm_affine emitting the fmt codes + scales of its bf16 output."""
     _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
     Cc = x.shape[-1]
     assert w.numel() == Cc and b.numel() == Cc
-    q, s = _mx6_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
+    q, s = fmt.empty(tuple(x.shape), x.device)
+    entry = "ll_layernorm_affine_" + fmt.name
     t0 = _t0("layernorm_affine")
-    _lib.check(lib.ll_layernorm_affine_mx6(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // Cc, Cc,
-                                           eps, _stream()), "ll_layernorm_affine_mx6")
-    _t1("layernorm_affine", t0, 3.0 * x.numel())
+    _lib.check(getattr(_lib.load(), entry)(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // Cc, Cc,
+                                           eps, _stream()), entry)
+    _t1("layernorm_affine", t0, fmt.prod_bytes * x.numel())
     return q, s
 
 
-def gemm_plan_mx6(M: int, N: int, K: int) -> str:
-    """Kernel instance, tile and grid of a gemm_mx6 / gemm_mx6_qkv_v_insert call (host only)."""
+def _gemm_plan(entry: str, M: int, N: int, K: int) -> str:
+    """Kernel instance, tile and grid of the GEMM (and its QKV V-insert form) behind a ll_gemm_plan_* entry (host only)."""
     import ctypes
     buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_gemm_plan_mx6(M, N, K, buf, 256), "ll_gemm_plan_mx6")
+    _lib.check(getattr(_lib.load(), entry)(M, N, K, buf, 256), entry)
     return buf.value.decode()
 
 
-# ---- MXFP4 weights over MXFP6 activations (E2M1 codes packed 4 bits each, uint8 [rows, K/2] + E8M0 scale bytes [rows, K / 32];
-# include/longlive_hip.h ll_quantize_mx4: K % 256 == 0; activations as in the MXFP6 wrappers above) ----------------------------------
-def _mx4_pair(wm, name: str):
-    q, s = wm
-    _chk(q, name, u8); _chk(s, name + " scales", u8)
-    assert q.shape[-1] % 128 == 0, q.shape
-    K = q.shape[-1] * 2
-    rows = q.numel() // q.shape[-1]
-    assert s.numel() == rows * (K // 32), (q.shape, s.shape)
-    return q, s, rows, K
+# The public names.  Per format: the quantiser and the three producers, each returning (codes, scales) equal bit for bit to the
+# quantiser applied to the bf16 form's output (int8: quantize_rows and ln_modulate_tab(q8=True) above share their C entry points with
+# the bf16 forms).  Per activation x weight pairing: the GEMM, its QKV V-insert form and its plan string.
+quantize_rows_f8, quantize_mx, quantize_mx6, quantize_mx4 = (_bind(_quantize, f) for f in (F8, MX, MX6, MX4))
+ln_modulate_q8, ln_modulate_f8, ln_modulate_mx, ln_modulate_mx6, ln_modulate_mx4 = (_bind(_ln_modulate_q, f) for f in (Q8, F8, MX, MX6, MX4))
+ln_modulate_tab_f8, ln_modulate_tab_mx, ln_modulate_tab_mx6, ln_modulate_tab_mx4 = (_bind(_ln_modulate_tab_q, f) for f in (F8, MX, MX6, MX4))
+layernorm_affine_q8, layernorm_affine_f8, layernorm_affine_mx, layernorm_affine_mx6, layernorm_affine_mx4 = (
+    _bind(_layernorm_affine_q, f) for f in (Q8, F8, MX, MX6, MX4))
 
-
-def quantize_mx4(x, tag: str = "quantize_mx4"):
-    """MXFP4 quantisation of a [..., K] bf16 tensor along K (blocks of 32) -> (packed E2M1 uint8 [..., K/2], uint8 scales [rows, K / 32])."""
-    _chk(x, "x")
-    K = x.shape[-1]
-    assert K % 256 == 0, f"MXFP4 rows need K % 256 == 0, got {K}"
-    rows = x.numel() // K
-    q = torch.empty(*x.shape[:-1], K // 2, dtype=u8, device=x.device)
-    s = torch.empty(rows, K // 32, dtype=u8, device=x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_quantize_mx4(x.data_ptr(), q.data_ptr(), s.data_ptr(), rows, K, K, _stream()), "ll_quantize_mx4")
-    _t1(tag, t0, 2.53 * x.numel())
-    return q, s
-
-
-def gemm_mx4w6(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-               rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
-    """gemm_mx6 with MXFP4 weights: xm = (packed E2M3 codes [..., 3K/4], scales) as from quantize_mx6 or an MXFP6 producer,
-    wm = (packed E2M1 codes [N, K/2], scales) from quantize_mx4.  mx_out (GELU only): returns the MXFP6 codes + scales of the bf16
-    result instead of it."""
-    xq, sx, M, K = _mx6_pair(xm, "xq")
-    wq, sw, N, Kw = _mx4_pair(wm, "wq")
-    _chk(bias, "bias")
-    assert Kw == K and wq.dim() == 2 and bias.numel() == N, (wq.shape, K, bias.shape)
-    nmod = 0
-    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
-        _chk(res, "res")
-        assert res.numel() == M * N
-    if epilogue == EPI_BIAS_GATE_RES:
-        _chk(e, "e")
-        nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
-        if mod is not None:
-            _chk(mod, "mod")
-            assert mod.numel() == nmod * N
-    if mx_out:
-        assert epilogue == EPI_BIAS_GELU and out is None
-        qo, so = _mx6_empty((*xq.shape[:-1], N), xq.device)
-    else:
-        qo = so = None
-        if out is None:
-            out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
-        _chk(out, "out")
-        assert out.numel() == M * N
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx4w6(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), _ptr(out), _ptr(qo),
-                                 _ptr(so), M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len,
-                                 _stream()), "ll_gemm_mx4w6")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return (qo, so) if mx_out else out
-
-
-def gemm_mx4w6_qkv_v_insert(xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int,
-                            tag: str = "gemm_qkv"):
-    """gemm_mx6_qkv_v_insert with MXFP4 weights.  Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v
-    [B, S, H, D]."""
-    xq, sx, M, K = _mx6_pair(xm, "xq")
-    wq, sw, N, Kw = _mx4_pair(wm, "wq")
-    _chk(bias, "bias"); _chk(cache_v, "cache_v")
-    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
-    S = cache_v.shape[1]
-    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
-    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx4w6_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                     M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-               "ll_gemm_mx4w6_qkv")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return out
-
-
-def gemm_plan_mx4w6(M: int, N: int, K: int) -> str:
-    """Kernel instance, tile and grid of a gemm_mx4w6 / gemm_mx4w6_qkv_v_insert call (host only)."""
-    import ctypes
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_gemm_plan_mx4w6(M, N, K, buf, 256), "ll_gemm_plan_mx4w6")
-    return buf.value.decode()
-
-
-# ---- W4A4: MXFP4 activations and weights (both as from quantize_mx4: packed E2M1 [rows, K/2] + E8M0 scales [rows, K / 32]) ----------
-def _mx4_empty(shape, device):
-    K = shape[-1]
-    assert K % 256 == 0, f"MXFP4 rows need K % 256 == 0, got {K}"
-    rows = math.prod(shape) // K
-    return torch.empty(*shape[:-1], K // 2, dtype=u8, device=device), torch.empty(rows, K // 32, dtype=u8, device=device)
-
-
-def gemm_mx4(xm, wm, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-             rows_per_batch: int = 0, frame_len: int = 0, mx_out: bool = False, tag: str = "gemm"):
-    """gemm_mx4w6 with MXFP4 activations: xm = (packed E2M1 codes [..., K/2], scales) as from quantize_mx4 or an MXFP4 producer,
-    wm = (packed E2M1 codes [N, K/2], scales).  mx_out (GELU only): returns the MXFP4 codes + scales of the bf16 result instead of it."""
-    xq, sx, M, K = _mx4_pair(xm, "xq")
-    wq, sw, N, Kw = _mx4_pair(wm, "wq")
-    _chk(bias, "bias")
-    assert Kw == K and wq.dim() == 2 and bias.numel() == N, (wq.shape, K, bias.shape)
-    nmod = 0
-    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
-        _chk(res, "res")
-        assert res.numel() == M * N
-    if epilogue == EPI_BIAS_GATE_RES:
-        _chk(e, "e")
-        nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
-        if mod is not None:
-            _chk(mod, "mod")
-            assert mod.numel() == nmod * N
-    if mx_out:
-        assert epilogue == EPI_BIAS_GELU and out is None
-        qo, so = _mx4_empty((*xq.shape[:-1], N), xq.device)
-    else:
-        qo = so = None
-        if out is None:
-            out = torch.empty(*xq.shape[:-1], N, dtype=bf16, device=xq.device)
-        _chk(out, "out")
-        assert out.numel() == M * N
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx4(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), _ptr(out), _ptr(qo), _ptr(so),
-                               M, N, K, N, epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
-               "ll_gemm_mx4")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return (qo, so) if mx_out else out
-
-
-def gemm_mx4_qkv_v_insert(xm, wm, bias, cache_v, write_start: int, roped_offset: int, write_len: int, B: int, L: int,
-                          tag: str = "gemm_qkv"):
-    """gemm_mx6_qkv_v_insert on MXFP4 operands.  Returns [B, L, 3C] with the q and k thirds valid; the V third went into cache_v
-    [B, S, H, D]."""
-    xq, sx, M, K = _mx4_pair(xm, "xq")
-    wq, sw, N, Kw = _mx4_pair(wm, "wq")
-    _chk(bias, "bias"); _chk(cache_v, "cache_v")
-    assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
-    S = cache_v.shape[1]
-    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
-    out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_mx4_qkv(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                   M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-               "ll_gemm_mx4_qkv")
-    _t1(tag, t0, 2.0 * M * N * K)
-    return out
-
-
-def ln_modulate_mx4(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate emitting the MXFP4 codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(e, "e")
-    B, L, Cc = x.shape
-    nmod = e.shape[-2]
-    assert e.shape == (B, num_frames, nmod, Cc)
-    if mod is not None:
-        _chk(mod, "mod")
-        assert mod.numel() == nmod * Cc
-    q, s = _mx4_empty((B, L, Cc), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_mx4(x.data_ptr(), q.data_ptr(), s.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
-                                      B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_mx4")
-    _t1(tag, t0, 2.53 * x.numel())
-    return q, s
-
-
-def ln_modulate_tab_mx4(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate_tab emitting the MXFP4 codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(tab, "tab", torch.float32)
-    B, L, Cc = x.shape
-    nmod = tab.shape[2]
-    assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
-    q, s = _mx4_empty((B, L, Cc), x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_tab_mx4(x.data_ptr(), q.data_ptr(), s.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
-                                          B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab_mx4")
-    _t1(tag, t0, 2.53 * B * L * Cc)
-    return q, s
-
-
-def layernorm_affine_mx4(x, w, b, eps: float):
-    """layernorm_affine emitting the MXFP4 codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
-    Cc = x.shape[-1]
-    assert w.numel() == Cc and b.numel() == Cc
-    q, s = _mx4_empty(tuple(x.shape), x.device)
-    lib = _lib.load()
-    t0 = _t0("layernorm_affine")
-    _lib.check(lib.ll_layernorm_affine_mx4(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // Cc, Cc,
-                                           eps, _stream()), "ll_layernorm_affine_mx4")
-    _t1("layernorm_affine", t0, 2.53 * x.numel())
-    return q, s
-
-
-def gemm_plan_mx4(M: int, N: int, K: int) -> str:
-    """Kernel instance, tile and grid of a gemm_mx4 / gemm_mx4_qkv_v_insert call (host only)."""
-    import ctypes
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_gemm_plan_mx4(M, N, K, buf, 256), "ll_gemm_plan_mx4")
-    return buf.value.decode()
+gemm_w8a8 = _qgemm_rowwise("ll_gemm_w8a8", Q8)       # int8 codes, int32 accumulation
+gemm_f8 = _qgemm_rowwise("ll_gemm_f8", F8)           # e4m3fn codes (uint8), fp32 accumulation
+gemm_mx = _bind(_qgemm, "ll_gemm_mx", MX, MX)
+gemm_mx6 = _bind(_qgemm, "ll_gemm_mx6", MX6, MX6)
+gemm_mx4w6 = _bind(_qgemm, "ll_gemm_mx4w6", MX6, MX4)      # MXFP4 weights over MXFP6 activations
+gemm_mx4 = _bind(_qgemm, "ll_gemm_mx4", MX4, MX4)
+gemm_f8_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_f8_qkv", F8, F8)
+gemm_mx_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_mx_qkv", MX, MX)
+gemm_mx6_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_mx6_qkv", MX6, MX6)
+gemm_mx4w6_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_mx4w6_qkv", MX6, MX4)
+gemm_mx4_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_mx4_qkv", MX4, MX4)
+gemm_plan_f8, gemm_plan_mx, gemm_plan_mx6, gemm_plan_mx4w6, gemm_plan_mx4 = (
+    _bind(_gemm_plan, "ll_gemm_plan_" + n) for n in ("f8", "mx", "mx6", "mx4w6", "mx4"))
 
 
 # ---- MXFP8 self-attention over a block-scaled shadow of the KV cache (attention_mx.hip) ------------------------------------------

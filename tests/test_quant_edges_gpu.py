@@ -362,19 +362,20 @@ def test_quantizers_at_small_rows_and_k_with_row_stride(fam, rows, K_sel):
 # 1536 (3, w: the model's, tested in the families' own modules), 1792 (4, p), 2048 (4, w); plus the narrowest C each family accepts.
 PRODUCER_C = (256, 512, 768, 1024, 1280, 1792, 2048)
 PRODUCERS = [(f, C) for f in ("mx6", "mx4") for C in PRODUCER_C] + [("mx", C) for C in (32,) + PRODUCER_C] + \
-            [("f8", C) for C in (8,) + PRODUCER_C]
+            [(f, C) for f in ("f8", "q8") for C in (8,) + PRODUCER_C]
 
 
 @pytest.mark.parametrize("fam,C", PRODUCERS)
 def test_producers_every_dispatch_instance(ops, fam, C):
     """ln_modulate (with and without mod), its _tab_ form and layernorm_affine emitting each family's codes + scales, B = 2, F = 3,
     frame_len 7 (42 rows: not a multiple of the 4 rows per workgroup): the bytes equal the family's quantiser applied to the bf16
-    producer."""
+    producer.  q8 (int8 rows): the quantiser is quantize_rows and the _tab_ form is ln_modulate_tab(q8=True)."""
     B, F, fs = 2, 3, 7
     L = F * fs
     suffix = "_" + fam
-    q = getattr(ops, "quantize_rows_f8" if fam == "f8" else "quantize" + suffix)
-    x = (hard_x_f8 if fam == "f8" else hard_x_mx)(B * L, max(C, 128), C)[:, :C].contiguous().view(B, L, C).to(DEV)
+    q = getattr(ops, {"f8": "quantize_rows_f8", "q8": "quantize_rows"}.get(fam, "quantize" + suffix))
+    ln_tab = (lambda *a: ops.ln_modulate_tab(*a, q8=True)) if fam == "q8" else getattr(ops, "ln_modulate_tab" + suffix)
+    x = (hard_x_f8 if fam in ("f8", "q8") else hard_x_mx)(B * L, max(C, 128), C)[:, :C].contiguous().view(B, L, C).to(DEV)
     e, mod = hn(f"pe{C}", (B, F, 6, C), 0.5).to(DEV), hn(f"pm{C}", (6, C), 0.1).to(DEV)
 
     def same(got, want, what):
@@ -385,7 +386,7 @@ def test_producers_every_dispatch_instance(ops, fam, C):
         same(getattr(ops, "ln_modulate" + suffix)(x, e, md, 3, 4, F, 1e-6), q(ops.ln_modulate(x, e, md, 3, 4, F, 1e-6)),
              f"ln_modulate mod={md is not None}")
     tab = ops.modulation_table_f32(e, mod.view(1, 6, C), 0b010010)[0]
-    same(getattr(ops, "ln_modulate_tab" + suffix)(x, tab, 3, 4, F, 1e-6), q(ops.ln_modulate_tab(x, tab, 3, 4, F, 1e-6)), "ln_modulate_tab")
+    same(ln_tab(x, tab, 3, 4, F, 1e-6), q(ops.ln_modulate_tab(x, tab, 3, 4, F, 1e-6)), "ln_modulate_tab")
     w, b = hn(f"nw{C}", (C,), 0.2).to(DEV), hn(f"nb{C}", (C,), 0.1).to(DEV)
     same(getattr(ops, "layernorm_affine" + suffix)(x, w, b, 1e-6), q(ops.layernorm_affine(x, w, b, 1e-6)), "layernorm_affine")
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Outputs of the row kernels (ll_ln_modulate [+ q8], ll_layernorm_affine [+ q8], ll_rmsnorm, ll_qk_norm_rope_kv_store) on seeded
+"""Outputs of the row kernels (ll_ln_modulate, ll_ln_modulate_tab, ll_layernorm_affine, each in its bf16, q8, f8, mx, mx6 and mx4 forms,
+ll_rmsnorm, ll_qk_norm_rope_kv_store) on seeded
 inputs at the production width and at a ragged one, written to a .pt file: run once per library build
 (LONGLIVE_HIP_LIB=... python3 tools/rowkernel_dump.py out.pt) and compare the files (`--compare a.pt b.pt`: every tensor
 bit-identical or the script exits 1).  Used when the arithmetic of these kernels is re-expressed without changing its values."""
@@ -42,6 +43,15 @@ def main(path):
         out[f"{tag}.ln_affine"] = ops.layernorm_affine(x, w, b, 1e-6)
         qv, sc = ops.layernorm_affine_q8(x, w, b, 1e-6)
         out[f"{tag}.ln_affine_q8"], out[f"{tag}.ln_affine_q8_scale"] = qv, sc
+        tab = ops.modulation_table_f32(e, mod.view(1, 6, C), 0b010010)[0]
+        out[f"{tag}.ln_tab"] = ops.ln_modulate_tab(x, tab, 3, 4, F, 1e-6)
+        out[f"{tag}.ln_tab_q8"], out[f"{tag}.ln_tab_q8_scale"] = ops.ln_modulate_tab(x, tab, 3, 4, F, 1e-6, q8=True)
+        for fmt in ("f8", "mx", "mx6", "mx4"):
+            for name, (qv, sc) in (("ln_mod_pre", getattr(ops, "ln_modulate_" + fmt)(x, e, None, 0, 1, F, 1e-6)),
+                                   ("ln_mod", getattr(ops, "ln_modulate_" + fmt)(x, e, mod, 3, 4, F, 1e-6)),
+                                   ("ln_tab", getattr(ops, "ln_modulate_tab_" + fmt)(x, tab, 3, 4, F, 1e-6)),
+                                   ("ln_affine", getattr(ops, "layernorm_affine_" + fmt)(x, w, b, 1e-6))):
+                out[f"{tag}.{name}_{fmt}"], out[f"{tag}.{name}_{fmt}_scale"] = qv.view(torch.uint8), sc
         out[f"{tag}.rmsnorm"] = ops.rmsnorm(x, w, 1e-6)
         qkv = rnd(1, L, 3 * C, scale=1.5)
         fs = L // F
