@@ -414,7 +414,9 @@ int ll_add_noise(const ll_bf16* x0, const ll_bf16* noise, const float* sigma, ll
                  ll_stream stream);
 
 /* out[i] = sigmas[argmin_j |timesteps[j] - t[i]|]: the table lookup shared by flow->x0 and add_noise
- * (utils/wan_wrapper.py:195-197; utils/scheduler.py:172-174).  All fp32 device arrays; lowest index wins ties. */
+ * (utils/wan_wrapper.py:195-197; utils/scheduler.py:172-174).  All fp32 device arrays; lowest index wins ties.
+ * A query with no nearest entry -- t[i] NaN, or +-inf against a finite table (every distance NaN or +inf) -- gives sigmas[0], the
+ * index torch.argmin returns for such a row; no query reads outside the tables. */
 int ll_sigma_lookup(const float* t, const float* timesteps, const float* sigmas, float* out, int n, int n_table,
                     ll_stream stream);
 

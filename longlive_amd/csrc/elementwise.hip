@@ -625,7 +625,8 @@ __global__ __launch_bounds__(256) void add_noise_kernel(const bf16* __restrict__
 
 
 // sigma_t = sigmas[argmin_i |timesteps[i] - t|]  (utils/wan_wrapper.py:195-197, utils/scheduler.py:172-174).
-// One wave per query; fp64 differences; ties resolve to the lowest index like torch.argmin.
+// One wave per query; fp64 differences; ties resolve to the lowest index like torch.argmin.  A query whose distances are all NaN
+// or all +inf (t NaN or +-inf) has no candidate below the initial +inf: index 0, torch.argmin's answer for such a row.
 __global__ __launch_bounds__(64) void sigma_lookup_kernel(const float* __restrict__ t, const float* __restrict__ timesteps,
                                                           const float* __restrict__ sigmas, float* __restrict__ out,
                                                           int n_table) {
@@ -643,6 +644,7 @@ __global__ __launch_bounds__(64) void sigma_lookup_kernel(const float* __restric
     int oi = __shfl_xor(bi, o, 64);
     if (ob < best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
+  if (bi == 0x7fffffff) bi = 0;     // no lane found a candidate (t is NaN: no distance compares below inf): torch.argmin's index 0
   if (lane == 0) out[blockIdx.x] = sigmas[bi];
 }
 
