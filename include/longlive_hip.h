@@ -51,7 +51,8 @@ enum ll_epilogue {
  * ll_layernorm_affine_mx6, ll_gemm_plan_mx6);
  * 111 = MXFP4 weights over MXFP6 activations (ll_quantize_mx4, ll_gemm_mx4w6, ll_gemm_mx4w6_qkv, ll_gemm_plan_mx4w6); W4A4 block
  * linears (ll_gemm_mx4, ll_gemm_mx4_qkv, ll_ln_modulate_mx4, ll_ln_modulate_tab_mx4, ll_layernorm_affine_mx4, ll_gemm_plan_mx4) only
- * add entry points, so they keep 111; so does ll_conv_plan. */
+ * add entry points, so they keep 111; so does ll_conv_plan, and so do the VAE encoder's entry points (ll_conv_cl_down, ll_conv_cl_tdown,
+ * ll_conv_down_plan, ll_pixels_to_cl, ll_vae_scale_tchw). */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -426,7 +427,7 @@ int ll_sigma_lookup(const float* t, const float* timesteps, const float* sigmas,
  * hash_normal on any host (csrc/synth_hash.h is compiled for both sides; tests/test_synth_hash.py). */
 int ll_synth_hash(float* out, long long lo, long long n, unsigned long long stream_const, int kind, ll_stream stream);
 
-/* ---- VAE decoder (wan/modules/vae.py, utils/wan_wrapper.py:83-116) ------------------- */
+/* ---- VAE decoder and encoder (wan/modules/vae.py, utils/wan_wrapper.py:80-116) ------- */
 
 /* CausalConv3d 3x3x3 / (3,1,1) / 1x1x1 and Conv2d 3x3 / 1x1 (wan/modules/vae.py:17-36; the Upsample + Conv2d pair of
  * Resample, vae.py:74-84, with upsample=1) as one implicit GEMM on channels-last activations:
@@ -469,6 +470,38 @@ int ll_vae_unscale_cl(const ll_bf16* z, const ll_bf16* mean, const ll_bf16* inv_
 /* Decoder output: channels-last bf16 [T,H,W,ldc] (first 3 channels) -> fp32 [T,3,H,W] clamped to [-1,1]
  * (wan/modules/vae.py decode's clamp_ + utils/wan_wrapper.py:112-116). */
 int ll_cl_to_tchw_clamp(const ll_bf16* x, float* out, int T, int H, int W, int ldc, ll_stream stream);
+
+/* -- encoder (Encoder3d + conv1, wan/modules/vae.py:265-366, 517-543): every stride-1 convolution runs on ll_conv_cl; the two
+ * strided gathers below are further gather modes of the same implicit GEMM (same LDS staging, swizzle and epilogue). -- */
+
+/* Resample 'downsample2d' / 'downsample3d' (vae.py:87-94, 139-141): ZeroPad2d((0,1,0,1)) + Conv2d(Cin, Cout, 3, stride 2) per frame:
+ *   out[t,ho,wo,co] = bias[co] + sum_{kh,kw,ci} x[t, 2ho+kh, 2wo+kw, ci] * w[co,(kh,kw),ci],  Ho = H / 2, Wo = W / 2 (H, W >= 2),
+ * taps with 2ho+kh >= H or 2wo+kw >= W read zero (pad on the right and bottom only; never read when H / W is odd).  x [T,H,W,Cin],
+ * w [Cout, Kpad] in ll_conv_cl's layout (KT = 1, KH = 3), out rows of ldo elements (ldo >= Cout, ldo % 4 == 0), Cin % 8 == 0,
+ * Cout % 8 == 0.  Reads stay inside the T frames; columns >= Cout and rows beyond the last pixel are never written. */
+int ll_conv_cl_down(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, int T, int H, int W,
+                    int Cin, int Cout, int Kpad, int ldo, ll_stream stream);
+/* Resample 'downsample3d' time_conv = CausalConv3d(C, C, (3,1,1), stride (2,1,1), padding 0) over [cached last frame | chunk]
+ * (vae.py:95-96, 151-158):  out[j,p,co] = bias[co] + sum_{kt,ci} x[2j+kt-1, p, ci] * w[co,kt,ci] for j < T / 2, T even.
+ * x points at the first of T new frames; the ONE frame before it in memory is the stream's previous frame (feat_cache[idx][:, :, -1:]).
+ * No zero padding in time; frames before x - 1 frame are never read.  w [Cout, Kpad] with KT = 3, KH = 1. */
+int ll_conv_cl_tdown(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, int T, int H, int W,
+                     int Cin, int Cout, int Kpad, int ldo, ll_stream stream);
+/* Host only: kernel instance, tile, grid and k-steps of ll_conv_cl_down (kind 0) / ll_conv_cl_tdown (kind 1) as text, from the plan
+ * the launcher dispatches on.  Shapes the entry points reject are rejected here. */
+int ll_conv_down_plan(int kind, int T, int H, int W, int Cin, int Cout, char* out, int cap);
+
+/* Encoder input: pixels [3,T,H,W] or [T,3,H,W] (element strides stride_c / stride_t, rows of a frame contiguous), fp32 (is_f32 = 1,
+ * rounded to bf16 once: the pixel.to(bf16) of the reference's callers) or bf16 -> channels-last bf16 [T,H,W,Cpad], channels >= 3 zero;
+ * Cpad in {8, 16, 32}.  encoder.conv1 (vae.py:288, 3 -> 96) then runs on ll_conv_cl with zero-padded weights. */
+int ll_pixels_to_cl(const void* px, int is_f32, long long stride_c, long long stride_t, ll_bf16* out, int T, int H, int W, int Cpad,
+                    ll_stream stream);
+
+/* Latent scaling of WanVAE_.encode (vae.py:537-539) with scale = [bf16(mean), bf16(1 / bf16(std))] (utils/wan_wrapper.py:83-84), the
+ * layout change and .float() (wan_wrapper.py:87): channels-last mu [T,h,w,ld] (first z_dim channels) -> fp32 [T,z_dim,h,w] =
+ * float(bf16(bf16(mu - mean) * inv_std)). */
+int ll_vae_scale_tchw(const ll_bf16* mu, const ll_bf16* mean, const ll_bf16* inv_std, float* out, int T, int z_dim, int h, int w, int ld,
+                      ll_stream stream);
 
 /* ---- umT5 text encoder (wan/modules/t5.py, utils/wan_wrapper.py:16-57) ----------------- */
 

@@ -32,6 +32,11 @@ struct ConvGeo {
 // waves of a SIMD, was what bounded the first version of this kernel (profiles/r01_vae_kernels.md).
 // MODE 2 adds the nearest x2 upsample: source row (ho + kh - 1) >> 1 = base + ((kh + parity) >> 1).
 // MODE 0: generic per-lane decode for Cin < 64 (conv2, decoder.conv1: 16 input channels, < 0.1 % of the FLOPs).
+// MODE 3 / 4 (encoder, Cin >= 64): MODE 1's staging with another row base.  MODE 3 = ZeroPad2d((0,1,0,1)) + Conv2d(3, stride 2)
+// (Resample 'downsample2d/3d', vae.py:87-94): base at input pixel (2ho, 2wo), mask bit = tap left of / above the right / bottom
+// edge; consecutive rows of a tile are 2 Cin apart, so a K-step's DMA reads every other Cin-wide run of an image row.  MODE 4 = the
+// (3,1,1) stride-(2,1,1) time_conv (vae.py:95-96, 156-157): base at frame 2j - 1, every tap valid.  MODE 5 / 6: the same two
+// gathers on MODE 0's per-lane decode for Cin < 64.
 template <int MODE>
 struct ConvRows {
   const char* ptr[4];   // MODE 1/2: address of the (kt, kh, kw) = (0, 0, 0) tap of each row's pixel, channel 0
@@ -52,6 +57,23 @@ __device__ __forceinline__ void conv_rows_init(ConvRows<MODE>& R, const ConvGeo&
     int h = rem / g.Wo;
     int w = rem - h * g.Wo;
     R.rt[i] = t; R.rh[i] = h; R.rw[i] = w;
+    if (MODE == 3 || MODE == 6) {       // stride-2 spatial gather: (h, w) is an OUTPUT pixel, its taps start at input pixel (2h, 2w)
+      unsigned mk = 0;
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) mk |= (2 * h + kh < g.H && 2 * w + kw < g.W) ? 1u << (kh * 3 + kw) : 0u;   // pad: right / bottom only
+      R.ptr[i] = g.x + (long long)t * fb + ((long long)(2 * h) * g.W + 2 * w) * g.Cin * 2;
+      R.mask[i] = mk;
+      R.rh[i] = 2 * h + 1; R.rw[i] = 2 * w + 1;     // MODE 6 decodes hy = rh + kh - 1
+      continue;
+    }
+    if (MODE == 4 || MODE == 5) {       // stride-2 temporal gather: output frame t reads input frames 2t - 1 .. 2t + 1, no padding
+      R.ptr[i] = g.x + (long long)(2 * t - 1) * fb + ((long long)h * g.W + w) * g.Cin * 2;
+      R.mask[i] = 1u;
+      R.rt[i] = 2 * t + 1;                          // MODE 5 decodes ti = rt + kt - 2
+      continue;
+    }
     unsigned mk = 0;
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh)
@@ -89,8 +111,9 @@ template <int MODE>
 __device__ __forceinline__ void stage_conv_rows(const ConvRows<MODE>& R, const ConvGeo& g, int kstep, char* lds, int wave,
                                                 int lane) {
   const int c = (lane & 7) ^ ((lane >> 3) & 7);
-  if (MODE == 0) {
+  if (MODE == 0 || MODE == 5 || MODE == 6) {
     const int pad = g.KH >> 1;
+    const int bh = MODE == 6 ? g.H : g.Ho, bw = MODE == 6 ? g.W : g.Wo;      // MODE 6 walks INPUT coordinates
     const long long fb = (long long)g.H * g.W * g.Cin * 2;
     int gch = kstep * 8 + c;
     int tap = (int)(((unsigned)gch * g.inv_cpt) >> 16);
@@ -103,7 +126,7 @@ __device__ __forceinline__ void stage_conv_rows(const ConvRows<MODE>& R, const C
       int inst = wave * 4 + i;
       int ti = R.rt[i] + kt - (g.KT - 1);
       int hy = R.rh[i] + kh - pad, wx = R.rw[i] + kw - pad;
-      bool ok = gch < g.nchunks && hy >= 0 && hy < g.Ho && wx >= 0 && wx < g.Wo;
+      bool ok = gch < g.nchunks && hy >= 0 && hy < bh && wx >= 0 && wx < bw;
       if (g.up) { hy >>= 1; wx >>= 1; }
       const char* src = g.x + (long long)ti * fb + ((long long)(hy * g.W + wx) * g.Cin + ci8 * 8) * 2;
       src = ok ? src : g.zero;
@@ -119,7 +142,7 @@ __device__ __forceinline__ void stage_conv_rows(const ConvRows<MODE>& R, const C
     bool inB = c >= split;
     int ci8 = inB ? c - split : ciA + c;
     int idx = inB ? B.idx : A.idx;
-    if (MODE == 1) {
+    if (MODE != 2) {
       unsigned off = (unsigned)((inB ? B.off : A.off) + ci8 * 16);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -618,6 +641,43 @@ __global__ __launch_bounds__(256) void cl_to_tchw_clamp_kernel(const bf16* __res
   }
 }
 
+// Encoder input: pixels [3, T, H, W] or [T, 3, H, W] (element strides sc, st; rows contiguous), fp32 or bf16 -> channels-last bf16
+// [T, H, W, CPAD], channels >= 3 zero; fp32 is rounded to bf16 once (the `pixel.to(bf16)` of the reference's callers).
+template <typename TI, int CPAD>
+__global__ __launch_bounds__(256) void pixels_to_cl_kernel(const TI* __restrict__ px, bf16* __restrict__ out, long long sc, long long st,
+                                                           long long hw, long long total) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;      // output pixel
+  if (i >= total) return;
+  long long t = i / hw, p = i - t * hw;
+  const TI* s = px + t * st + p;
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (bf16)0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = (bf16)(float)s[c * sc];
+  bf16x8 z;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) z[j] = (bf16)0.f;
+  bf16x8* o = reinterpret_cast<bf16x8*>(out + i * CPAD);
+  o[0] = v;
+#pragma unroll
+  for (int q = 1; q < CPAD / 8; ++q) o[q] = z;
+}
+
+// Latent scaling of WanVAE_.encode (vae.py:537-539) under bf16 + the layout change + .float() (utils/wan_wrapper.py:87):
+// channels-last mu [T, h, w, ld] (first C channels) -> fp32 [T, C, h, w] = float(bf16(bf16(mu - mean) * inv_std)).
+__global__ __launch_bounds__(256) void vae_scale_tchw_kernel(const bf16* __restrict__ mu, const bf16* __restrict__ mean,
+                                                             const bf16* __restrict__ inv_std, float* __restrict__ out, int C,
+                                                             long long hw, long long total, int ld) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;      // index into out
+  if (i >= total) return;
+  long long p = i % hw, tc = i / hw;
+  int c = (int)(tc % C);
+  long long t = tc / C;
+  float v = (float)mu[(t * hw + p) * ld + c];
+  out[i] = rbf(rbf(v - (float)mean[c]) * (float)inv_std[c]);
+}
+
 // ===============================================================================================================
 static int g_conv_halo = 1;       // tuning key conv_halo: 0 = always the implicit-GEMM kernel
 void ll_set_conv_halo_internal(int v) { g_conv_halo = v; }
@@ -859,4 +919,123 @@ extern "C" int ll_cl_to_tchw_clamp(const ll_bf16* x, float* out, int T, int H, i
   hipLaunchKernelGGL(cl_to_tchw_clamp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)x, out, ppf, total, ldc);
   return ll_check_launch("ll_cl_to_tchw_clamp");
+}
+
+// ---- encoder: strided gathers (Resample 'downsample2d' / 'downsample3d', wan/modules/vae.py:87-96, 143-159) -------------------
+// kind 0 = ll_conv_cl_down, 1 = ll_conv_cl_tdown.  The one place that decides instance, tile and grid (ll_conv_down_plan prints it;
+// the launcher dispatches on it).
+struct ConvDownPlan {
+  int To, Ho, Wo, M, taps, KT, KH;
+  int nt, mode, nk, ntm, ntn;
+};
+
+static const char* conv_down_name(int kind) { return kind ? "ll_conv_cl_tdown" : "ll_conv_cl_down"; }
+
+static int conv_down_check(int kind, int T, int H, int W, int Cin, int Cout) {
+  const char* nm = conv_down_name(kind);
+  LL_REQUIRE(kind == 0 || kind == 1, "ll_conv_down_plan: kind=%d must be 0 (spatial) or 1 (temporal)", kind);
+  LL_REQUIRE(Cin > 0 && Cin % 8 == 0, "%s: Cin=%d must be a multiple of 8", nm, Cin);
+  LL_REQUIRE(Cout > 0 && Cout % 8 == 0, "%s: Cout=%d must be a multiple of 8 (pad the weights)", nm, Cout);
+  LL_REQUIRE(T > 0 && H > 0 && W > 0, "%s: empty input %d x %d x %d", nm, T, H, W);
+  if (kind == 0) LL_REQUIRE(H >= 2 && W >= 2, "ll_conv_cl_down: H=%d, W=%d must both be >= 2 (Ho = H / 2, Wo = W / 2)", H, W);
+  else LL_REQUIRE(T % 2 == 0, "ll_conv_cl_tdown: T=%d input frames must be even (two per output frame, one history frame before them)", T);
+  LL_REQUIRE((kind ? 3 : 9) * (Cin / 8) < 4096, "%s: K too large for the chunk decoder", nm);
+  const long long fb = (long long)H * W * Cin * 2;
+  LL_REQUIRE(3 * fb + 4ll * (W + 2) * Cin < (1ll << 31), "%s: frame of %lld bytes too large for 32-bit tap offsets", nm, fb);
+  const long long Mll = kind ? (long long)(T / 2) * H * W : (long long)T * (H / 2) * (W / 2);
+  LL_REQUIRE(Mll > 0 && Mll < (1ll << 31), "%s: too many output pixels", nm);
+  return LL_OK;
+}
+
+static ConvDownPlan conv_down_plan(int kind, int T, int H, int W, int Cin, int Cout) {
+  ConvDownPlan p{};
+  p.To = kind ? T / 2 : T, p.Ho = kind ? H : H / 2, p.Wo = kind ? W : W / 2;
+  p.M = p.To * p.Ho * p.Wo;
+  p.KT = kind ? 3 : 1, p.KH = kind ? 1 : 3, p.taps = kind ? 3 : 9;
+  const bool nt3 = (Cout % 96 == 0) && (Cout % 128 != 0), nt1 = Cout <= 32;      // conv_plan's n-tiling
+  p.nt = nt1 ? 1 : nt3 ? 3 : 4;
+  p.mode = kind ? (Cin < 64 ? 5 : 4) : (Cin < 64 ? 6 : 3);
+  p.nk = (p.taps * Cin + 63) / 64;
+  p.ntm = (p.M + CV_BM - 1) / CV_BM, p.ntn = (Cout + 32 * p.nt - 1) / (32 * p.nt);
+  return p;
+}
+
+extern "C" int ll_conv_down_plan(int kind, int T, int H, int W, int Cin, int Cout, char* out, int cap) {
+  LL_REQUIRE(out != nullptr && cap > 0, "ll_conv_down_plan: needs an output buffer");
+  if (int rc = conv_down_check(kind, T, H, W, Cin, Cout)) return rc;
+  const ConvDownPlan p = conv_down_plan(kind, T, H, W, Cin, Cout);
+  snprintf(out, (size_t)cap, "conv_cl_kernel<bias, NT %d, MODE %d> %s %dx%dx%d -> %dx%dx%d, tile %dx%d, %d workgroups (%d m-tiles x %d n-tiles), %d k-steps",
+           p.nt, p.mode, kind ? "tdown" : "down", T, H, W, p.To, p.Ho, p.Wo, CV_BM, 32 * p.nt, p.ntm * p.ntn, p.ntm, p.ntn, p.nk);
+  return LL_OK;
+}
+
+static int conv_down_launch(int kind, const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out,
+                            int T, int H, int W, int Cin, int Cout, int Kpad, int ldo, ll_stream stream) {
+  const char* nm = conv_down_name(kind);
+  LL_REQUIRE(x && zero16 && w && bias && out, "%s: null operand", nm);
+  if (int rc = conv_down_check(kind, T, H, W, Cin, Cout)) return rc;
+  const ConvDownPlan p = conv_down_plan(kind, T, H, W, Cin, Cout);
+  const int nchunks = p.taps * (Cin / 8);
+  LL_REQUIRE(Kpad % 64 == 0 && Kpad >= nchunks * 8 && Kpad < nchunks * 8 + 64, "%s: Kpad=%d does not match taps*Cin=%d", nm, Kpad, nchunks * 8);
+  LL_REQUIRE(ldo >= Cout && ldo % 4 == 0, "%s: ldo=%d must be >= Cout and a multiple of 4", nm, ldo);
+  ConvGeo g;
+  g.x = (const char*)x; g.zero = (const char*)zero16;
+  g.T = T; g.H = H; g.W = W; g.Cin = Cin; g.Ho = p.Ho; g.Wo = p.Wo; g.KT = p.KT; g.KH = p.KH; g.up = 0;
+  g.cpt = Cin / 8; g.nchunks = nchunks; g.taps = p.taps; g.inv_cpt = (65536u + g.cpt - 1) / g.cpt;
+  EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid(p.ntm * p.ntn), block(512);
+  const size_t lds = 3 * CV_STAGE;
+#define CVD_LAUNCH(NTV, MD)                                                                                            \
+  do {                                                                                                                 \
+    (void)ll_lds_attr((const void*)conv_cl_kernel<LL_EPI_BIAS, NTV, MD>, (int)lds);                                    \
+    hipLaunchKernelGGL((conv_cl_kernel<LL_EPI_BIAS, NTV, MD>), grid, block, lds, s, g, (const char*)w, (bf16*)out, p.M, Cout, p.nk, \
+                       (size_t)Kpad * 2, ldo, p.ntm, p.ntn, ea);                                                       \
+  } while (0)
+#define CVD_MODES(NTV)                                                                                                 \
+  do {                                                                                                                 \
+    if (p.mode == 3) CVD_LAUNCH(NTV, 3); else if (p.mode == 4) CVD_LAUNCH(NTV, 4);                                     \
+    else if (p.mode == 5) CVD_LAUNCH(NTV, 5); else CVD_LAUNCH(NTV, 6);                                                 \
+  } while (0)
+  if (p.nt == 1) CVD_MODES(1); else if (p.nt == 3) CVD_MODES(3); else CVD_MODES(4);
+#undef CVD_MODES
+#undef CVD_LAUNCH
+  return ll_check_launch(nm);
+}
+
+extern "C" int ll_conv_cl_down(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, int T,
+                               int H, int W, int Cin, int Cout, int Kpad, int ldo, ll_stream stream) {
+  return conv_down_launch(0, x, zero16, w, bias, out, T, H, W, Cin, Cout, Kpad, ldo, stream);
+}
+
+extern "C" int ll_conv_cl_tdown(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, int T,
+                                int H, int W, int Cin, int Cout, int Kpad, int ldo, ll_stream stream) {
+  return conv_down_launch(1, x, zero16, w, bias, out, T, H, W, Cin, Cout, Kpad, ldo, stream);
+}
+
+extern "C" int ll_pixels_to_cl(const void* px, int is_f32, long long stride_c, long long stride_t, ll_bf16* out, int T, int H, int W,
+                               int Cpad, ll_stream stream) {
+  LL_REQUIRE(px != nullptr && out != nullptr, "ll_pixels_to_cl: null operand");
+  LL_REQUIRE(Cpad == 8 || Cpad == 16 || Cpad == 32, "ll_pixels_to_cl: Cpad=%d must be 8, 16 or 32", Cpad);
+  LL_REQUIRE(T > 0 && H > 0 && W > 0, "ll_pixels_to_cl: empty input %d x %d x %d", T, H, W);
+  const long long hw = (long long)H * W, total = hw * T;
+  LL_REQUIRE(stride_c >= hw && stride_t >= hw, "ll_pixels_to_cl: strides c=%lld t=%lld must each span a %d x %d frame", stride_c, stride_t, H, W);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define PX_LAUNCH(TI, CP) hipLaunchKernelGGL((pixels_to_cl_kernel<TI, CP>), grid, block, 0, s, (const TI*)px, (bf16*)out, stride_c, stride_t, hw, total)
+  if (is_f32) { if (Cpad == 8) PX_LAUNCH(float, 8); else if (Cpad == 16) PX_LAUNCH(float, 16); else PX_LAUNCH(float, 32); }
+  else { if (Cpad == 8) PX_LAUNCH(bf16, 8); else if (Cpad == 16) PX_LAUNCH(bf16, 16); else PX_LAUNCH(bf16, 32); }
+#undef PX_LAUNCH
+  return ll_check_launch("ll_pixels_to_cl");
+}
+
+extern "C" int ll_vae_scale_tchw(const ll_bf16* mu, const ll_bf16* mean, const ll_bf16* inv_std, float* out, int T, int z_dim, int h,
+                                 int w, int ld, ll_stream stream) {
+  LL_REQUIRE(mu && mean && inv_std && out, "ll_vae_scale_tchw: null operand");
+  LL_REQUIRE(z_dim > 0 && ld >= z_dim, "ll_vae_scale_tchw: need 0 < z_dim=%d <= ld=%d", z_dim, ld);
+  LL_REQUIRE(T > 0 && h > 0 && w > 0, "ll_vae_scale_tchw: empty input %d x %d x %d", T, h, w);
+  const long long hw = (long long)h * w, total = hw * T * z_dim;
+  hipLaunchKernelGGL(vae_scale_tchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16*)mu, (const bf16*)mean, (const bf16*)inv_std, out, z_dim, hw, total, ld);
+  return ll_check_launch("ll_vae_scale_tchw");
 }

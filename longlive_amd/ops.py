@@ -662,6 +662,96 @@ def cl_to_tchw_clamp(x):
     return out
 
 
+# ---- VAE encoder: strided gathers, pixel intake, latent scaling ------------------------------------------------------
+def _conv_down(kind: int, x, packed, bias, geo, out):
+    cin, cout, kpad, kt, kh = geo
+    name = "conv_cl_tdown" if kind else "conv_cl_down"
+    _chk(x, "x"); _chk(packed, "w"); _chk(bias, "bias")
+    assert (kt, kh) == ((3, 1) if kind else (1, 3)), f"{name}: weights are {kt}x{kh}x{kh}"
+    hist = 1 if kind else 0
+    T, H, W, C = x.shape[0] - hist, x.shape[1], x.shape[2], x.shape[3]
+    assert T >= 1, f"{name}: takes [1 + T, H, W, Cin] (the stream's previous frame first)"
+    assert C == cin, f"{name}: input has {C} channels, weights expect {cin}"
+    assert packed.shape == (cout, kpad) and bias.numel() == cout
+    To, Ho, Wo = (T // 2, H, W) if kind else (T, H // 2, W // 2)
+    if out is None:
+        out = torch.empty(To, Ho, Wo, cout, dtype=bf16, device=x.device)
+    _chk(out, "out")
+    assert out.shape[:3] == (To, Ho, Wo) and out.shape[3] >= cout, f"{name}: out {tuple(out.shape)} for {(To, Ho, Wo, cout)}"
+    lib = _lib.load()
+    fn = lib.ll_conv_cl_tdown if kind else lib.ll_conv_cl_down
+    t0 = timer.begin(name) if timer is not None else None
+    _lib.check(fn(x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(), out.data_ptr(), T, H, W, cin,
+                  cout, kpad, out.shape[3], _stream()), "ll_" + name)
+    if timer is not None:
+        timer.end(name, t0, 2.0 * To * Ho * Wo * cout * (kt * kh * kh * cin))
+    return out
+
+
+def conv_cl_down(x, packed, bias, geo, out=None):
+    """ZeroPad2d((0,1,0,1)) + Conv2d(3, stride 2) per frame (Resample 'downsample2d/3d', vae.py:87-94): x [T, H, W, Cin] ->
+    [T, H // 2, W // 2, Cout]; `out` may have rows wider than Cout (columns >= Cout are left alone)."""
+    return _conv_down(0, x, packed, bias, geo, out)
+
+
+def conv_cl_tdown(x, packed, bias, geo, out=None):
+    """The (3,1,1) stride-(2,1,1) time_conv of 'downsample3d' (vae.py:95-96, 156-157): x [1 + T, H, W, Cin] -- the stream's previous
+    frame, then T (even) new ones -> [T // 2, H, W, Cout]."""
+    return _conv_down(1, x, packed, bias, geo, out)
+
+
+def conv_down_plan(kind: int, T: int, H: int, W: int, cin: int, cout: int) -> str:
+    """Kernel instance, tile, grid and k-steps conv_cl_down (kind 0) / conv_cl_tdown (kind 1) launch for this shape (host only)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().ll_conv_down_plan(kind, T, H, W, cin, cout, buf, 256), "ll_conv_down_plan")
+    return buf.value.decode()
+
+
+def conv_plan(T: int, H: int, W: int, geo, upsample: bool = False, res: bool = False, rms: bool = False) -> str:
+    """ll_conv_plan's text for a pack_conv_weight geometry."""
+    import ctypes
+    cin, cout, kpad, kt, kh = geo
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().ll_conv_plan(T, H, W, cin, cout, kt, kh, 1 if upsample else 0, 1 if res else 0, 1 if rms else 0, buf, 256),
+               "ll_conv_plan")
+    return buf.value.decode()
+
+
+def pixels_to_cl(px, channel_dim: int, cpad: int = 8, out=None):
+    """Pixels [3, T, H, W] (channel_dim 0) or [T, 3, H, W] (channel_dim 1), fp32 or bf16, any view whose frames are contiguous ->
+    channels-last bf16 [T, H, W, cpad], channels >= 3 zero; fp32 is rounded to bf16 once."""
+    if not px.is_cuda:
+        raise RuntimeError("pixels: expected a device tensor (longlive_amd has no CPU path)")
+    if px.dtype not in (torch.float32, bf16):
+        raise RuntimeError(f"pixels: expected float32 or bfloat16, got {px.dtype}")
+    assert channel_dim in (0, 1) and px.dim() == 4 and px.shape[channel_dim] == 3, f"pixels: {tuple(px.shape)}, channel_dim {channel_dim}"
+    T, H, W = px.shape[1 - channel_dim], px.shape[2], px.shape[3]
+    if px.stride(3) != 1 or px.stride(2) != W:
+        px = px.contiguous()
+    if out is None:
+        out = torch.empty(T, H, W, cpad, dtype=bf16, device=px.device)
+    _chk(out, "out")
+    assert out.shape == (T, H, W, cpad)
+    lib = _lib.load()
+    _lib.check(lib.ll_pixels_to_cl(px.data_ptr(), 1 if px.dtype == torch.float32 else 0, px.stride(channel_dim), px.stride(1 - channel_dim),
+                                   out.data_ptr(), T, H, W, cpad, _stream()), "ll_pixels_to_cl")
+    return out
+
+
+def vae_scale_tchw(mu, mean, inv_std):
+    """Channels-last mu [T, h, w, ld] (first z channels) -> fp32 [T, z, h, w] = float(bf16(bf16(mu - mean) * inv_std))."""
+    _chk(mu, "mu"); _chk(mean, "mean"); _chk(inv_std, "inv_std")
+    T, h, w, ld = mu.shape
+    z = mean.numel()
+    assert inv_std.numel() == z and ld >= z
+    out = torch.empty(T, z, h, w, dtype=torch.float32, device=mu.device)
+    lib = _lib.load()
+    _lib.check(lib.ll_vae_scale_tchw(mu.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), out.data_ptr(), T, z, h, w, ld, _stream()),
+               "ll_vae_scale_tchw")
+    return out
+
+
 # ---- umT5 text encoder -----------------------------------------------------------------------------------------------
 def t5_rmsnorm(x, w, eps: float = 1e-6):
     _chk(x, "x"); _chk(w, "w")

@@ -306,6 +306,73 @@ def synth_vae_state_dict(cfg: VaeConfig, seed: int = 0, device="cpu", dtype=torc
     return sd
 
 
+# Wan VAE encoder (wan/modules/vae.py:265-316, 503-505: Encoder3d with z_dim * 2 output channels + conv1; temperal_downsample
+# (False, True, True) = temporal_upsample reversed, vae.py:500)
+def vae_encoder_layout(cfg: VaeConfig):
+    """The encoder's layer list in execution order: ('res', name, cin, cout) | ('attn', name, c) | ('down3d' | 'down2d', name, c).
+    Mirrors Encoder3d.__init__ (vae.py:283-311)."""
+    dims = [cfg.dim * u for u in [1] + list(cfg.dim_mult)]
+    temperal_downsample = tuple(reversed(cfg.temporal_upsample))
+    layers = []
+    idx = 0
+    for i, (cin, cout) in enumerate(zip(dims[:-1], dims[1:])):
+        for _ in range(cfg.num_res_blocks):
+            layers.append(("res", f"encoder.downsamples.{idx}", cin, cout))
+            idx += 1
+            cin = cout
+        if i != len(cfg.dim_mult) - 1:
+            layers.append(("down3d" if temperal_downsample[i] else "down2d", f"encoder.downsamples.{idx}", cout))
+            idx += 1
+    c = dims[-1]
+    layers += [("res", "encoder.middle.0", c, c), ("attn", "encoder.middle.1", c), ("res", "encoder.middle.2", c, c)]
+    return dims, layers
+
+
+def vae_encoder_param_shapes(cfg: VaeConfig) -> Dict[str, Tuple[int, ...]]:
+    dims, layers = vae_encoder_layout(cfg)
+    z2 = 2 * cfg.z_dim
+    sh: Dict[str, Tuple[int, ...]] = {"encoder.conv1.weight": (dims[0], 3, 3, 3, 3), "encoder.conv1.bias": (dims[0],)}
+    for L in layers:
+        kind, name = L[0], L[1]
+        if kind == "res":
+            cin, cout = L[2], L[3]
+            sh[name + ".residual.0.gamma"] = (cin, 1, 1, 1)
+            sh[name + ".residual.2.weight"] = (cout, cin, 3, 3, 3); sh[name + ".residual.2.bias"] = (cout,)
+            sh[name + ".residual.3.gamma"] = (cout, 1, 1, 1)
+            sh[name + ".residual.6.weight"] = (cout, cout, 3, 3, 3); sh[name + ".residual.6.bias"] = (cout,)
+            if cin != cout:
+                sh[name + ".shortcut.weight"] = (cout, cin, 1, 1, 1); sh[name + ".shortcut.bias"] = (cout,)
+        elif kind == "attn":
+            c = L[2]
+            sh[name + ".norm.gamma"] = (c, 1, 1)
+            sh[name + ".to_qkv.weight"] = (3 * c, c, 1, 1); sh[name + ".to_qkv.bias"] = (3 * c,)
+            sh[name + ".proj.weight"] = (c, c, 1, 1); sh[name + ".proj.bias"] = (c,)
+        else:
+            c = L[2]
+            sh[name + ".resample.1.weight"] = (c, c, 3, 3); sh[name + ".resample.1.bias"] = (c,)
+            if kind == "down3d":
+                sh[name + ".time_conv.weight"] = (c, c, 3, 1, 1); sh[name + ".time_conv.bias"] = (c,)
+    sh["encoder.head.0.gamma"] = (dims[-1], 1, 1, 1)
+    sh["encoder.head.2.weight"] = (z2, dims[-1], 3, 3, 3); sh["encoder.head.2.bias"] = (z2,)
+    sh["conv1.weight"] = (z2, z2, 1, 1, 1); sh["conv1.bias"] = (z2,)
+    return sh
+
+
+def synth_vae_encoder_state_dict(cfg: VaeConfig, seed: int = 0, device="cpu", dtype=torch.bfloat16) -> Dict[str, torch.Tensor]:
+    """Random-init encoder weights, by synth_vae_state_dict's recipe (the two dicts share no key: merge them for a whole WanVAE_)."""
+    sd = {}
+    for name, shape in vae_encoder_param_shapes(cfg).items():
+        if name.endswith("gamma"):
+            w = 1.0 + 0.1 * hash_normal(seed, name, shape, device)
+        elif name.endswith(".bias"):
+            w = 0.02 * hash_normal(seed, name, shape, device)
+        else:
+            fan_in = int(math.prod(shape[1:]))
+            w = (hash_uniform(seed, name, shape, device) * 2.0 - 1.0) * math.sqrt(3.0 / fan_in)
+        sd[name] = w.to(dtype)
+    return sd
+
+
 # ---- umT5 text encoder (SURVEY.md section 8f rank 3) ------------------------------------------------------------------
 @dataclass
 class T5Config:
