@@ -344,7 +344,9 @@ int ll_gemm_plan_f8(int M, int N, int K, char* out, int cap);
  *   V^: codes vq [B, H, S32 / 32, 128, 32] + scales vs [B, H, S32 / 32, 128]: per (head, channel d, slots 32 j .. 32 j + 31) the MX rule
  *       over the 32 values V[32 j + i, head, d] (slots >= S read as 0); code position 16 hh + jj of a row holds slot
  *       32 j + (jj & 3) + 8 (jj >> 2) + 4 hh (the order in which the kernel's score registers arrive).
- *   ll_kv_shadow_mx: re-derives K^ rows and V^ blocks of the slots [lo, hi), widened to whole 32-slot blocks.  It follows every write
+ *   ll_kv_shadow_mx: re-derives K^ rows and V^ blocks of the slots [lo, hi), widened to whole 32-slot blocks: blocks lo / 32 ..
+ *       ceil(hi / 32) - 1 of all four arrays are rewritten (padding slots >= S of the last block: zero codes under scale byte 127 in
+ *       K^, zeros in V^'s block), no other byte is touched, lo == hi launches nothing.  It follows every write
  *       of the cache in block_forward (the QKV epilogue's V insert and qk_norm_rope_kv_store's K insert, causal_model.py:264-269,302-311;
  *       ll_kv_roll, :257-260) and any external change of k / v (the pipelines' in-place zero_ before a recache).
  *   ll_flash_attn_mx: ll_flash_attn's self-attention (wan/modules/attention.py:43-197 over the sink/window of causal_model.py:331-360)
@@ -352,6 +354,16 @@ int ll_gemm_plan_f8(int M, int N, int K, char* out, int cap);
  *       s = sum_b 2^(eq + ek) sum q^ k^ in fp32, P^ = e4m3fn(exp2(c s - c m_ref)) with the lazy max (m_ref moves only when a tile's max
  *       exceeds it by more than 8 / c), O = sum P^ V^ / sum P^ written as bf16 (row stride ldo).  Key tiles of 64 slots start at each
  *       range's start rounded down to 32 (adjacent ranges are merged first); slots outside the ranges are masked.  head_dim must be 128.
+ *       Preconditions, each refused with LL_ERR_INVALID_ARG before anything is launched: S32 == S rounded up to 32; both ranges inside
+ *       [0, S), the first non-empty, the second in any position but NOT overlapping the first (shared keys would be counted twice;
+ *       ll_flash_attn refuses overlap alike); scale positive and finite (the tile maximum is taken before the multiplication by
+ *       scale * log2 e); ldq % 8 == 0, ldo % 4 == 0 (a lane stores 4 bf16 at column offsets that are multiples of 4: rows on 8 bytes
+ *       suffice), both >= H * 128.  Padding columns of q and out are neither read nor written.
+ *       Not checkable here: EVERY 32-SLOT BLOCK A TILE STAGES MUST HAVE BEEN DERIVED OR ZEROED.  A tile is two blocks, so the last
+ *       tile of a range may stage a block past its end (for [0, 9360) block 293) whose keys are masked: P^ = 0 there, but the block's
+ *       V^ codes and scale bytes still enter the MFMA, and an e4m3 NaN code (0x7f / 0xff) or an E8M0 NaN byte (0xff) times 0 is NaN.
+ *       Allocate the shadow zero-filled (ops.kv_shadow_mx_alloc does) or refresh it over [0, S) first.  K^ rows of masked slots and
+ *       blocks no tile stages may hold anything.
  *   ll_flash_attn_mx_plan: kernel, tile and grid of an ll_flash_attn_mx call (host only). */
 int ll_kv_shadow_mx(const ll_bf16* k, const ll_bf16* v, uint8_t* kq, uint8_t* ks, uint8_t* vq, uint8_t* vs, int B, int S, int S32, int H,
                     int head_dim, int lo, int hi, ll_stream stream);

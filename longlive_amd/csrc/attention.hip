@@ -736,6 +736,8 @@ extern "C" int ll_flash_attn(const ll_bf16* q, const ll_bf16* k, const ll_bf16* 
   LL_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldk % 8 == 0, "ll_flash_attn: row strides must be multiples of 8 elements");
   LL_REQUIRE(ldq >= H * 128 && ldo >= H * 128 && ldk >= H * 128, "ll_flash_attn: row stride smaller than H*128");
   LL_REQUIRE(seg0_len > 0 && seg1_len >= 0 && seg0_start >= 0 && seg1_start >= 0, "ll_flash_attn: needs a non-empty first key range");
+  LL_REQUIRE(seg1_len == 0 || seg1_start >= seg0_start + seg0_len || seg1_start + seg1_len <= seg0_start, "ll_flash_attn: key ranges "
+             "[%d, +%d) and [%d, +%d) overlap (their shared keys would be counted twice)", seg0_start, seg0_len, seg1_start, seg1_len);
   if (B == 0 || Lq == 0 || H == 0) return LL_OK;
   Segs sg;
   sg.s0 = seg0_start; sg.n0 = seg0_len; sg.s1 = seg1_start; sg.n1 = seg1_len;

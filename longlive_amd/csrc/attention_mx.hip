@@ -355,6 +355,8 @@ static int mx_attn_check_segs(const char* fn, int S, int S32, int s0, int n0, in
              s0, n0, S);
   LL_REQUIRE(n1 >= 0 && (n1 == 0 || (s1 >= 0 && s1 + n1 <= S)), "%s: second key range [%d, +%d) outside the cache of %d slots", fn, s1,
              n1, S);
+  LL_REQUIRE(n1 == 0 || s1 >= s0 + n0 || s1 + n1 <= s0, "%s: key ranges [%d, +%d) and [%d, +%d) overlap (their shared keys would be "
+             "counted twice)", fn, s0, n0, s1, n1);
   return LL_OK;
 }
 
@@ -394,6 +396,8 @@ extern "C" int ll_flash_attn_mx(const ll_bf16* q, const uint8_t* kq, const uint8
   LL_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldq >= H * 128 && ldo >= H * 128, "ll_flash_attn_mx: row strides ldq=%d ldo=%d (>= H*128, "
              "multiples of 8 / 4)", ldq, ldo);
   if (int rc = mx_attn_check_segs("ll_flash_attn_mx", S, S32, seg0_start, seg0_len, seg1_start, seg1_len)) return rc;
+  LL_REQUIRE(scale > 0.f && scale <= 3.0e38f, "ll_flash_attn_mx: scale=%g must be positive and finite (the tile maximum is taken before "
+             "the multiplication by scale * log2 e)", (double)scale);
   if (B == 0 || Lq == 0) return LL_OK;
   const MxSegs sg = mx_segs(seg0_start, seg0_len, seg1_start, seg1_len);
   const dim3 grid((Lq + MXA_NW * 32 - 1) / (MXA_NW * 32), H, B), block(MXA_NW * 64);

@@ -1031,16 +1031,18 @@ gemm_plan_f8, gemm_plan_mx, gemm_plan_mx6, gemm_plan_mx4w6, gemm_plan_mx4 = (
 
 # ---- MXFP8 self-attention over a block-scaled shadow of the KV cache (attention_mx.hip) ------------------------------------------
 def kv_shadow_mx_alloc(cache_k) -> dict:
-    """Uninitialised MX shadow of one layer's cache k (or v) [B, S, H, 128]: K^ codes [B, S32, H, 128] + scales [B, S32, H, 4],
-    V^ codes [B, H, S32 / 32, 128, 32] + scales [B, H, S32 / 32, 128] (include/longlive_hip.h ll_kv_shadow_mx)."""
+    """Zero-filled MX shadow of one layer's cache k (or v) [B, S, H, 128]: K^ codes [B, S32, H, 128] + scales [B, S32, H, 4],
+    V^ codes [B, H, S32 / 32, 128, 32] + scales [B, H, S32 / 32, 128] (include/longlive_hip.h ll_kv_shadow_mx).  Zero, not empty: a
+    key tile stages two 32-slot blocks, and the second may be one no refresh has derived yet; its keys are masked (P^ = 0), but its
+    V^ bytes still enter the MFMA, where a NaN code or scale byte times 0 is NaN (ll_flash_attn_mx's precondition)."""
     _chk(cache_k, "cache_k")
     B, S, H, D = cache_k.shape
     assert D == 128, "the shadow is specialised for head_dim 128"
     S32 = (S + 31) // 32 * 32
     dev = cache_k.device
-    return dict(kq=torch.empty(B, S32, H, D, dtype=fp8, device=dev), ks=torch.empty(B, S32, H, 4, dtype=u8, device=dev),
-                vq=torch.empty(B, H, S32 // 32, D, 32, dtype=fp8, device=dev), vs=torch.empty(B, H, S32 // 32, D, dtype=u8, device=dev),
-                S=S)
+    return dict(kq=torch.zeros(B, S32, H, D, dtype=u8, device=dev).view(fp8), ks=torch.zeros(B, S32, H, 4, dtype=u8, device=dev),
+                vq=torch.zeros(B, H, S32 // 32, D, 32, dtype=u8, device=dev).view(fp8),
+                vs=torch.zeros(B, H, S32 // 32, D, dtype=u8, device=dev), S=S)
 
 
 def kv_shadow_mx(cache_k, cache_v, shadow: dict, lo: int, hi: int, tag: str = "kv_shadow_mx"):

@@ -75,30 +75,43 @@ def deq_v(vq: Tensor, vs: Tensor, dtype=torch.float64) -> Tensor:
     return nat.permute(0, 2, 4, 1, 3).reshape(B, NB * 32, H, D)
 
 
-def merge_segments(segments) -> List[Tuple[int, int]]:
+def merge_segments(segments, merge: bool = True) -> List[Tuple[int, int]]:
     segs = [(int(a), int(b)) for a, b in segments if b > a]
-    if len(segs) == 2 and segs[1][0] == segs[0][1]:
+    if merge and len(segs) == 2 and segs[1][0] == segs[0][1]:
         segs = [(segs[0][0], segs[1][1])]
     return segs
 
 
-def tiles(segments) -> List[Tuple[int, int, int]]:
-    """(base, lo, hi) of every key tile, in the kernel's order: tiles of range [lo, hi) start at lo & ~31, step 64."""
+def tiles(segments, align: int = 32, merge: bool = True, index: bool = False) -> List[Tuple[int, ...]]:
+    """(base, lo, hi) of every key tile, in the kernel's order: tiles of range [lo, hi) start at lo & ~31, step 64.  index: also the
+    range's number.  align / merge exist for tests/test_mx_attn_edges_host.py, which shows what each of them decides."""
     out = []
-    for lo, hi in merge_segments(segments):
-        base = lo & ~31
+    for g, (lo, hi) in enumerate(merge_segments(segments, merge)):
+        base = lo & ~(align - 1)
         while base < hi:
-            out.append((base, lo, hi))
+            out.append((base, lo, hi, g) if index else (base, lo, hi))
             base += KT
     return out
 
 
-def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = None, dtype=torch.float32, rcp: bool = False) -> Tensor:
+def trunc_e4m3(p: Tensor) -> Tensor:
+    """e4m3fn by truncation of non-negative p <= 448 (a wrong rounding mode, for the edge suite's mutation list)."""
+    e = torch.floor(torch.log2(p.double().clamp_min(2.0 ** -40))).clamp_min(-6.0)
+    step = torch.pow(2.0, e - 3)
+    return (torch.floor(p.double() / step) * step).to(p.dtype)
+
+
+def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = None, dtype=torch.float32, rcp: bool = False,
+                 mut=(), perm: torch.Generator = None, hook=None, v_tile=None) -> Tensor:
     """The kernel's arithmetic on dequantised shadows kd, vd [B, S32, H, 128] (deq_k / deq_v): q [B, Lq, H, 128] bf16 -> fp32 O / l
     [B, Lq, H, 128].  dtype: the accumulation type (float32 = the kernel's; float64 to measure the quantisation alone).  rcp: the
-    kernel's normalisation, fp32(O) times the fp32 reciprocal of fp32(l), instead of one division (for data whose sums are exact)."""
+    kernel's normalisation, fp32(O) times the fp32 reciprocal of fp32(l), instead of one division (for data whose sums are exact).
+    The rest serves the edge suite (tests/mx_attn_exact.py) and leaves the scheme alone when unset: mut names deliberate departures
+    from the scheme (each a bug the suite must see), perm permutes the keys of every tile (the sums' order), hook(dict) receives every
+    tile's terms, v_tile(base, idx) supplies a tile's V^ rows [B, H, 64, 128] instead of vd."""
     B, Lq, H, D = q.shape
     S32 = kd.shape[1]
+    mut = {mut} if isinstance(mut, str) else set(mut)
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     c = torch.tensor(scale * LOG2E, dtype=torch.float32).item()
@@ -109,20 +122,40 @@ def mx_attention(q: Tensor, kd: Tensor, vd: Tensor, segments, scale: float = Non
     M = torch.full((B, H, Lq, 1), -math.inf, dtype=torch.float32, device=q.device)
     l = torch.zeros(B, H, Lq, 1, dtype=dtype, device=q.device)
     O = torch.zeros(B, H, Lq, D, dtype=dtype, device=q.device)
-    slot_ids = torch.arange(KT, device=q.device)
-    for base, lo, hi in tiles(segments):
-        idx = (base + slot_ids).clamp(max=S32 - 1)
+    for base, lo, hi, g in tiles(segments, 64 if "base64" in mut else 32, "unmerged" not in mut, index=True):
+        slot_ids = base + torch.arange(KT, device=q.device)
+        if perm is not None:
+            slot_ids = slot_ids[torch.randperm(KT, generator=perm)]
+        idx = slot_ids.clamp(max=S32 - 1)
         s = (qd @ kdh[:, :, idx].transpose(-1, -2)).float()                      # [B, H, Lq, 64] fp32 scores
-        valid = ((base + slot_ids) >= lo) & ((base + slot_ids) < hi)
+        mlo = lo + ("mask:lo%d+" % g in mut) - ("mask:lo%d-" % g in mut)            # "mask:hi1-": range 1's end one slot early
+        mhi = hi + ("mask:hi%d+" % g in mut) - ("mask:hi%d-" % g in mut)
+        valid = (slot_ids >= mlo) & (slot_ids < mhi)
         s = s.masked_fill(~valid, -math.inf)
         tm = s.amax(-1, keepdim=True) * c
-        Mn = torch.where(tm - M > THR, tm, M)
+        if "nonlazy" in mut:
+            Mn = torch.maximum(tm, M)
+        elif "ge" in mut:
+            Mn = torch.where(tm - M >= THR, tm, M)
+        else:
+            Mn = torch.where(tm - M > THR, tm, M)
         alpha = torch.exp2(M - Mn)
         p = torch.exp2(s * c - Mn)
-        ph = p.to(FP8).to(dtype)
+        ph = (trunc_e4m3(p) if "trunc" in mut else p.to(FP8)).to(dtype)
+        if "flush" in mut:
+            ph = torch.where(ph < 2.0 ** -6, torch.zeros_like(ph), ph)
         ph = ph.masked_fill(~valid, 0.0)
-        l = l * alpha.to(dtype) + ph.sum(-1, keepdim=True)
-        O = O * alpha.to(dtype) + ph @ vdh[:, :, idx]
+        vt = vdh[:, :, idx] if v_tile is None else v_tile(base, idx).to(dtype)
+        al, ao = alpha.to(dtype), alpha.to(dtype)
+        if "no_l_rescale" in mut:
+            al = torch.ones_like(al)
+        if "no_o_rescale" in mut:
+            ao = torch.ones_like(ao)
+        if hook is not None:
+            hook(dict(base=base, lo=lo, hi=hi, l_old=l * al, O_old=O * ao, ph=ph, v=vt, M=M, Mn=Mn, valid=valid))
+        rs = p.to(dtype).masked_fill(~valid, 0.0) if "l_unrounded" in mut else ph
+        l = l * al + rs.sum(-1, keepdim=True)
+        O = O * ao + ph @ vt
         M = Mn
     if rcp:
         return (O.float() * (1.0 / l.float())).permute(0, 2, 1, 3)

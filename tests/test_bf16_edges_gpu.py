@@ -650,3 +650,21 @@ def test_attn_production_shapes(geom):
     _tune(attn_asm=0)
     assert _attn_plan(B, Lq, H, ranges[0][1]).startswith("flash_attn_pipe_kernel<8, 1>")
     _attn(case, 1, True, build=built)
+
+
+def test_attn_refuses_overlapping_ranges():
+    """Two ranges that share keys would count them twice: refused before anything is launched (ll_flash_attn_mx has the same rule);
+    ranges that only touch, and a second range before the first, are accepted."""
+    case = E.AttnCase(1, 33, 1, [(0, 64), (100, 28)])
+    q, k, v, _ = case.build(0, DEV)
+    q, k, v = (t.to(bf).contiguous() for t in (q, k, v))
+    out = _nan_bf16(33 + 3, 128)
+    for s0, n0, s1, n1 in ((0, 64, 63, 10), (40, 30, 0, 41), (0, 64, 0, 64), (10, 50, 20, 5)):
+        with pytest.raises(RuntimeError, match="overlap"):
+            _run("ll_flash_attn", q, k, v, out, 1, 33, 1, 128, 128, 128, case.Sk * 128, s0, n0, s1, n1, SCALE)
+    torch.cuda.synchronize()
+    assert _untouched_bf16(out)
+    for s0, n0, s1, n1 in ((0, 64, 64, 10), (100, 28, 0, 64)):
+        _run("ll_flash_attn", q, k, v, out, 1, 33, 1, 128, 128, 128, case.Sk * 128, s0, n0, s1, n1, SCALE)
+    torch.cuda.synchronize()
+    assert _untouched_bf16(out[33:]) and bool(torch.isfinite(out[:33].float()).all())

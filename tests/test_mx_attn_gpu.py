@@ -1,7 +1,8 @@
 """MXFP8 self-attention on the MI355X (flash_attn_mx_kernel, kv_shadow_mx_kernel: v_mfma_scale_f32_32x32x64_f8f6f4), pinned to the
 scheme's restatement (tests/mx_attn_ref.py): shadow bytes bit for bit after an unaligned insert, a roll and an outside zero_; both
 products' lane maps with exact data; the kernel against the restatement on the production grid and its neighbours, with a bound that
-the bf16 kernel fails; the model with and without MX linears against the oracle and the reference's goldens; the switch back to bf16."""
+the bf16 kernel fails; the model with and without MX linears against the oracle and the reference's goldens; the switch back to bf16.
+The tile, range, row and stride edges of both kernels are pinned bit for bit by tests/test_mx_attn_edges_gpu.py."""
 import math
 
 import pytest
