@@ -50,6 +50,25 @@ static inline void set_v_insert(EpiArgs& ea, ll_bf16* cache_v, int N, int L, int
   ea.v_write_start = write_start; ea.v_roped_offset = roped_offset; ea.v_write_len = write_len;
 }
 
+// Host-side argument check of the fused epilogues, shared by every ll_gemm_* entry point that takes one.
+static inline int check_epilogue(const char* fn, int M, int N, int ldo, int epilogue, const void* bias, const void* res,
+                                 const void* e, const void* mod, int nmod, int gate_idx, int rows_per_batch, int frame_len) {
+  LL_REQUIRE(N > 0 && N % 8 == 0, "%s: N=%d must be a positive multiple of 8", fn, N);
+  // the generated epilogues, the LDS-staged HIP epilogues and the split-K reduce kernels store (and load the residual as) 16-byte
+  // vectors at row * ldo + n: rows must start on 16 bytes (the direct HIP epilogue alone stores 8-byte vectors)
+  LL_REQUIRE(ldo >= N && ldo % 8 == 0, "%s: ldo=%d must be >= N and a multiple of 8", fn, ldo);
+  LL_REQUIRE(bias != nullptr, "%s: bias is required", fn);
+  LL_REQUIRE(epilogue >= 0 && epilogue <= 3, "%s: unknown epilogue %d", fn, epilogue);
+  if (epilogue == LL_EPI_BIAS_GATE_RES) {
+    LL_REQUIRE(res && e, "%s: gate-residual epilogue needs res and e (mod may be NULL: e then holds bf16(mod + e))", fn);
+    LL_REQUIRE(frame_len > 0 && rows_per_batch > 0 && rows_per_batch % frame_len == 0 && M % rows_per_batch == 0,
+               "%s: rows_per_batch=%d / frame_len=%d do not tile M=%d", fn, rows_per_batch, frame_len, M);
+    LL_REQUIRE(gate_idx >= 0 && gate_idx < nmod, "%s: gate_idx %d outside nmod %d", fn, gate_idx, nmod);
+  }
+  if (epilogue == LL_EPI_BIAS_RES) LL_REQUIRE(res != nullptr, "%s: residual epilogue needs res", fn);
+  return LL_OK;
+}
+
 template <int Q>
 struct Ty;
 template <>

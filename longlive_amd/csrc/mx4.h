@@ -1,4 +1,4 @@
-// MXFP4 (OCP FP4 E2M1) block quantisation of the W4A6 block linears' weights (gemm_mx4.hip).  One block = 32 consecutive values of a
+// MXFP4 (OCP FP4 E2M1) block quantisation of the W4A6 block linears' weights (gemm_mx_packed.hip).  One block = 32 consecutive values of a
 // row along K.  amax = m 2^p (frexp, m in [0.5, 1)); the block exponent e = p - 3 + (m > 0.75) is the smallest integer with
 // amax <= 6 2^e, clamped to [-127, 127] and stored as the E8M0 byte e + 127 (an all-zero block: byte 127, codes 0).  This is mx6.h's
 // rule with 6 (the largest E2M1 value) in place of 7.5, so no code ever saturates.  Codes: E2M1 of x 2^-e (sign bit 3, 2 exponent bits

@@ -1,5 +1,5 @@
 // MXFP6 (OCP FP6 E2M3) block quantisation shared by the quantiser, the MXFP6-emitting producers and the FFN1 epilogue
-// (gemm_mx6.hip, elementwise.hip).  One block = 32 consecutive values of a row along K.  amax = m 2^p (frexp, m in [0.5, 1)); the
+// (gemm_mx_packed.hip, elementwise.hip).  One block = 32 consecutive values of a row along K.  amax = m 2^p (frexp, m in [0.5, 1)); the
 // block exponent e = p - 3 + (m > 0.9375) is the smallest integer with amax <= 7.5 2^e, clamped to [-127, 127] and stored as the E8M0
 // byte e + 127 (an all-zero block: byte 127, codes 0).  This is mx.h's rule with 7.5 (the largest E2M3 value) in place of 448, so no
 // code ever saturates.  Codes: E2M3 of x 2^-e (sign bit 5, 2 exponent bits of bias 1, 3 mantissa bits; subnormals in steps of 0.125),
