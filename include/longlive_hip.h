@@ -65,9 +65,11 @@ const char* ll_last_error(void);
  *               tiles than CUs run the PERSISTENT form (gemm_asmp_*: one workgroup per CU walks its tiles and stages the next
  *               tile's first pieces under the current epilogue; bit-identical results); default 35; 0 = HIP kernels only
  *   "gemm_variant" / "gemm_variant_wide" (N >= 4096 only)  tile of the HIP kernels (int8, embeddings / head, gemm_asm = 0):
- *               0 = auto (cost model), 2 = 256x128, 3 = 256x256, 5 = 256x192, 6 = 256x224
+ *               0 = auto (cost model), 2 = 256x128 (gemm_kernel_v2, 3-stage ring), 3 = 256x256, 5 = 256x192, 6 = 256x224 (all three
+ *               instances of the two-stage gemm_kernel_v5; ll_gemm_plan names the kernel and tile a shape takes)
  *   "gemm_group_m"  m-tiles per group of the GEMM tile walk (default 4; <= 1: N fastest);  "gemm_lds_epi" 0 / 1 / 2 = HIP epilogues
- *               staged through LDS: none / all but GELU (default) / all
+ *               staged through LDS: none / all but GELU (default) / all (256x256 always keeps the register epilogue: its wave tile's
+ *               LDS image would not fit the ring); any other value is refused (timing-experiment bits need a -DLL_GEMM_DIAG build)
  *   "attn_asm"  1 (default) = the generated attention kernel (flash_attn_asm_kernel) for single key ranges of at least
  *               "attn_asm_min_keys" keys (default 512: self- and cross-attention), 0 = the HIP kernels
  *   "attn_variant"  HIP attention: 0 = plain kernel, 1 = software-pipelined, 2 = + ping-pong wave groups from "attn_pp_min_keys"

@@ -698,31 +698,88 @@ extern "C" int ll_conv_cl_rms_ok(int H, int W, int Cin, int Cout, int KT, int KH
   return (Cout == 96 && conv_halo_takes(H, W, Cin, Cout, KT, KH, upsample)) ? 1 : 0;
 }
 
-// What conv_cl_launch runs for a shape under the current tuning: the one place that decides kernel, template instance, tile and grid
-// (ll_conv_plan prints it; the launcher dispatches on it).
+// ---- the implicit-GEMM half of a convolution call, written once for the decoder (ll_conv_cl) and the encoder (ll_conv_cl_down /
+// ll_conv_cl_tdown): instance, tile and grid of conv_cl_kernel<EPI, nt, mode>, the argument checks both share, and the launch.
+struct ConvGemm {
+  int M, nt, mode, nk, ntm, ntn;
+};
+
+static ConvGemm conv_gemm_plan(int M, int taps, int Cin, int Cout, int mode) {
+  ConvGemm c{};
+  c.M = M, c.mode = mode;
+  const bool nt3 = (Cout % 96 == 0) && (Cout % 128 != 0), nt1 = Cout <= 32;
+  c.nt = nt1 ? 1 : nt3 ? 3 : 4;
+  c.nk = (taps * Cin + 63) / 64;
+  c.ntm = (M + CV_BM - 1) / CV_BM, c.ntn = (Cout + 32 * c.nt - 1) / (32 * c.nt);
+  return c;
+}
+
+// Shape preconditions every entry has; `nm` is the entry's name in the messages.  Each side puts its own conditions between the two.
+static int conv_check_channels(const char* nm, int Cin, int Cout) {
+  LL_REQUIRE(Cin > 0 && Cin % 8 == 0, "%s: Cin=%d must be a multiple of 8", nm, Cin);
+  LL_REQUIRE(Cout > 0 && Cout % 8 == 0, "%s: Cout=%d must be a multiple of 8 (pad the weights)", nm, Cout);
+  return LL_OK;
+}
+static int conv_check_size(const char* nm, int H, int W, int Cin, int taps, long long Mll) {
+  LL_REQUIRE(taps * (Cin / 8) < 4096, "%s: K too large for the chunk decoder", nm);
+  const long long fb = (long long)H * W * Cin * 2;
+  LL_REQUIRE(3 * fb + 4ll * (W + 2) * Cin < (1ll << 31), "%s: frame of %lld bytes too large for 32-bit tap offsets", nm, fb);
+  LL_REQUIRE(Mll > 0 && Mll < (1ll << 31), "%s: too many output pixels", nm);
+  return LL_OK;
+}
+static int conv_check_strides(const char* nm, int taps, int Cin, int Cout, int Kpad, int ldo) {
+  const int nchunks = taps * (Cin / 8);
+  LL_REQUIRE(Kpad % 64 == 0 && Kpad >= nchunks * 8 && Kpad < nchunks * 8 + 64, "%s: Kpad=%d does not match taps*Cin=%d", nm, Kpad, nchunks * 8);
+  LL_REQUIRE(ldo >= Cout && ldo % 4 == 0, "%s: ldo=%d must be >= Cout and a multiple of 4", nm, ldo);
+  return LL_OK;
+}
+
+// the instance of (EPI, nt, mode): the decoder's gathers (modes 0-2) with or without a residual, the encoder's (3-6) without
+typedef void (*conv_cl_kernel_t)(ConvGeo, const char*, bf16*, int, int, int, size_t, int, int, int, EpiArgs);
+template <int E, int NT>
+static conv_cl_kernel_t conv_cl_instance(int mode) {
+  if constexpr (E == LL_EPI_BIAS) {
+    if (mode >= 3) return mode == 3 ? conv_cl_kernel<E, NT, 3> : mode == 4 ? conv_cl_kernel<E, NT, 4> : mode == 5 ? conv_cl_kernel<E, NT, 5> : conv_cl_kernel<E, NT, 6>;
+  }
+  return mode == 0 ? conv_cl_kernel<E, NT, 0> : mode == 1 ? conv_cl_kernel<E, NT, 1> : conv_cl_kernel<E, NT, 2>;
+}
+template <int E>
+static conv_cl_kernel_t conv_cl_instance(int nt, int mode) {
+  return nt == 1 ? conv_cl_instance<E, 1>(mode) : nt == 3 ? conv_cl_instance<E, 3>(mode) : conv_cl_instance<E, 4>(mode);
+}
+
+static void conv_gemm_launch(const ConvGemm& c, const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const EpiArgs& ea, ll_bf16* out,
+                             int T, int H, int W, int Cin, int Cout, int Kpad, int Ho, int Wo, int KT, int KH, int up, int ldo,
+                             hipStream_t s) {
+  ConvGeo g;
+  g.x = (const char*)x; g.zero = (const char*)zero16;
+  g.T = T; g.H = H; g.W = W; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.KT = KT; g.KH = KH; g.up = up;
+  g.cpt = Cin / 8; g.taps = KT * KH * KH; g.nchunks = g.taps * g.cpt; g.inv_cpt = (65536u + g.cpt - 1) / g.cpt;
+  const conv_cl_kernel_t k = ea.res ? conv_cl_instance<LL_EPI_BIAS_RES>(c.nt, c.mode) : conv_cl_instance<LL_EPI_BIAS>(c.nt, c.mode);
+  const size_t lds = 3 * CV_STAGE;
+  (void)ll_lds_attr((const void*)k, (int)lds);
+  hipLaunchKernelGGL(k, dim3(c.ntm * c.ntn), dim3(512), lds, s, g, (const char*)w, (bf16*)out, c.M, Cout, c.nk, (size_t)Kpad * 2, ldo, c.ntm,
+                     c.ntn, ea);
+}
+
+// ---- decoder.  What conv_cl_launch runs for a shape under the current tuning: the one place that decides kernel, template instance,
+// tile and grid (ll_conv_plan prints it; the launcher dispatches on it).
 struct ConvPlan {
   int Ho, Wo, M;
   bool halo;                        // conv_halo_kernel, else conv_cl_kernel
   // conv_halo_kernel<EPI, ncb, up, RMS>
   int ncb, up, tiles_w, tiles_h, ntn_h;
   long long nwg;
-  // conv_cl_kernel<EPI, nt, mode>
-  int nt, mode, nk, ntm, ntn;
+  ConvGemm g;                       // conv_cl_kernel<EPI, nt, mode>
 };
 
 // The shape preconditions of ll_conv_cl / ll_conv_cl_rms / ll_conv_plan.
 static int conv_check_shape(int T, int H, int W, int Cin, int Cout, int KT, int KH, int upsample) {
-  LL_REQUIRE(Cin > 0 && Cin % 8 == 0, "ll_conv_cl: Cin=%d must be a multiple of 8", Cin);
-  LL_REQUIRE(Cout > 0 && Cout % 8 == 0, "ll_conv_cl: Cout=%d must be a multiple of 8 (pad the weights)", Cout);
+  if (int rc = conv_check_channels("ll_conv_cl", Cin, Cout)) return rc;
   LL_REQUIRE((KT == 1 || KT == 3) && (KH == 1 || KH == 3), "ll_conv_cl: taps must be 1 or 3 (got %d x %d x %d)", KT, KH, KH);
   LL_REQUIRE(upsample == 0 || (upsample == 1 && KT == 1 && KH == 3), "ll_conv_cl: upsample is 0, or 1 with a 1x3x3 kernel");
   LL_REQUIRE(T > 0 && H > 0 && W > 0, "ll_conv_cl: empty input %d x %d x %d", T, H, W);
-  LL_REQUIRE(KT * KH * KH * (Cin / 8) < 4096, "ll_conv_cl: K too large for the chunk decoder");
-  const long long fb = (long long)H * W * Cin * 2;
-  LL_REQUIRE(3 * fb + 4ll * (W + 2) * Cin < (1ll << 31), "ll_conv_cl: frame of %lld bytes too large for 32-bit tap offsets", fb);
-  const long long Mll = (long long)T * (upsample ? 2 * H : H) * (upsample ? 2 * W : W);
-  LL_REQUIRE(Mll > 0 && Mll < (1ll << 31), "ll_conv_cl: too many output pixels");
-  return LL_OK;
+  return conv_check_size("ll_conv_cl", H, W, Cin, KT * KH * KH, (long long)T * (upsample ? 2 * H : H) * (upsample ? 2 * W : W));
 }
 
 static ConvPlan conv_plan(int T, int H, int W, int Cin, int Cout, int KT, int KH, int upsample) {
@@ -737,12 +794,7 @@ static ConvPlan conv_plan(int T, int H, int W, int Cin, int Cout, int KT, int KH
   p.tiles_w = (p.Wo + HL_TW - 1) / HL_TW, p.tiles_h = (p.Ho + HL_TH - 1) / HL_TH;
   p.ntn_h = head ? 1 : Cout / 96;
   p.nwg = (long long)T * p.tiles_h * p.tiles_w * p.ntn_h;
-  // implicit GEMM
-  const bool nt3 = (Cout % 96 == 0) && (Cout % 128 != 0), nt1 = Cout <= 32;
-  p.nt = nt1 ? 1 : nt3 ? 3 : 4;
-  p.mode = Cin < 64 ? 0 : upsample ? 2 : 1;
-  p.nk = (KT * KH * KH * Cin + 63) / 64;
-  p.ntm = (p.M + CV_BM - 1) / CV_BM, p.ntn = (Cout + 32 * p.nt - 1) / (32 * p.nt);
+  p.g = conv_gemm_plan(p.M, KT * KH * KH, Cin, Cout, Cin < 64 ? 0 : upsample ? 2 : 1);
   return p;
 }
 
@@ -761,13 +813,55 @@ extern "C" int ll_conv_plan(int T, int H, int W, int Cin, int Cout, int KT, int 
              (p.up ? 3 : 9) * (Cin / 32));
   else
     snprintf(out, (size_t)cap, "conv_cl_kernel<%s, NT %d, MODE %d> tile %dx%d, %d workgroups (%d m-tiles x %d n-tiles), %d k-steps",
-             epi, p.nt, p.mode, CV_BM, 32 * p.nt, p.ntm * p.ntn, p.ntm, p.ntn, p.nk);
+             epi, p.g.nt, p.g.mode, CV_BM, 32 * p.g.nt, p.g.ntm * p.g.ntn, p.g.ntm, p.g.ntn, p.g.nk);
   return LL_OK;
+}
+
+// the halo-tile kernel's instance: <EPI, NCB, UP> (RMS: NCB = 6 with the fused RMS_norm output)
+template <int E, int NCBV, int UPV, bool RMS, class... Extra>
+static void conv_halo_launch_one(const ConvPlan& p, const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, ll_bf16* out, int T, int H,
+                                 int W, int Cin, int Cout, int Kpad, int ldo, const EpiArgs& ea, hipStream_t s, Extra... extra) {
+  (void)ll_lds_attr((const void*)conv_halo_kernel<E, NCBV, UPV, RMS>, (int)HL_LDS(NCBV, UPV));
+  hipLaunchKernelGGL((conv_halo_kernel<E, NCBV, UPV, RMS>), dim3((unsigned)p.nwg), dim3(512), HL_LDS(NCBV, UPV), s, (const char*)x,
+                     (const char*)zero16, (const char*)w, (bf16*)out, T, H, W, Cin, Cout, (size_t)Kpad * 2, ldo, p.tiles_w, p.tiles_h,
+                     p.ntn_h, ea, extra...);
 }
 
 static int conv_cl_launch(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, const ll_bf16* res,
                           ll_bf16* out, int T, int H, int W, int Cin, int Cout, int Kpad, int KT, int KH, int upsample, int ldo,
-                          ll_stream stream, const ll_bf16* rms_gamma, ll_bf16* out_rms, int rms_silu);
+                          ll_stream stream, const ll_bf16* rms_gamma, ll_bf16* out_rms, int rms_silu) {
+  LL_REQUIRE(x && zero16 && w && bias && (out || out_rms), "ll_conv_cl: null operand");
+  if (int rc = conv_check_shape(T, H, W, Cin, Cout, KT, KH, upsample)) return rc;
+  if (int rc = conv_check_strides("ll_conv_cl", KT * KH * KH, Cin, Cout, Kpad, ldo)) return rc;
+  const ConvPlan p = conv_plan(T, H, W, Cin, Cout, KT, KH, upsample);
+  EpiArgs ea{(const bf16*)bias, (const bf16*)res, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
+  hipStream_t s = (hipStream_t)stream;
+  if (p.halo) {
+    LL_REQUIRE(p.nwg < (1ll << 31), "ll_conv_cl: too many tiles");
+#define HL_LAUNCH(E, NCBV, UPV) conv_halo_launch_one<E, NCBV, UPV, false>(p, x, zero16, w, out, T, H, W, Cin, Cout, Kpad, ldo, ea, s)
+#define HL_LAUNCH_RMS(E, UPV)                                                                                                      \
+  conv_halo_launch_one<E, 6, UPV, true>(p, x, zero16, w, out, T, H, W, Cin, Cout, Kpad, ldo, ea, s, (const bf16*)rms_gamma, (bf16*)out_rms, \
+                                        rms_silu, sqrtf((float)Cout))
+    if (rms_gamma != nullptr) {           // Cout == 96: one n-tile holds every channel of a pixel (ll_conv_cl_rms_ok)
+      if (p.up) { if (res) HL_LAUNCH_RMS(LL_EPI_BIAS_RES, 1); else HL_LAUNCH_RMS(LL_EPI_BIAS, 1); }
+      else { if (res) HL_LAUNCH_RMS(LL_EPI_BIAS_RES, 0); else HL_LAUNCH_RMS(LL_EPI_BIAS, 0); }
+      return ll_check_launch("ll_conv_cl_rms(halo)");
+    }
+    if (p.up) {
+      if (res) HL_LAUNCH(LL_EPI_BIAS_RES, 6, 1); else HL_LAUNCH(LL_EPI_BIAS, 6, 1);
+    } else if (p.ncb == 1) {
+      if (res) HL_LAUNCH(LL_EPI_BIAS_RES, 1, 0); else HL_LAUNCH(LL_EPI_BIAS, 1, 0);
+    } else {
+      if (res) HL_LAUNCH(LL_EPI_BIAS_RES, 6, 0); else HL_LAUNCH(LL_EPI_BIAS, 6, 0);
+    }
+#undef HL_LAUNCH_RMS
+#undef HL_LAUNCH
+    return ll_check_launch("ll_conv_cl(halo)");
+  }
+  LL_REQUIRE(rms_gamma == nullptr, "ll_conv_cl_rms: only the halo-tile kernel has the fused RMS_norm epilogue");
+  conv_gemm_launch(p.g, x, zero16, w, ea, out, T, H, W, Cin, Cout, Kpad, p.Ho, p.Wo, KT, KH, upsample, ldo, s);
+  return ll_check_launch("ll_conv_cl");
+}
 
 extern "C" int ll_conv_cl(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, const ll_bf16* res,
                           ll_bf16* out, int T, int H, int W, int Cin, int Cout, int Kpad, int KT, int KH, int upsample,
@@ -784,93 +878,6 @@ extern "C" int ll_conv_cl_rms(const ll_bf16* x, const ll_bf16* zero16, const ll_
              "first and run ll_conv_cl + ll_rms_silu_cl instead)");
   LL_REQUIRE(ldo == Cout, "ll_conv_cl_rms: ldo=%d must equal Cout (both outputs are dense [pixels, Cout])", ldo);
   return conv_cl_launch(x, zero16, w, bias, res, out, T, H, W, Cin, Cout, Kpad, KT, KH, upsample, ldo, stream, rms_gamma, out_rms, rms_silu);
-}
-
-static int conv_cl_launch(const ll_bf16* x, const ll_bf16* zero16, const ll_bf16* w, const ll_bf16* bias, const ll_bf16* res,
-                          ll_bf16* out, int T, int H, int W, int Cin, int Cout, int Kpad, int KT, int KH, int upsample, int ldo,
-                          ll_stream stream, const ll_bf16* rms_gamma, ll_bf16* out_rms, int rms_silu) {
-  LL_REQUIRE(x && zero16 && w && bias && (out || out_rms), "ll_conv_cl: null operand");
-  if (int rc = conv_check_shape(T, H, W, Cin, Cout, KT, KH, upsample)) return rc;
-  const int taps = KT * KH * KH;
-  const int nchunks = taps * (Cin / 8);
-  LL_REQUIRE(Kpad % 64 == 0 && Kpad >= nchunks * 8 && Kpad < nchunks * 8 + 64, "ll_conv_cl: Kpad=%d does not match taps*Cin=%d", Kpad, nchunks * 8);
-  LL_REQUIRE(ldo >= Cout && ldo % 4 == 0, "ll_conv_cl: ldo=%d must be >= Cout and a multiple of 4", ldo);
-  const ConvPlan p = conv_plan(T, H, W, Cin, Cout, KT, KH, upsample);
-  const int Ho = p.Ho, Wo = p.Wo, M = p.M;
-  ConvGeo g;
-  g.x = (const char*)x; g.zero = (const char*)zero16;
-  g.T = T; g.H = H; g.W = W; g.Cin = Cin; g.Ho = Ho; g.Wo = Wo; g.KT = KT; g.KH = KH; g.up = upsample;
-  g.cpt = Cin / 8; g.nchunks = nchunks; g.taps = taps; g.inv_cpt = (65536u + g.cpt - 1) / g.cpt;
-  EpiArgs ea{(const bf16*)bias, (const bf16*)res, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-  hipStream_t s = (hipStream_t)stream;
-  {
-    const bool shape_up = p.up == 1, head = p.ncb == 1;
-    const int tiles_w = p.tiles_w, tiles_h = p.tiles_h;
-    if (p.halo) {
-      const int ntn_h = p.ntn_h;
-      const long long nwg = p.nwg;
-      LL_REQUIRE(nwg < (1ll << 31), "ll_conv_cl: too many tiles");
-      dim3 hgrid((unsigned)nwg), hblock(512);
-#define HL_LAUNCH(E, NCBV, UPV)                                                                                        \
-      do {                                                                                                             \
-        {                                                                                      \
-          (void)ll_lds_attr((const void*)conv_halo_kernel<E, NCBV, UPV>, \
-                                    (int)HL_LDS(NCBV, UPV));                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL((conv_halo_kernel<E, NCBV, UPV>), hgrid, hblock, HL_LDS(NCBV, UPV), s, (const char*)x,      \
-                           (const char*)zero16, (const char*)w, (bf16*)out, T, H, W, Cin, Cout, (size_t)Kpad * 2, ldo,  \
-                           tiles_w, tiles_h, ntn_h, ea);                                                               \
-      } while (0)
-      if (rms_gamma != nullptr) {           // Cout == 96: one n-tile holds every channel of a pixel (ll_conv_cl_rms_ok)
-        const float sqc = sqrtf((float)Cout);
-#define HL_LAUNCH_RMS(E, UPV)                                                                                          \
-        do {                                                                                                           \
-          (void)ll_lds_attr((const void*)conv_halo_kernel<E, 6, UPV, true>, (int)HL_LDS(6, UPV));                      \
-          hipLaunchKernelGGL((conv_halo_kernel<E, 6, UPV, true>), hgrid, hblock, HL_LDS(6, UPV), s, (const char*)x,    \
-                             (const char*)zero16, (const char*)w, (bf16*)out, T, H, W, Cin, Cout, (size_t)Kpad * 2, ldo, \
-                             tiles_w, tiles_h, ntn_h, ea, (const bf16*)rms_gamma, (bf16*)out_rms, rms_silu, sqc);       \
-        } while (0)
-        if (shape_up) { if (res) HL_LAUNCH_RMS(LL_EPI_BIAS_RES, 1); else HL_LAUNCH_RMS(LL_EPI_BIAS, 1); }
-        else { if (res) HL_LAUNCH_RMS(LL_EPI_BIAS_RES, 0); else HL_LAUNCH_RMS(LL_EPI_BIAS, 0); }
-#undef HL_LAUNCH_RMS
-        return ll_check_launch("ll_conv_cl_rms(halo)");
-      }
-      if (shape_up) {
-        if (res) HL_LAUNCH(LL_EPI_BIAS_RES, 6, 1); else HL_LAUNCH(LL_EPI_BIAS, 6, 1);
-      } else if (head) {
-        if (res) HL_LAUNCH(LL_EPI_BIAS_RES, 1, 0); else HL_LAUNCH(LL_EPI_BIAS, 1, 0);
-      } else {
-        if (res) HL_LAUNCH(LL_EPI_BIAS_RES, 6, 0); else HL_LAUNCH(LL_EPI_BIAS, 6, 0);
-      }
-#undef HL_LAUNCH
-      return ll_check_launch("ll_conv_cl(halo)");
-    }
-  }
-  LL_REQUIRE(rms_gamma == nullptr, "ll_conv_cl_rms: only the halo-tile kernel has the fused RMS_norm epilogue");
-  const int nk = p.nk, mode = p.mode, ntm = p.ntm, ntn = p.ntn;
-  const bool nt3 = p.nt == 3, nt1 = p.nt == 1;
-  dim3 grid(ntm * ntn), block(512);
-  size_t lds = 3 * CV_STAGE;
-#define CV_LAUNCH(E, NTV, MD)                                                                                          \
-  do {                                                                                                                 \
-    {                                                                                          \
-      (void)ll_lds_attr((const void*)conv_cl_kernel<E, NTV, MD>, (int)lds); \
-    }                                                                                                                  \
-    hipLaunchKernelGGL((conv_cl_kernel<E, NTV, MD>), grid, block, lds, s, g, (const char*)w, (bf16*)out, M, Cout, nk,   \
-                       (size_t)Kpad * 2, ldo, ntm, ntn, ea);                                                           \
-  } while (0)
-#define CV_MODES(E, NTV)                                                                                               \
-  do {                                                                                                                 \
-    if (mode == 0) CV_LAUNCH(E, NTV, 0); else if (mode == 1) CV_LAUNCH(E, NTV, 1); else CV_LAUNCH(E, NTV, 2);          \
-  } while (0)
-  if (res) {
-    if (nt1) CV_MODES(LL_EPI_BIAS_RES, 1); else if (nt3) CV_MODES(LL_EPI_BIAS_RES, 3); else CV_MODES(LL_EPI_BIAS_RES, 4);
-  } else {
-    if (nt1) CV_MODES(LL_EPI_BIAS, 1); else if (nt3) CV_MODES(LL_EPI_BIAS, 3); else CV_MODES(LL_EPI_BIAS, 4);
-  }
-#undef CV_MODES
-#undef CV_LAUNCH
-  return ll_check_launch("ll_conv_cl");
 }
 
 extern "C" int ll_rms_silu_cl(const ll_bf16* x, const ll_bf16* gamma, ll_bf16* out, long long pixels, int C, int do_silu,
@@ -925,8 +932,8 @@ extern "C" int ll_cl_to_tchw_clamp(const ll_bf16* x, float* out, int T, int H, i
 // kind 0 = ll_conv_cl_down, 1 = ll_conv_cl_tdown.  The one place that decides instance, tile and grid (ll_conv_down_plan prints it;
 // the launcher dispatches on it).
 struct ConvDownPlan {
-  int To, Ho, Wo, M, taps, KT, KH;
-  int nt, mode, nk, ntm, ntn;
+  int To, Ho, Wo, KT, KH;
+  ConvGemm g;
 };
 
 static const char* conv_down_name(int kind) { return kind ? "ll_conv_cl_tdown" : "ll_conv_cl_down"; }
@@ -934,29 +941,18 @@ static const char* conv_down_name(int kind) { return kind ? "ll_conv_cl_tdown" :
 static int conv_down_check(int kind, int T, int H, int W, int Cin, int Cout) {
   const char* nm = conv_down_name(kind);
   LL_REQUIRE(kind == 0 || kind == 1, "ll_conv_down_plan: kind=%d must be 0 (spatial) or 1 (temporal)", kind);
-  LL_REQUIRE(Cin > 0 && Cin % 8 == 0, "%s: Cin=%d must be a multiple of 8", nm, Cin);
-  LL_REQUIRE(Cout > 0 && Cout % 8 == 0, "%s: Cout=%d must be a multiple of 8 (pad the weights)", nm, Cout);
+  if (int rc = conv_check_channels(nm, Cin, Cout)) return rc;
   LL_REQUIRE(T > 0 && H > 0 && W > 0, "%s: empty input %d x %d x %d", nm, T, H, W);
   if (kind == 0) LL_REQUIRE(H >= 2 && W >= 2, "ll_conv_cl_down: H=%d, W=%d must both be >= 2 (Ho = H / 2, Wo = W / 2)", H, W);
   else LL_REQUIRE(T % 2 == 0, "ll_conv_cl_tdown: T=%d input frames must be even (two per output frame, one history frame before them)", T);
-  LL_REQUIRE((kind ? 3 : 9) * (Cin / 8) < 4096, "%s: K too large for the chunk decoder", nm);
-  const long long fb = (long long)H * W * Cin * 2;
-  LL_REQUIRE(3 * fb + 4ll * (W + 2) * Cin < (1ll << 31), "%s: frame of %lld bytes too large for 32-bit tap offsets", nm, fb);
-  const long long Mll = kind ? (long long)(T / 2) * H * W : (long long)T * (H / 2) * (W / 2);
-  LL_REQUIRE(Mll > 0 && Mll < (1ll << 31), "%s: too many output pixels", nm);
-  return LL_OK;
+  return conv_check_size(nm, H, W, Cin, kind ? 3 : 9, kind ? (long long)(T / 2) * H * W : (long long)T * (H / 2) * (W / 2));
 }
 
 static ConvDownPlan conv_down_plan(int kind, int T, int H, int W, int Cin, int Cout) {
   ConvDownPlan p{};
   p.To = kind ? T / 2 : T, p.Ho = kind ? H : H / 2, p.Wo = kind ? W : W / 2;
-  p.M = p.To * p.Ho * p.Wo;
-  p.KT = kind ? 3 : 1, p.KH = kind ? 1 : 3, p.taps = kind ? 3 : 9;
-  const bool nt3 = (Cout % 96 == 0) && (Cout % 128 != 0), nt1 = Cout <= 32;      // conv_plan's n-tiling
-  p.nt = nt1 ? 1 : nt3 ? 3 : 4;
-  p.mode = kind ? (Cin < 64 ? 5 : 4) : (Cin < 64 ? 6 : 3);
-  p.nk = (p.taps * Cin + 63) / 64;
-  p.ntm = (p.M + CV_BM - 1) / CV_BM, p.ntn = (Cout + 32 * p.nt - 1) / (32 * p.nt);
+  p.KT = kind ? 3 : 1, p.KH = kind ? 1 : 3;
+  p.g = conv_gemm_plan(p.To * p.Ho * p.Wo, kind ? 3 : 9, Cin, Cout, kind ? (Cin < 64 ? 5 : 4) : (Cin < 64 ? 6 : 3));
   return p;
 }
 
@@ -965,7 +961,7 @@ extern "C" int ll_conv_down_plan(int kind, int T, int H, int W, int Cin, int Cou
   if (int rc = conv_down_check(kind, T, H, W, Cin, Cout)) return rc;
   const ConvDownPlan p = conv_down_plan(kind, T, H, W, Cin, Cout);
   snprintf(out, (size_t)cap, "conv_cl_kernel<bias, NT %d, MODE %d> %s %dx%dx%d -> %dx%dx%d, tile %dx%d, %d workgroups (%d m-tiles x %d n-tiles), %d k-steps",
-           p.nt, p.mode, kind ? "tdown" : "down", T, H, W, p.To, p.Ho, p.Wo, CV_BM, 32 * p.nt, p.ntm * p.ntn, p.ntm, p.ntn, p.nk);
+           p.g.nt, p.g.mode, kind ? "tdown" : "down", T, H, W, p.To, p.Ho, p.Wo, CV_BM, 32 * p.g.nt, p.g.ntm * p.g.ntn, p.g.ntm, p.g.ntn, p.g.nk);
   return LL_OK;
 }
 
@@ -975,31 +971,9 @@ static int conv_down_launch(int kind, const ll_bf16* x, const ll_bf16* zero16, c
   LL_REQUIRE(x && zero16 && w && bias && out, "%s: null operand", nm);
   if (int rc = conv_down_check(kind, T, H, W, Cin, Cout)) return rc;
   const ConvDownPlan p = conv_down_plan(kind, T, H, W, Cin, Cout);
-  const int nchunks = p.taps * (Cin / 8);
-  LL_REQUIRE(Kpad % 64 == 0 && Kpad >= nchunks * 8 && Kpad < nchunks * 8 + 64, "%s: Kpad=%d does not match taps*Cin=%d", nm, Kpad, nchunks * 8);
-  LL_REQUIRE(ldo >= Cout && ldo % 4 == 0, "%s: ldo=%d must be >= Cout and a multiple of 4", nm, ldo);
-  ConvGeo g;
-  g.x = (const char*)x; g.zero = (const char*)zero16;
-  g.T = T; g.H = H; g.W = W; g.Cin = Cin; g.Ho = p.Ho; g.Wo = p.Wo; g.KT = p.KT; g.KH = p.KH; g.up = 0;
-  g.cpt = Cin / 8; g.nchunks = nchunks; g.taps = p.taps; g.inv_cpt = (65536u + g.cpt - 1) / g.cpt;
+  if (int rc = conv_check_strides(nm, p.KT * p.KH * p.KH, Cin, Cout, Kpad, ldo)) return rc;
   EpiArgs ea{(const bf16*)bias, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(p.ntm * p.ntn), block(512);
-  const size_t lds = 3 * CV_STAGE;
-#define CVD_LAUNCH(NTV, MD)                                                                                            \
-  do {                                                                                                                 \
-    (void)ll_lds_attr((const void*)conv_cl_kernel<LL_EPI_BIAS, NTV, MD>, (int)lds);                                    \
-    hipLaunchKernelGGL((conv_cl_kernel<LL_EPI_BIAS, NTV, MD>), grid, block, lds, s, g, (const char*)w, (bf16*)out, p.M, Cout, p.nk, \
-                       (size_t)Kpad * 2, ldo, p.ntm, p.ntn, ea);                                                       \
-  } while (0)
-#define CVD_MODES(NTV)                                                                                                 \
-  do {                                                                                                                 \
-    if (p.mode == 3) CVD_LAUNCH(NTV, 3); else if (p.mode == 4) CVD_LAUNCH(NTV, 4);                                     \
-    else if (p.mode == 5) CVD_LAUNCH(NTV, 5); else CVD_LAUNCH(NTV, 6);                                                 \
-  } while (0)
-  if (p.nt == 1) CVD_MODES(1); else if (p.nt == 3) CVD_MODES(3); else CVD_MODES(4);
-#undef CVD_MODES
-#undef CVD_LAUNCH
+  conv_gemm_launch(p.g, x, zero16, w, ea, out, T, H, W, Cin, Cout, Kpad, p.Ho, p.Wo, p.KT, p.KH, 0, ldo, (hipStream_t)stream);
   return ll_check_launch(nm);
 }
 

@@ -109,6 +109,14 @@ __device__ __forceinline__ i32x8 frag_f8(const char* __restrict__ base, int r, i
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// MFMA fragment of row r of an LDS stage (the XOR-swizzled 128-byte rows of stage_rows), half step ks of the stage's K: bf16 and
+// int8 take the stage as two half steps of one 16-byte chunk per lane (chunk ks * 4 + fg), fp8 as one step of two (frag_f8).
+template <int Q>
+__device__ __forceinline__ typename Ty<Q>::frag lds_frag(const char* base, int r, int ks, int fg) {
+  if constexpr (Q == GQ_F8) return frag_f8(base, r, fg);
+  else return *reinterpret_cast<const typename Ty<Q>::frag*>(base + r * ROWB + (((ks * 4 + fg) ^ (r & 7)) << 4));
+}
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 

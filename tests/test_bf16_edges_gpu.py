@@ -249,7 +249,7 @@ def test_gemm_hip_tilings_bit_exact(variant, bn, N):
         _tune(gemm_asm=0, gemm_variant=variant)
         for M in (1, 257, 1100):
             plan = _text("ll_gemm_plan", M, N, K, 0)
-            name = {0: "gemm_kernel_v2", 2: "gemm_kernel_v2", 3: "gemm_kernel_v3", 5: "gemm_kernel_v5", 6: "gemm_kernel_v5"}[variant]
+            name = {0: "gemm_kernel_v2", 2: "gemm_kernel_v2", 3: "gemm_kernel_v5", 5: "gemm_kernel_v5", 6: "gemm_kernel_v5"}[variant]
             assert plan.startswith(name) and f"tile 256x{bn}" in plan, plan
             assert _plan_epi(M, N, K, BIAS) == plan
             for lds_epi in (1, 0, 2) if N == 1544 else (1,):
@@ -269,6 +269,29 @@ def test_gemm_hip_tilings_bit_exact(variant, bn, N):
             _tune(gemm_variant=0, gemm_variant_wide=variant, gemm_lds_epi=1)
             assert f"tile 256x{bn}" in _text("ll_gemm_plan", 1100, N, K, 0)
             assert torch.equal(_gemm(D, 1100, BIAS, K + 8, N + 8), D.want[:1100])
+    finally:
+        _tune(**SHIPPED)
+
+
+@pytest.mark.parametrize("variant,bn", [(2, 128), (3, 256), (5, 192), (6, 224)])
+@pytest.mark.parametrize("K", [64, 128])
+def test_gemm_hip_tilings_at_one_and_two_k_steps(variant, bn, K):
+    """gemm_asm 0 with gemm_variant 2 / 3 / 5 / 6 at K = 64 and 128: one and two K-steps, so the rings have no next stage (or exactly
+    one) to issue.  M = 257, N = 200: a partial n-tile in every width, and in the second m-tile only row 256 is live, so most of its
+    waves take the stage-and-sync path.  Bit for bit against the host, with and without LDS-staged epilogues, at contiguous and wide
+    strides."""
+    M, N = 257, 200
+    D = Data.get(M, N, K, gelu=True)
+    try:
+        _tune(gemm_asm=0, gemm_variant=variant)
+        plan = _text("ll_gemm_plan", M, N, K, 0)
+        assert plan.startswith("gemm_kernel_v2" if variant == 2 else "gemm_kernel_v5") and f"tile 256x{bn}" in plan, plan
+        for lds_epi in (1, 0):
+            _tune(gemm_lds_epi=lds_epi)
+            for ldx, ldo in _strides(N, K):
+                for epi in (BIAS, RES, GELU):
+                    got = _gemm(D, M, epi, ldx, ldo)
+                    _check_vs_host(D, M, epi, got, f"v{variant} {M}x{N}x{K} epi {epi} lds_epi {lds_epi} ldx {ldx} ldo {ldo}")
     finally:
         _tune(**SHIPPED)
 

@@ -110,7 +110,7 @@ def test_every_epilogue_and_instance_with_exact_data(ops):
     finally:
         lib.ll_set_tuning(b"gemm_variant", 0)
     assert seen == {"gemm_kernel_v5<f8> tile 256x192", "gemm_kernel_v2<f8> tile 256x128", "gemm_kernel_v5<f8> tile 256x224",
-                    "gemm_kernel_v3<f8> tile 256x256"}, seen
+                    "gemm_kernel_v5<f8> tile 256x256"}, seen
 
 
 def test_qkv_form_writes_q_k_to_out_and_v_to_the_cache_slots(ops):

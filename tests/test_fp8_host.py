@@ -153,6 +153,24 @@ def test_plan_strings_name_the_fp8_instances_at_the_production_shapes():
         assert ops.gemm_plan_f8(4680, N, K).replace("<f8>", "<i8>") == buf.value.decode()
 
 
+def test_forced_256_wide_tiling_is_named_as_the_two_stage_kernel():
+    """gemm_variant 3 (256 x 256) is an instance of gemm_kernel_v5: the plan names the device symbol, for every operand kind."""
+    import ctypes
+    from longlive_amd import ops
+    lib = _lib.load()
+    try:
+        assert lib.ll_set_tuning(b"gemm_variant", 3) == 0
+        buf = ctypes.create_string_buffer(256)
+        plans = [ops.gemm_plan_f8(4680, 4608, 1536)]
+        for int8 in (0, 1):
+            assert lib.ll_gemm_plan(4680, 4608, 1536, int8, buf, 256) == 0
+            plans.append(buf.value.decode())
+        for plan, kind in zip(plans, ("f8", "bf16", "i8")):
+            assert plan.startswith(f"gemm_kernel_v5<{kind}>") and "tile 256x256" in plan, plan
+    finally:
+        assert lib.ll_set_tuning(b"gemm_variant", 0) == 0
+
+
 def test_set_quant_and_cli_key_accept_fp8_rowwise_and_still_refuse_fp8():
     from longlive_amd import cli, synth
     from longlive_amd.model import CausalWanModelHIP

@@ -200,7 +200,7 @@ def test_residual_and_gate_residual_small_frames_ragged_tile(fs, F):
             assert torch.equal(got, epi_tail(v, 2, res, e, md, 4, fs)), f"{fam} fs={fs} mod={md is not None}: gate-residual"
 
 
-TILINGS = {2: "gemm_kernel_v2<{}> tile 256x128", 3: "gemm_kernel_v3<{}> tile 256x256", 5: "gemm_kernel_v5<{}> tile 256x192",
+TILINGS = {2: "gemm_kernel_v2<{}> tile 256x128", 3: "gemm_kernel_v5<{}> tile 256x256", 5: "gemm_kernel_v5<{}> tile 256x192",
            6: "gemm_kernel_v5<{}> tile 256x224"}
 
 
@@ -241,6 +241,30 @@ def test_rowwise_tilings_at_ragged_n(ops, N):
                 got = _gemm(fam, od, bd, epi=2, res=rd, e=ed, mod=md_, gate_idx=1, rpb=F * fs, fl=fs).cpu()
                 assert torch.equal(got, want_gate), f"{fam} v{variant} N={N}: gate-residual"
             _gelu_checks(gel, v, f"v{variant} N={N}")
+    finally:
+        lib.ll_set_tuning(b"gemm_variant", 0)
+        lib.ll_set_tuning(b"gemm_asm", GEMM_ASM_DEFAULT)
+
+
+def test_rowwise_tilings_at_one_k_step(ops):
+    """The same four tilings at K = 128, one K-step: the rings have no next stage to issue.  M = 257, N = 200: a partial n-tile in
+    every width, and only row 256 live in the second m-tile.  Bias and residual of f8 and w8a8, bit for bit against the host."""
+    lib = ops._lib.load()
+    M, N, K = 257, 200, 128
+    od = Operands(M, N, K, 11)
+    bias, res = hn("kb", (N,), 0.1), hn("kres", (M, N))
+    bd, rd = bias.to(DEV), res.to(DEV)
+    v = od.want("f8", bias)
+    assert torch.equal(v, od.want("w8a8", bias))
+    want_res = epi_tail(v, 3, res)
+    try:
+        assert lib.ll_set_tuning(b"gemm_asm", GEMM_ASM_DEFAULT & ~16) == 0      # int8 on the HIP kernels, as above
+        for variant, name in TILINGS.items():
+            assert lib.ll_set_tuning(b"gemm_variant", variant) == 0
+            assert ops.gemm_plan_f8(M, N, K).split(",")[0] == name.format("f8")
+            for fam in RW_FAMS:
+                assert torch.equal(_gemm(fam, od, bd).cpu(), v), f"{fam} v{variant}: bias"
+                assert torch.equal(_gemm(fam, od, bd, epi=3, res=rd).cpu(), want_res), f"{fam} v{variant}: residual"
     finally:
         lib.ll_set_tuning(b"gemm_variant", 0)
         lib.ll_set_tuning(b"gemm_asm", GEMM_ASM_DEFAULT)
