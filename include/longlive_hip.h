@@ -64,6 +64,12 @@ const char* ll_last_error(void);
  *               generated W8A8 kernels too (bit-identical results, measured slower end to end), bit 5 (32) = launches with more
  *               tiles than CUs run the PERSISTENT form (gemm_asmp_*: one workgroup per CU walks its tiles and stages the next
  *               tile's first pieces under the current epilogue; bit-identical results); default 35; 0 = HIP kernels only
+ *   "gemm_asm_mfma16"  mask of the generated bf16 kernels that run their v_mfma_f32_16x16x32_bf16 form (gemm_asm*_m16: the same tile
+ *               per wave, staging and epilogue arithmetic; only the fp32 summation order inside an MFMA differs): bit 0 = 128_bias,
+ *               1 = 128_res, 2 = 128_gate_res (each classic and persistent), 3 = 128_bias_ssq, 4 / 5 = 192_bias persistent / classic,
+ *               6 / 7 = 224_gelu persistent / classic, 8 = 256_bias; 0 = every kernel on v_mfma_f32_32x32x16_bf16; default 511
+ *               (the whole family: its members are held to each other bit for bit, which needs one order of the fp32 sum;
+ *               profiles/gemm_mfma16_ab.md); -1 restores the default
  *   "gemm_variant" / "gemm_variant_wide" (N >= 4096 only)  tile of the HIP kernels (int8, embeddings / head, gemm_asm = 0):
  *               0 = auto (cost model), 2 = 256x128 (gemm_kernel_v2, 3-stage ring), 3 = 256x256, 5 = 256x192, 6 = 256x224 (all three
  *               instances of the two-stage gemm_kernel_v5; ll_gemm_plan names the kernel and tile a shape takes)

@@ -190,6 +190,8 @@ static int g_gemm_variant_wide = 0;  // like gemm_variant, but only for N >= 409
 static int g_gemm_lds_epi = 1;
 static int g_gemm_asm = 35;        // generated kernels where they cover the call (bits 0, 1), persistent form for multi-round launches (bit 5)
 extern int g_gemm_asm_persistent;
+extern const int g_gemm_asm_mfma16_default;
+extern int g_gemm_asm_mfma16;      // bit mask: which generated bf16 kernels run their 16x16x32 MFMA form (gemm_asm.hip)
 static int g_gemm_group_m = 4;     // m-tiles per group in the workgroup -> tile walk (tile_of); <= 1: N fastest (round 1's order)
 void ll_set_attn_variant_internal(int v);
 void ll_set_attn_xcd_internal(int v);
@@ -214,6 +216,11 @@ extern "C" int ll_set_tuning(const char* key, int value) {
   if (!strcmp(key, "attn_asm_min_keys")) { ll_set_attn_asm_min_internal(value); return LL_OK; }
   if (!strcmp(key, "attn_asm")) { ll_set_attn_asm_internal(value); return LL_OK; }
   if (!strcmp(key, "conv_halo")) { ll_set_conv_halo_internal(value); return LL_OK; }
+  if (!strcmp(key, "gemm_asm_mfma16")) {
+    if (value < -1 || value > 511) { ll_set_error("ll_set_tuning: gemm_asm_mfma16=%d (a mask of 9 bits, one per kernel; -1 = the default)", value); return LL_ERR_INVALID_ARG; }
+    g_gemm_asm_mfma16 = value < 0 ? g_gemm_asm_mfma16_default : value;
+    return LL_OK;
+  }
   if (!strcmp(key, "gemm_asm")) { g_gemm_asm = value; g_gemm_asm_persistent = (value & 32) ? 1 : 0; return LL_OK; }
   ll_set_error("ll_set_tuning: unknown key %s", key);
   return LL_ERR_INVALID_ARG;

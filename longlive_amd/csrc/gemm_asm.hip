@@ -139,7 +139,99 @@
 #undef GA_WN
 #undef GA_INC
 
+// The bf16 kernels above once more on v_mfma_f32_16x16x32_bf16 (gen/gemm_asm_gen.py generate(..., mfma=16)): the same output tile per
+// wave, staging, tile walk and epilogue arithmetic; only the fragment and accumulator path differs.  The W8A8 and split-K partial
+// kernels have the 32-shape only.
+#define GA_NAME gemm_asm_224_gelu_m16
+#define GA_WN 224
+#define GA_INC "build/gemm_asm16_224_1.inc"
+#include "gemm_asm_kernel.inl"
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asm_256_bias_m16
+#define GA_WN 256
+#define GA_INC "build/gemm_asm16_256_0.inc"
+#include "gemm_asm_kernel.inl"
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asm_192_bias_m16
+#define GA_WN 192
+#define GA_INC "build/gemm_asm16_192_0.inc"
+#include "gemm_asm_kernel.inl"
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asm_128_bias_m16
+#define GA_WN 128
+#define GA_INC "build/gemm_asm16_128_0.inc"
+#include "gemm_asm_kernel.inl"
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asm_128_gate_res_m16
+#define GA_WN 128
+#define GA_INC "build/gemm_asm16_128_2.inc"
+#include "gemm_asm_kernel.inl"
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asm_128_res_m16
+#define GA_WN 128
+#define GA_INC "build/gemm_asm16_128_3.inc"
+#include "gemm_asm_kernel.inl"
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asm_128_bias_ssq_m16
+#define GA_WN 128
+#define GA_INC "build/gemm_asm16_128_5.inc"
+#define GA_SSQ 1
+#include "gemm_asm_kernel.inl"
+#undef GA_SSQ
+#undef GA_NAME
+#undef GA_WN
+#undef GA_INC
+#define GA_NAME gemm_asmp_224_gelu_m16
+#define GA_INC "build/gemm_asmp16_224_1.inc"
+#include "gemm_asm_kernel_p.inl"
+#undef GA_NAME
+#undef GA_INC
+#define GA_NAME gemm_asmp_192_bias_m16
+#define GA_INC "build/gemm_asmp16_192_0.inc"
+#include "gemm_asm_kernel_p.inl"
+#undef GA_NAME
+#undef GA_INC
+#define GA_NAME gemm_asmp_128_bias_m16
+#define GA_INC "build/gemm_asmp16_128_0.inc"
+#include "gemm_asm_kernel_p.inl"
+#undef GA_NAME
+#undef GA_INC
+#define GA_NAME gemm_asmp_128_gate_res_m16
+#define GA_INC "build/gemm_asmp16_128_2.inc"
+#include "gemm_asm_kernel_p.inl"
+#undef GA_NAME
+#undef GA_INC
+#define GA_NAME gemm_asmp_128_res_m16
+#define GA_INC "build/gemm_asmp16_128_3.inc"
+#include "gemm_asm_kernel_p.inl"
+#undef GA_NAME
+#undef GA_INC
+
 int g_gemm_asm_persistent = 1;      // tuning key gemm_asm bit 5 (set from gemm.hip's ll_set_tuning)
+// tuning key gemm_asm_mfma16: which bf16 kernels run their 16x16x32 form, one bit per kernel (0 = every kernel on 32x32x16)
+enum { GA16_128_BIAS = 1, GA16_128_RES = 2, GA16_128_GATE_RES = 4, GA16_128_BIAS_SSQ = 8, GA16_192P = 16, GA16_192 = 32, GA16_224P = 64, GA16_224 = 128,
+       GA16_256 = 256 };
+// the shipped mask (profiles/gemm_mfma16_ab.md; ll_set_tuning value -1 restores it): every bf16 kernel.  The family moves as one: the
+// suite holds its members to each other bit for bit (classic against persistent, the fused QKV projection on the 192-wide kernel
+// against the unfused one on the 128-wide, the row-sum kernel against the bias kernel), which needs one order of the fp32 sum.
+extern const int g_gemm_asm_mfma16_default = 511;
+int g_gemm_asm_mfma16 = g_gemm_asm_mfma16_default;
+static int gemm_asm_mfma16_bit(int wn, int epilogue, bool persistent) {
+  return wn == 224 ? (persistent ? GA16_224P : GA16_224) : wn == 192 ? (persistent ? GA16_192P : GA16_192) : wn == 256 ? GA16_256
+         : epilogue == LL_EPI_BIAS ? GA16_128_BIAS : epilogue == LL_EPI_BIAS_GATE_RES ? GA16_128_GATE_RES : GA16_128_RES;
+}
 static int gemm_asm_cus() {
   static int cus[64];
   int dev = 0;
@@ -194,6 +286,19 @@ int gemm_asm_launch(const bf16* x, const bf16* w, bf16* out, int M, int N, int K
                     : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asmp_128_gate_res : (const void*)gemm_asmp_128_res;
   const bool persistent = g_gemm_asm_persistent && pfn != nullptr && cus >= 8 && ntm * ntn > cus;
   if (persistent) fn = pfn;
+  if (g_gemm_asm_mfma16 & gemm_asm_mfma16_bit(wn, epilogue, persistent)) {
+    if (persistent)
+      fn = wn == 224 ? (const void*)gemm_asmp_224_gelu_m16
+           : wn == 192 ? (const void*)gemm_asmp_192_bias_m16
+           : epilogue == LL_EPI_BIAS ? (const void*)gemm_asmp_128_bias_m16
+           : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asmp_128_gate_res_m16 : (const void*)gemm_asmp_128_res_m16;
+    else
+      fn = wn == 224 ? (const void*)gemm_asm_224_gelu_m16
+           : wn == 256 ? (const void*)gemm_asm_256_bias_m16
+           : wn == 192 ? (const void*)gemm_asm_192_bias_m16
+           : epilogue == LL_EPI_BIAS ? (const void*)gemm_asm_128_bias_m16
+           : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asm_128_gate_res_m16 : (const void*)gemm_asm_128_res_m16;
+  }
   if (int rc = ll_lds_attr(fn, lds)) return rc;
   const bf16* gate = epilogue == LL_EPI_BIAS_GATE_RES ? ea.e + (size_t)ea.gate_idx * N : nullptr;
   const int gstride = ea.nmod * N * 2;
@@ -212,7 +317,8 @@ int gemm_asm_launch(const bf16* x, const bf16* w, bf16* out, int M, int N, int K
 int gemm_asm_ssq_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* out, float* ssq, int M, int N, int K, int ldx, int ldo, int gm,
                         hipStream_t s) {
   if (gemm_asm_width(M, N, K, ldx, LL_EPI_BIAS, true, false, false, 0) != 128) return 0;
-  const void* fn = (const void*)gemm_asm_128_bias_ssq;
+  const bool m16 = (g_gemm_asm_mfma16 & GA16_128_BIAS_SSQ) != 0;
+  const void* fn = m16 ? (const void*)gemm_asm_128_bias_ssq_m16 : (const void*)gemm_asm_128_bias_ssq;
   const int lds = 3 * 128 * 128 + 4 * 2 * 8192;
   if (int rc = ll_lds_attr(fn, lds)) return rc;
   const int ntm = (M + 255) / 256, ntn = N / 128;
@@ -222,19 +328,21 @@ int gemm_asm_ssq_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* ou
   void* args[] = {(void*)&x, (void*)&w, (void*)&bias, (void*)&out, (void*)&nullb, (void*)&nullb, (void*)&M, (void*)&N, (void*)&K,
                   (void*)&ldx, (void*)&ldo, (void*)&zero, (void*)&zero, (void*)&ntm, (void*)&ntn, (void*)&gm,
                   (void*)&nov, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&ssq};
-  if (hipLaunchKernel(fn, dim3(ntm * ntn), dim3(256), args, (size_t)lds, s) != hipSuccess) return ll_check_launch("gemm_asm_128_bias_ssq");
+  if (hipLaunchKernel(fn, dim3(ntm * ntn), dim3(256), args, (size_t)lds, s) != hipSuccess) return ll_check_launch(m16 ? "gemm_asm_128_bias_ssq_m16" : "gemm_asm_128_bias_ssq");
   return 1;
 }
 
 const char* gemm_asm_plan(int M, int N, int wn, int epilogue, char* out, int cap, bool i8) {
   const char* tail = wn == 224 ? "gelu" : wn == 256 ? "bias" : epilogue == LL_EPI_BIAS ? "bias" : epilogue == LL_EPI_BIAS_GATE_RES ? "gate_res" : "res";      // wn == 192: bias
   const int tiles = ((M + 255) / 256) * (N / wn), cus = gemm_asm_cus() & ~7;
-  if (!i8 && g_gemm_asm_persistent && wn != 256 && cus >= 8 && tiles > cus)
-    snprintf(out, (size_t)cap, "gemm_asmp_%d_%s<bf16> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d persistent workgroups "
-             "walk %d tiles, next tile staged under the epilogue", wn, tail, wn, cus, tiles);
+  const bool persistent = !i8 && g_gemm_asm_persistent && wn != 256 && cus >= 8 && tiles > cus;
+  const char* m16 = !i8 && (g_gemm_asm_mfma16 & gemm_asm_mfma16_bit(wn, epilogue, persistent)) ? "_m16" : "";      // the kernel gemm_asm_launch takes
+  if (persistent)
+    snprintf(out, (size_t)cap, "gemm_asmp_%d_%s%s<bf16> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d persistent workgroups "
+             "walk %d tiles, next tile staged under the epilogue", wn, tail, m16, wn, cus, tiles);
   else
-    snprintf(out, (size_t)cap, "gemm_asm%s_%d_%s<%s> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d workgroups", i8 ? "q" : "", wn,
-             tail, i8 ? "i8" : "bf16", wn, tiles);
+    snprintf(out, (size_t)cap, "gemm_asm%s_%d_%s%s<%s> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d workgroups", i8 ? "q" : "", wn,
+             tail, m16, i8 ? "i8" : "bf16", wn, tiles);
   return out;
 }
 

@@ -23,6 +23,12 @@ tools/gfx950_emu.py in the CPU suite before any GPU run):
     bound at 15 B/clk of staging per CU -- no faster than the HIP kernels.)  vmcnt is one in-order queue: the wait at the end of
     a half-step is counted so that the next half-step's X fragments -- and with them every W piece older than ~3 half-steps --
     have landed; one barrier per K-step.
+  * MFMA shape (Cfg.mfma, bf16 texts only): 32 = v_mfma_f32_32x32x16_bf16 as described above; 16 = v_mfma_f32_16x16x32_bf16 at the SAME
+    output tile per wave, accumulator count, LDS image, staging, waits and tile walk: one MFMA per (16-column W block, 16-row X block)
+    and half-step, fragments read as row l & 15 / 16 bytes of K at 16 (l >> 4) of the 64-byte half line (as many ds_read_b128 and
+    bytes; conflict-free under the same XOR swizzle, tests/test_gemm_asm_mfma16_emu.py), twice as many 16-cycle gaps for the same
+    fillers; v_permlane16_swap between the two 16-row blocks of a 32-row block gives the epilogue the 16-byte runs of the 32-shape.
+    Text for mfma = 32 is byte-identical to the generator before the parameter existed.
   * epilogues in the same text, rounding points as gemm_common.h (v = bf16(acc + bias); GELU x.sigma(2u) with v_exp / v_rcp;
     x + bf16(v . gate[frame]); x + v), packed-f32 VALU where it halves the instruction count (no MFMA runs beside it).
 """
@@ -81,10 +87,15 @@ def KN(k):
 
 
 class Cfg:
-    def __init__(self, WN, epi, i8=False):
+    def __init__(self, WN, epi, i8=False, mfma=32):
         assert WN % 32 == 0 and 64 <= WN <= 256
         assert not (i8 and epi in (EPI_PARTIAL, EPI_BIAS_SSQ))
+        assert mfma in (32, 16) and not (mfma == 16 and (i8 or epi == EPI_PARTIAL))
         self.WN, self.NB, self.MB, self.epi, self.i8 = WN, WN // 32, 2, epi, i8
+        self.mfma = mfma                                          # bf16 MFMA shape: 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16 (same output tile
+        self.m16 = mfma == 16                                     # per wave, same registers; see mfmas() for the layout)
+        self.sc = 2 if self.m16 else 1                            # MFMAs per half-step relative to the 32-shape: filler positions scale with it
+        self.bl = 2 if self.m16 else 4                            # bias loads (8 bytes per lane each) per 32-column block
         self.nacc = self.MB * self.NB * 16
         self.slotb = WN * 128                                      # bytes of one W slot: WN rows x 128 B (a 64-deep K-step)
         self.npw = WN // 32                                        # 1-KiB LDS-DMA pieces of W per wave and K-step (WN / 8 pieces of 8 rows)
@@ -107,7 +118,7 @@ class Cfg:
         # vectors of the first `early_nb` column blocks and the first block's gate / residual pieces are fetched before the
         # first staging piece, so the epilogue starts without an exposed memory latency
         self.V_EA = nxt + 37                                      # +0,+1 row byte offsets in Y / RES; +2 bias column offset; +3,+4 gate row offsets
-        top = self.V_EA + 5
+        top = self.V_EA + (7 if self.m16 else 5)                  # (16-shape: +3..+6, one gate row offset per 16-row block)
         if i8:                                                    # W8A8: +5 column byte offset into the weight scales (16 h); V_SX[mb] = (sx[row], sx[row]) pairs
             self.V_SX = top + 2                                   # (register pairs start on even registers)
             top += 6
@@ -116,7 +127,7 @@ class Cfg:
         self.V_E0 = top                                           # the first block's gate / residual pieces (16 registers) when nl
         top += 16 if self.nl else 0
         self.V_SS = top                                           # EPI_BIAS_SSQ: running sums of squares SS[mb] = 2 registers each (even / odd column of a pair)
-        top += 4 if epi == EPI_BIAS_SSQ else 0
+        top += (8 if self.m16 else 4) if epi == EPI_BIAS_SSQ else 0      # (16-shape: SS[mb16], a lane's accumulators span two rows per 32-row block)
         self.V_EB = top                                           # early bias [nb][g4], 2 registers each
         self.early_nb = 0 if epi == EPI_PARTIAL else max(0, min(self.NB, (256 - top) // 8))
 
@@ -129,10 +140,29 @@ class Cfg:
     def fx(self, b, mb, ks4):
         return self.FX + ((b * self.MB + mb) * 4 + ks4) * 4
 
+    # 16-shape: the same files cut into 16-row blocks -- acc16[mb16][nb16] (4 registers), FW16[p][nb16], FX16[b][mb16][hs]
+    def acc16(self, mb16, nb16):
+        return (mb16 * 2 * self.NB + nb16) * 4
+
+    def fw16(self, p, nb16):
+        return self.FW + (p * 2 * self.NB + nb16) * 4
+
+    def fx16(self, b, mb16, hs):
+        return self.FX + ((b * 4 + mb16) * 2 + hs) * 4
+
 
 def mfmas(c: Cfg, h):
     p, b, hf = h & 1, (h >> 1) & 1, h & 1
     out = []
+    if c.m16:
+        # one MFMA per (16-column W block, 16-row X block) covers the half-step's 32 K: lane l feeds row l & 15 and the 16 bytes of K
+        # at 16 (l >> 4) of the 64-byte half line, and ends up with row m = 16 mb16 + (l & 15), columns 16 nb16 + 4 (l >> 4) + (0..3).
+        # nb16 outer: a W fragment feeds four consecutive MFMAs, no two consecutive MFMAs share an accumulator.
+        for nb16 in range(2 * c.NB):
+            for mb16 in range(4):
+                a = areg(c.acc16(mb16, nb16), 4)
+                out.append(f"v_mfma_f32_16x16x32_bf16 {a}, {vreg(c.fw16(p, nb16), 4)}, {vreg(c.fx16(b, mb16, hf), 4)}, {a}")
+        return out
     for ks in range(2):
         for nb in range(c.NB):
             for mb in range(c.MB):
@@ -146,6 +176,12 @@ def w_frag_reads(c: Cfg, h):
     """W fragments of half-step h (K-step h >> 1, half h & 1) from its ring slot into FW[h & 1]"""
     slot, hs = (h >> 1) % NSLOT, h & 1
     out = []
+    if c.m16:                                                     # as many reads and bytes as below: one per 16-row block (2 KiB apart) and half-step
+        for nb16 in range(2 * c.NB):
+            off = slot * c.slotb + nb16 * 2048
+            b64, imm = off >> 16, off & 0xFFFF
+            out.append(f"ds_read_b128 {vreg(c.fw16(h & 1, nb16), 4)}, {vreg(c.V_WOFF + 4 * b64 + 2 * hs)} offset:{imm}")
+        return out
     for ks in range(2):
         for nb in range(c.NB):
             off = slot * c.slotb + nb * 4096
@@ -157,6 +193,11 @@ def w_frag_reads(c: Cfg, h):
 def x_frag_reads(c: Cfg, s):
     """the wave's X fragments of K-step s (both half-steps) from its own unit s % XU into FX[s & 1]"""
     out = []
+    if c.m16:
+        for hs in range(2):
+            for mb16 in range(4):
+                out.append(f"ds_read_b128 {vreg(c.fx16(s & 1, mb16, hs), 4)}, {vreg(c.V_XROFF + 2 * hs)} offset:{(s % XU) * c.xunit + mb16 * 2048}")
+        return out
     for ks4 in range(4):
         for mb in range(c.MB):
             out.append(f"ds_read_b128 {vreg(c.fx(s & 1, mb, ks4), 4)}, {vreg(c.V_XROFF + ks4)} offset:{(s % XU) * c.xunit + mb * 4096}")
@@ -306,7 +347,7 @@ def gen_tile_bases(g: Gen, c, xdst, wdst, rows_dst, skip_label, full: bool, pref
     g.L(lab)
 
 
-def generate(WN: int, epi: int, prefix: str, i8: bool = False, persistent: bool = False) -> str:
+def generate(WN: int, epi: int, prefix: str, i8: bool = False, persistent: bool = False, mfma: int = 32) -> str:
     """Issue order of the staging (one in-order vmcnt queue per wave): W(j) in half-step 2 j - 5, X(j) in half-step 2 j - 4, so at
     the END of the even half-step 2 s the wave has issued ... W(s+1) X(s+1) W(s+2) X(s+2): `s_waitcnt vmcnt(npw + 8)` there = the
     next K-step's operands have landed.  The one barrier per K-step stands right behind that wait: it makes W(s+1) visible (first
@@ -314,7 +355,7 @@ def generate(WN: int, epi: int, prefix: str, i8: bool = False, persistent: bool 
     which the odd half-step then refills with W(s+3).  X needs no barrier: unit (s+1) % 2 is read into FX[(s+1) & 1] in the odd
     half-step of K-step s and refilled (X(s+3)) in the even half-step after it -- the reads are retired by the fragment waits of
     the W reads issued after them (LDS returns in order)."""
-    c = Cfg(WN, epi, i8)
+    c = Cfg(WN, epi, i8, mfma)
     assert not (persistent and (i8 or epi in (EPI_PARTIAL, EPI_BIAS_SSQ)))
     g = Gen()
     I = g.I
@@ -374,10 +415,25 @@ def generate(WN: int, epi: int, prefix: str, i8: bool = False, persistent: bool 
         if mb:
             I(f"v_add_u32 {vreg(c.V_ROW + mb)}, {32 * mb}, {vreg(c.V_ROW + mb)}")
     # fragment read offsets: row r (+ 32 per block by immediate), chunk at position chunk ^ ((r >> 1) & 7)
-    I(f"v_lshrrev_b32 {vreg(T)}, 1, {vreg(c.V_R)}")
-    I(f"v_and_b32 {vreg(T)}, 7, {vreg(T)}")
-    I(f"v_lshlrev_b32 {vreg(T + 1)}, 7, {vreg(c.V_R)}")                    # r * 128
+    if c.m16:
+        # 16-shape: row l & 15 (+ 16 per block by immediate: the swizzle term (row >> 1) & 7 does not see it), chunk 4 hs + (l >> 4)
+        I(f"v_and_b32 {vreg(T + 1)}, 15, {vreg(c.V_LANE)}")
+        I(f"v_lshrrev_b32 {vreg(T + 3)}, 4, {vreg(c.V_LANE)}")
+        I(f"v_lshrrev_b32 {vreg(T)}, 1, {vreg(T + 1)}")
+        I(f"v_lshlrev_b32 {vreg(T + 1)}, 7, {vreg(T + 1)}")
+    else:
+        I(f"v_lshrrev_b32 {vreg(T)}, 1, {vreg(c.V_R)}")
+        I(f"v_and_b32 {vreg(T)}, 7, {vreg(T)}")
+        I(f"v_lshlrev_b32 {vreg(T + 1)}, 7, {vreg(c.V_R)}")                    # r * 128
     for hs in range(2):
+        if c.m16:
+            I(f"v_add_u32 {vreg(T + 2)}, {4 * hs}, {vreg(T + 3)}")
+            I(f"v_xor_b32 {vreg(T + 2)}, {vreg(T + 2)}, {vreg(T)}")
+            I(f"v_lshl_add_u32 {vreg(c.V_WOFF + 2 * hs)}, {vreg(T + 2)}, 4, {vreg(T + 1)}")
+            I(f"v_add_u32 {vreg(c.V_WOFF + 4 + 2 * hs)}, 0x10000, {vreg(c.V_WOFF + 2 * hs)}")
+            I(f"v_add_u32 {vreg(c.V_WOFF + 8 + 2 * hs)}, 0x20000, {vreg(c.V_WOFF + 2 * hs)}")
+            I(f"v_add_u32 {vreg(c.V_XROFF + 2 * hs)}, {sreg(S_XM0)}, {vreg(c.V_WOFF + 2 * hs)}")
+            continue
         for ks in range(2):
             I(f"v_add_u32 {vreg(T + 2)}, {4 * hs + 2 * ks}, {vreg(c.V_H)}")
             I(f"v_xor_b32 {vreg(T + 2)}, {vreg(T + 2)}, {vreg(T)}")
@@ -420,6 +476,7 @@ def generate(WN: int, epi: int, prefix: str, i8: bool = False, persistent: bool 
     I(f"s_mov_b32 {sreg(S_I)}, 0")
     # ================= main loop over half-steps, unrolled over lcm(NSLOT, XU) K-steps =================
     period = 2 * NSLOT * XU // (2 if NSLOT % 2 == 0 else 1)
+    sc = c.sc                                          # the 16-shape has twice the MFMAs (and gaps) per half-step: same fillers, positions scaled
     assert (period // 2) % NSLOT == 0 and (period // 2) % XU == 0
     g.L(f"{prefix}_LOOP")
     for h in range(period):
@@ -428,18 +485,18 @@ def generate(WN: int, epi: int, prefix: str, i8: bool = False, persistent: bool 
         n = len(mm)
         wr = [] if KN("NO_WREAD") else w_frag_reads(c, h + 1)
         if h & 1 == 0:
-            fillers = [(0.6 + k * (n - 6) / len(wr), op) for k, op in enumerate(wr)] if wr else []
+            fillers = [(0.6 * sc + k * (n - 6 * sc) / len(wr), op) for k, op in enumerate(wr)] if wr else []
             xd = x_dma(c, s + 2)
-            fillers += spread(drop_loads(xd) if KN("NO_X") else xd, 1.3, n - 1.5)
+            fillers += spread(drop_loads(xd) if KN("NO_X") else xd, 1.3 * sc, n - 1.5 * sc)
             g.phase([] if KN("NO_MFMA") else mm, fillers)
             I(f"s_waitcnt vmcnt({npw + 8})")           # W(s+1), X(s+1) have landed (younger: W(s+2), X(s+2))
             I("s_barrier")                             # W(s+1) visible to all; every wave is done reading the slot of W(s)
         else:
             xr = [] if KN("NO_WREAD") else x_frag_reads(c, s + 1)
-            fillers = [(0.3 + k * 0.5, op) for k, op in enumerate(xr)]                   # ahead of the W reads: retired with them
-            fillers += [(4.6 + k * (n - 10) / len(wr), op) for k, op in enumerate(wr)] if wr else []
+            fillers = [((0.3 + k * 0.5) * sc, op) for k, op in enumerate(xr)]            # ahead of the W reads: retired with them
+            fillers += [(4.6 * sc + k * (n - 10 * sc) / len(wr), op) for k, op in enumerate(wr)] if wr else []
             wd = w_dma(c, s + 3)
-            fillers += spread(drop_loads(wd) if KN("NO_W") else wd, 1.3, n - 1.5)
+            fillers += spread(drop_loads(wd) if KN("NO_W") else wd, 1.3 * sc, n - 1.5 * sc)
             g.phase([] if KN("NO_MFMA") else mm, fillers)
             I(f"s_add_u32 {sreg(S_I)}, {sreg(S_I)}, 1")
             I(f"s_cmp_ge_u32 {sreg(S_I)}, {sreg(S_NK)}")
@@ -559,13 +616,26 @@ def gen_epilogue_setup(g: Gen, c: Cfg):
     for mb in range(c.MB):
         I(f"v_mul_lo_u32 {vreg(EA + mb)}, {vreg(c.V_ROW + mb)}, {sreg(S_LDO)}")
         I(f"v_lshl_add_u32 {vreg(EA + mb)}, {vreg(c.V_H)}, 4, {vreg(EA + mb)}")
-    I(f"v_lshlrev_b32 {vreg(EA + 2)}, 3, {vreg(c.V_H)}")                     # bias / gate column byte offset of this half: 8 h
+    # 16-shape: BEFORE the lane exchange a lane holds rows 16 mb16 + (l & 15) and, per 16-column block, columns 4 q + (0..3), q = l >> 4;
+    # AFTER it (v_permlane16_swap between the two 16-row blocks of a 32-row block) the same rows and 16-byte column runs as the
+    # 32-shape after its swap -- row 32 mb + (l & 31), columns 8 h + (0..7) per 16-column block -- so everything above is shared
+    R16, Q16 = T + 60, T + 61
+    if c.m16:
+        I(f"v_and_b32 {vreg(R16)}, 0xffffffef, {vreg(c.V_ROW)}")             # 64 w + (l & 15)
+        I(f"v_lshrrev_b32 {vreg(Q16)}, 4, {vreg(c.V_LANE)}")
+        I(f"v_lshlrev_b32 {vreg(EA + 2)}, 3, {vreg(Q16)}")                   # bias / gate column byte offset of this lane group: 8 q
+    else:
+        I(f"v_lshlrev_b32 {vreg(EA + 2)}, 3, {vreg(c.V_H)}")                     # bias / gate column byte offset of this half: 8 h
     if epi == EPI_GATE_RES:
         # gate row of the lane's row: frame = (m0 + row) / frame_len  (integer division via float with one correction each way)
         I(f"s_sub_u32 {sreg(S_T1)}, {sreg(S_ROWS)}, 1")                      # rows past M take the last valid row's frame (gemm_common.h: mc = min(m, M - 1)):
-        for mb in range(c.MB):                                               # their gate address must stay inside the table
+        for mb in range(4 if c.m16 else c.MB):                               # their gate address must stay inside the table
             m, q, t = T + 66, EA + 3 + mb, T + 48
-            I(f"v_min_u32 {vreg(m)}, {sreg(S_T1)}, {vreg(c.V_ROW + mb)}")
+            if c.m16:                                                        # (mb counts 16-row blocks here)
+                I(f"v_add_u32 {vreg(m)}, {16 * mb}, {vreg(R16)}")
+                I(f"v_min_u32 {vreg(m)}, {sreg(S_T1)}, {vreg(m)}")
+            else:
+                I(f"v_min_u32 {vreg(m)}, {sreg(S_T1)}, {vreg(c.V_ROW + mb)}")
             I(f"v_add_u32 {vreg(m)}, {sreg(S_M0)}, {vreg(m)}")
             I(f"v_cvt_f32_u32 {vreg(t)}, {vreg(m)}")
             I(f"v_cvt_f32_u32 {vreg(t + 1)}, {sreg(S_FLEN)}")
@@ -583,7 +653,7 @@ def gen_epilogue_setup(g: Gen, c: Cfg):
             I(f"v_cndmask_b32_e64 {vreg(t + 2)}, 0, 1, {sreg(S_MSK, 2)}")
             I(f"v_add_u32 {vreg(q)}, {vreg(q)}, {vreg(t + 2)}")
             I(f"v_mul_lo_u32 {vreg(q)}, {vreg(q)}, {sreg(S_GSTRIDE)}")       # byte offset of the frame's gate row
-            I(f"v_lshl_add_u32 {vreg(q)}, {vreg(c.V_H)}, 3, {vreg(q)}")      # + 8 h: the gate is applied in the accumulator layout (as the bias)
+            I(f"v_lshl_add_u32 {vreg(q)}, {vreg(Q16 if c.m16 else c.V_H)}, 3, {vreg(q)}")      # + 8 h: the gate is applied in the accumulator layout (as the bias)
     for mb in range(c.MB):                                                   # stored rows: row_lo <= row < rows
         I(f"v_cmp_lt_u32_e64 {sreg(S_MSK + 2 * mb, 2)}, {vreg(c.V_ROW + mb)}, {sreg(S_ROWS)}")
         I(f"v_cmp_ge_u32_e64 vcc, {vreg(c.V_ROW + mb)}, {sreg(S_ROWLO)}")
@@ -600,8 +670,8 @@ def gen_epilogue_setup(g: Gen, c: Cfg):
     # early reads
     n0 = sum(1 for l in g.out if l.startswith("global_load"))
     for nb in range(c.early_nb):
-        for g4 in range(4):
-            I(f"global_load_dwordx2 {vreg(c.V_EB + 8 * nb + 2 * g4, 2)}, {vreg(EA + 2)}, {sreg(S_BIAS, 2)} offset:{64 * nb + 16 * g4}")
+        for g4 in range(c.bl):                                                # (16-shape: g4 = the 16-column half of the block)
+            I(f"global_load_dwordx2 {vreg(c.V_EB + 8 * nb + 2 * g4, 2)}, {vreg(EA + 2)}, {sreg(S_BIAS, 2)} offset:{64 * nb + (64 // c.bl) * g4}")
     if c.nl:
         epi_block_loads(g, c, 0, c.V_E0)
     return sum(1 for l in g.out if l.startswith("global_load")) - n0 + (c.MB if c.i8 else 0)      # vector-memory reads issued here
@@ -614,6 +684,9 @@ def epi_block_loads(g: Gen, c: Cfg, j: int, P: int):
     EA = c.V_EA
     if c.epi == EPI_GATE_RES:                                                # gate[frame][n] in the accumulator layout (as the bias)
         for g4 in range(4):
+            if c.m16:                                                        # group g4 = (16-column half g4 >> 1, 16-row half g4 & 1) of the block
+                I(f"global_load_dwordx2 {vreg(P + 2 * g4, 2)}, {vreg(EA + 3 + 2 * mb + (g4 & 1))}, {sreg(S_GATE, 2)} offset:{64 * nb + 32 * (g4 >> 1)}")
+                continue
             I(f"global_load_dwordx2 {vreg(P + 2 * g4, 2)}, {vreg(EA + 3 + mb)}, {sreg(S_GATE, 2)} offset:{64 * nb + 16 * g4}")
     if c.epi in (EPI_GATE_RES, EPI_RES):                                     # residual in the 8-column layout after the swap
         I(f"s_mov_b64 exec, {sreg(S_MSK + 2 * mb, 2)}")
@@ -623,7 +696,11 @@ def epi_block_loads(g: Gen, c: Cfg, j: int, P: int):
 
 
 def gen_epilogue(g: Gen, c: Cfg):
-    """per (mb, nb): 16 accumulators of a lane = its row m, columns 32 nb + 8 g4 + 4 h + (0..3), g4 = 0..3"""
+    """per (mb, nb): 16 accumulators of a lane = its row m, columns 32 nb + 8 g4 + 4 h + (0..3), g4 = 0..3.
+    16-shape: the block (mb, nb) is the four 16 x 16 tiles (mb16, nb16) = (2 mb + a, 2 nb + cc); group g4 = 2 cc + a of the lane's 16
+    values is row 32 mb + 16 a + (l & 15), columns 32 nb + 16 cc + 4 q + (0..3), q = l >> 4.  v_permlane16_swap between the groups
+    a = 0 / 1 of one cc (the 16-lane analogue of T21) leaves every lane with the 16-byte runs of the 32-shape after its swap, so the
+    residual arithmetic, the row masks and the stores are the same text; the rounding points and their order are untouched."""
     I = g.I
     T = c.V_T
     epi = c.epi
@@ -638,7 +715,7 @@ def gen_epilogue(g: Gen, c: Cfg):
     if epi == EPI_GELU:
         const_pair("k1", K1, 54); const_pair("k0", K0, 56); const_pair("ce", CEXP, 58); const_pair("one", 1.0, 60)
     if epi == EPI_BIAS_SSQ:
-        for k in range(2 * c.MB):
+        for k in range((4 if c.m16 else 2) * c.MB):
             I(f"v_mov_b32 {vreg(c.V_SS + k)}, 0")
     if epi == EPI_PARTIAL:
         # fp32 accumulators as they stand: a lane owns row m, columns 32 nb + 8 g4 + 4 h + (0..3) = 16 contiguous bytes per group
@@ -656,7 +733,7 @@ def gen_epilogue(g: Gen, c: Cfg):
     # bias vectors that did not fit up there, then the gate / residual pieces of block j + 1 while block j computes.
     BB, PB = T + 72, T + 72 + 8 * c.NB                                       # late bias raw [nb][g4] (2 registers each); block buffers P[2][16]
     assert PB + 32 <= min(c.V_WOFF + 32, 256), (PB, c.V_WOFF)               # below the registers that survive the loop (V_LANE ...)
-    n_late = 4 * (c.NB - c.early_nb)
+    n_late = c.bl * (c.NB - c.early_nb)
     q = []                                                                   # vector-memory operations issued by the epilogue, in order
     SWB = PB + 32                                                            # W8A8: weight scales of the current / next column block, 2 x 16 registers
     assert not c.i8 or SWB + 32 <= c.V_LANE, (SWB, c.V_LANE)
@@ -672,9 +749,9 @@ def gen_epilogue(g: Gen, c: Cfg):
         q.extend([("sw", nb)] * 4)
 
     for nb in range(c.early_nb, c.NB):                                       # lane needs columns 32 nb + 8 g4 + 4 h + (0..3): 4 loads of 8 bytes
-        for g4 in range(4):
-            I(f"global_load_dwordx2 {vreg(BB + 8 * nb + 2 * g4, 2)}, {vreg(EA + 2)}, {sreg(S_BIAS, 2)} offset:{64 * nb + 16 * g4}")
-        q.extend([("bias", nb)] * 4)
+        for g4 in range(c.bl):                                               # (16-shape: columns 32 nb + 16 g4 + 4 q + (0..3): 2 loads)
+            I(f"global_load_dwordx2 {vreg(BB + 8 * nb + 2 * g4, 2)}, {vreg(EA + 2)}, {sreg(S_BIAS, 2)} offset:{64 * nb + (64 // c.bl) * g4}")
+        q.extend([("bias", nb)] * c.bl)
     if c.i8:
         sw_loads(0)
         for mb in range(c.MB):                                               # (sx, sx) pairs for the packed multiplies
@@ -706,13 +783,14 @@ def gen_epilogue(g: Gen, c: Cfg):
         if mb == 0:
             for g4 in range(4):                                              # bf16 x4 -> f32 x4: T+24+4 g4 .. +3
                 for d in range(2):
-                    src = (c.V_EB if nb < c.early_nb else BB) + 8 * nb + 2 * g4 + d
+                    src = (c.V_EB if nb < c.early_nb else BB) + 8 * nb + 2 * (g4 >> 1 if c.m16 else g4) + d
                     I(f"v_lshlrev_b32 {vreg(T + 24 + 4 * g4 + 2 * d)}, 16, {vreg(src)}")
                     I(f"v_and_b32 {vreg(T + 24 + 4 * g4 + 2 * d + 1)}, 0xffff0000, {vreg(src)}")
         a0 = c.acc(mb, nb)
         # v = bf16(acc + bias), kept as f32 in T+0..15
         for r in range(16):
-            I(f"v_accvgpr_read_b32 {vreg(T + r)}, {areg(a0 + r)}")
+            src = c.acc16(2 * mb + ((r >> 2) & 1), 2 * nb + (r >> 3)) + (r & 3) if c.m16 else a0 + r
+            I(f"v_accvgpr_read_b32 {vreg(T + r)}, {areg(src)}")
         if c.i8:                                                             # acc_f * (sx[m] * sw[n]) with gemm_common.h's order of operations
             for r in range(16):
                 I(f"v_cvt_f32_i32 {vreg(T + r)}, {vreg(T + r)}")
@@ -728,8 +806,9 @@ def gen_epilogue(g: Gen, c: Cfg):
                 I(f"v_lshlrev_b32 {vreg(T + r)}, 16, {vreg(T + 16 + r // 2)}")
                 I(f"v_and_b32 {vreg(T + r + 1)}, 0xffff0000, {vreg(T + 16 + r // 2)}")
         if epi == EPI_BIAS_SSQ:                                              # SS[mb] += v * v of the ROUNDED outputs, fixed order: nb, then the 8 pairs
-            for r in range(0, 16, 2):
-                I(f"v_pk_fma_f32 {vreg(c.V_SS + 2 * mb, 2)}, {vreg(T + r, 2)}, {vreg(T + r, 2)}, {vreg(c.V_SS + 2 * mb, 2)}")
+            for r in range(0, 16, 2):                                        # (16-shape: SS[mb16] of the group's row half)
+                ss = c.V_SS + 2 * (2 * mb + ((r >> 2) & 1) if c.m16 else mb)
+                I(f"v_pk_fma_f32 {vreg(ss, 2)}, {vreg(T + r, 2)}, {vreg(T + r, 2)}, {vreg(ss, 2)}")
         if epi == EPI_GATE_RES:                                              # w = bf16(v * gate[frame][n])
             for r in range(0, 16, 2):
                 src = P + r // 2
@@ -762,8 +841,9 @@ def gen_epilogue(g: Gen, c: Cfg):
         for k in (0, 2):
             ax, ay, bx, by = T + 16 + 2 * k, T + 17 + 2 * k, T + 18 + 2 * k, T + 19 + 2 * k
             I("s_nop 1")
-            I(f"v_permlane32_swap_b32 {vreg(ax)}, {vreg(bx)}")
-            I(f"v_permlane32_swap_b32 {vreg(ay)}, {vreg(by)}")
+            swap = "v_permlane16_swap_b32" if c.m16 else "v_permlane32_swap_b32"          # 16-shape: groups (cc, a = 0) and (cc, a = 1), cc = k / 2
+            I(f"{swap} {vreg(ax)}, {vreg(bx)}")
+            I(f"{swap} {vreg(ay)}, {vreg(by)}")
         off_y = 64 * nb
         if epi in (EPI_GATE_RES, EPI_RES):
             # residual arithmetic in the 8-column layout after the swap: out = bf16(res + w), w = v or bf16(v * gate)
@@ -781,7 +861,35 @@ def gen_epilogue(g: Gen, c: Cfg):
             I(f"global_store_dwordx4 {vreg(EA + mb)}, {vreg(T + 16 + 2 * k, 4)}, {sreg(S_Y, 2)} offset:{off_y + 16 * k}")
         I("s_mov_b64 exec, -1")
         q.extend([("st", j)] * 2)
-    if epi == EPI_BIAS_SSQ:
+    if epi == EPI_BIAS_SSQ and c.m16:
+        # row sum of the tile, fixed order: per lane group q the pairs in the order above, even + odd columns; then (q0 + q2) + (q1 + q3)
+        # (lanes l, l + 16, l + 32, l + 48 hold the four column quarters of row 16 mb16 + (l & 15)); one 4-byte store per valid row
+        # from lane group 0
+        R16, Q16 = T + 8, T + 9
+        I(f"v_and_b32 {vreg(R16)}, 0xffffffef, {vreg(c.V_ROW)}")             # 64 w + (l & 15)
+        I(f"v_lshrrev_b32 {vreg(Q16)}, 4, {vreg(c.V_LANE)}")
+        for step in ("v_permlane32_swap_b32", "v_permlane16_swap_b32"):
+            for mb in range(4):
+                ss = c.V_SS + 2 * mb
+                I(f"v_add_f32 {vreg(ss)}, {vreg(ss)}, {vreg(ss + 1)}")
+                I(f"v_mov_b32 {vreg(ss + 1)}, {vreg(ss)}")
+            I("s_nop 1")
+            for mb in range(4):
+                ss = c.V_SS + 2 * mb
+                I(f"{step} {vreg(ss)}, {vreg(ss + 1)}")                      # ss = the lower group's sum in both groups, ss + 1 = the upper group's
+        for mb in range(4):
+            ss = c.V_SS + 2 * mb
+            I(f"v_add_f32 {vreg(ss)}, {vreg(ss)}, {vreg(ss + 1)}")
+            I(f"v_add_u32 {vreg(T + mb)}, {16 * mb}, {vreg(R16)}")                      # the row
+            I(f"v_cmp_lt_u32_e64 vcc, {vreg(T + mb)}, {sreg(S_ROWS)}")
+            I(f"v_cmp_eq_u32_e64 {sreg(S_MT, 2)}, {vreg(Q16)}, 0")           # (s[54:55]: free in the classic form)
+            I(f"s_and_b64 vcc, vcc, {sreg(S_MT, 2)}")
+            I(f"v_lshlrev_b32 {vreg(T + mb)}, 2, {vreg(T + mb)}")                       # byte offset of the row's sum
+            I("s_mov_b64 exec, vcc")
+            I(f"global_store_dword {vreg(T + mb)}, {vreg(ss)}, {sreg(S_SSQ, 2)}")
+            I("s_mov_b64 exec, -1")
+            q.append(("st", "ssq"))
+    elif epi == EPI_BIAS_SSQ:
         # row sum of the tile: (even + odd columns) of this half, + the other half of the wave (lanes r and r + 32 hold the two
         # halves of row r's columns); one 4-byte store per valid row from the lower half
         for mb in range(c.MB):
@@ -812,9 +920,9 @@ if __name__ == "__main__":
     if "--diag" in sys.argv:
         sys.argv.remove("--diag")                                            # (attn_asm_gen saw it at import: timing-only knobs allowed)
     WN, epi = int(sys.argv[1]), int(sys.argv[2])
-    i8 = len(sys.argv) > 5 and sys.argv[5] == "i8"
-    pers = len(sys.argv) > 5 and sys.argv[5] == "p"
-    txt = generate(WN, epi, f"GA{WN}E{epi}" + ("I8" if i8 else "") + ("P" if pers else ""), i8, pers)
+    form = sys.argv[5] if len(sys.argv) > 5 else ""                          # "", "i8", "p" (persistent), "m16" / "pm16" (16x16x32 MFMA shape)
+    i8, pers, mfma = form == "i8", form in ("p", "pm16"), 16 if form in ("m16", "pm16") else 32
+    txt = generate(WN, epi, f"GA{WN}E{epi}" + ("I8" if i8 else "") + ("P" if pers else "") + ("M16" if mfma == 16 else ""), i8, pers, mfma)
     probs = lint(txt)
     for p in probs[:20]:
         print("LINT:", p, file=sys.stderr)

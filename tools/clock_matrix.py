@@ -5,6 +5,7 @@ seconds on hash-normal data while the card's clock (hwmon + the eight XCDs' gfxc
 device in one gpurun call; prints one JSON line per load.
 
     python3 tools/clock_matrix.py [--seconds 2.5] [--loads attn,ffn1,ffn2,qkv,ffn1_hip,ffn2_hip,ffn1_i8_hip,ffn1_i8_gen,row]
+                                  [--mfma16 0,511 [--rounds 2]]      every load under each gemm_asm_mfma16 mask, interleaved
 """
 import argparse
 import json
@@ -31,6 +32,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.5)
     ap.add_argument("--loads", default="attn,ffn1,ffn2,qkv,ffn1_hip,ffn2_hip,ffn1_i8_hip,ffn1_i8_gen,ffn2_i8_hip,ffn2_i8_gen,row")
+    ap.add_argument("--mfma16", default="", help="comma list of gemm_asm_mfma16 masks: each load runs under each of them in turn")
+    ap.add_argument("--rounds", type=int, default=1)
     a = ap.parse_args()
     torch.cuda.set_device(0)
     lib = _lib.load()
@@ -51,11 +54,17 @@ def main():
     wo, bo = hn("wo", (C, C), 0.03), hn("bo", (C,), 0.1)
     ck, cv = hn("ck", (1, 512, H, D)), hn("cv", (1, 512, H, D), 0.5)
     a2 = ao.view(L, C)
+    EGR = ops.EPI_BIAS_GATE_RES
+    etab = hn("etab", (1, 3, 6, C), 0.5)
+    gate = dict(e=etab, mod=None, gate_idx=2, rows_per_batch=L, frame_len=L // 3)
     loads = {
         "attn": (lambda: ops.flash_attn(q, kc, vc, [(0, LK)], out=ao), 35, 4.0 * L * LK * D * H),
         "attn_hip": (lambda: ops.flash_attn(q, kc, vc, [(0, LK)], out=ao), -1, 4.0 * L * LK * D * H),      # attn_asm = 0: the HIP ping-pong kernel
         "cross": (lambda: ops.flash_attn(q, ck, cv, [(0, 512)], out=ao), 35, 4.0 * L * 512 * D * H),
         "o": (lambda: ops.gemm(a2, wo, bo, ER, out=o2, res=x), 35, 2.0 * L * C * C),
+        "o_gate": (lambda: ops.gemm(a2, wo, bo, EGR, out=o2, res=x, **gate), 35, 2.0 * L * C * C),                 # the self-attention output projection as the model calls it
+        "ffn2_gate": (lambda: ops.gemm(hid, w2, b2, EGR, out=o2, res=x, **gate), 35, 2.0 * L * FF * C),
+        "cq_ssq": (lambda: ops.gemm_ssq(x, wo, bo, out=o2), 35, 2.0 * L * C * C),                                 # cross-attention q projection + row sums of squares
         "o_hip": (lambda: ops.gemm(a2, wo, bo, ER, out=o2, res=x), 0, 2.0 * L * C * C),
         "qkv_hip": (lambda: ops.gemm(x, wq, bq, 0, out=o3), 0, 2.0 * L * 3 * C * C),
         "ffn1": (lambda: ops.gemm(x, w1, b1, EG, out=o1), 35, 2.0 * L * FF * C),
@@ -70,10 +79,13 @@ def main():
         "row": (lambda: ops.layernorm_affine(x, lnw, lnb, 1e-6, out=o2), 35, 0.0),
     }
     libname = os.environ.get("LONGLIVE_HIP_LIB", "shipped")
-    for name in a.loads.split(","):
+    masks = [int(m) for m in a.mfma16.split(",")] if a.mfma16 else [None]
+    for name, mask in [(n, m) for _ in range(a.rounds) for n in a.loads.split(",") for m in masks]:
         fn, asm, flops = loads[name]
         tune("attn_asm", 0 if asm < 0 else 1)
         tune("gemm_asm", 35 if asm < 0 else asm)
+        if mask is not None:
+            tune("gemm_asm_mfma16", mask)
         for _ in range(20):
             fn()
         torch.cuda.synchronize()
@@ -96,12 +108,13 @@ def main():
         t = tel.stop(0)
         us = e0.elapsed_time(e1) * 1e3 / n
         g = t.get("gpu_metrics_delta") or {}
-        rec = dict(lib=libname, load=name, gemm_asm=asm, us_per_launch=round(us, 2), tflops=round(flops / us * 1e-6, 1) if flops else None,
+        rec = dict(lib=libname, load=name, gemm_asm=asm, mfma16=mask, us_per_launch=round(us, 2), tflops=round(flops / us * 1e-6, 1) if flops else None,
                    sclk_mhz_avg=t.get("sclk_mhz_avg"), xcd_sclk_mhz_avg=t.get("xcd_sclk_mhz_avg"), power_w_avg=t.get("power_w_avg"),
                    ppt_residency=(g.get("ppt_residency_acc", 0) / max(1, g.get("accumulation_counter", 1))) if g else None,
                    energy_mj_per_launch=round((t.get("power_w_avg") or 0) * us * 1e-3, 2))
         print(json.dumps(rec), flush=True)
     tune("gemm_asm", 35)
+    tune("gemm_asm_mfma16", -1)
     tune("attn_asm", 1)
 
 
