@@ -24,6 +24,7 @@
 #include <string.h>
 #include <atomic>
 
+#include "gemm_asm.h"
 #include "gemm_common.h"
 #include "mx.h"
 
@@ -189,9 +190,6 @@ static int g_gemm_variant_wide = 0;  // like gemm_variant, but only for N >= 409
 // register form measured 1.6 % faster (FFN1 127.2 vs 129.3 us; everything else 1.5-11 % faster staged); 2: all; 0: none
 static int g_gemm_lds_epi = 1;
 static int g_gemm_asm = 35;        // generated kernels where they cover the call (bits 0, 1), persistent form for multi-round launches (bit 5)
-extern int g_gemm_asm_persistent;
-extern const int g_gemm_asm_mfma16_default;
-extern int g_gemm_asm_mfma16;      // bit mask: which generated bf16 kernels run their 16x16x32 MFMA form (gemm_asm.hip)
 static int g_gemm_group_m = 4;     // m-tiles per group in the workgroup -> tile walk (tile_of); <= 1: N fastest (round 1's order)
 void ll_set_attn_variant_internal(int v);
 void ll_set_attn_xcd_internal(int v);
@@ -450,22 +448,12 @@ extern "C" int ll_gemm_plan_f8(int M, int N, int K, char* out, int cap) {
 // `plain` = 1 when the call has no V-cache output and no per-batch modulation vector (the block linears of the pipeline except QKV).
 extern "C" int ll_gemm_plan_epi(int M, int N, int K, int int8, int epilogue, int plain, char* out, int cap);
 
+extern "C" int ll_t5_rmsnorm(const ll_bf16* x, const ll_bf16* w, ll_bf16* out, int rows, int C, float eps, ll_stream stream);
+
 // ===============================================================================================================
 // tuning key gemm_asm (declared near ll_set_tuning): bit 0 = bf16 block linears on the generated one-wave-per-SIMD kernels (gemm_asm.hip) where a
                                 // tile width fits (FFN1: 256 x 224 + GELU; N <= 2048: 256 x 128 with bias / gate-residual / residual);
                                 // (bit 1 was "also in place of the split-K kernel": that kernel is gone, experiments/gemm_r02_variants.hip)
-int gemm_asm_launch(const bf16* x, const bf16* w, bf16* out, int M, int N, int K, int ldx, int ldo, int epilogue, const EpiArgs& ea,
-                    int gm, hipStream_t s);
-int gemm_asm_width(int M, int N, int K, int ldx, int epilogue, bool plain, bool has_v, bool v_ok, int frame_len);
-int gemm_ksplit_splits(int M, int N, int K, int cus);
-int gemm_asm_launch_i8(const int8_t* x, const int8_t* w, bf16* out, int M, int N, int K, int ldo, int epilogue, const EpiArgs& ea,
-                       int gm, hipStream_t s);
-int gemm_asm_ksplit_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* out, int M, int N, int K, int ldx, int ldo,
-                           int epilogue, const bf16* res, float* workspace, int splits, int gm, hipStream_t s, const bf16* norm_w,
-                           float eps, bf16* h_out);
-extern "C" int ll_t5_rmsnorm(const ll_bf16* x, const ll_bf16* w, ll_bf16* out, int rows, int C, float eps, ll_stream stream);
-const char* gemm_asm_plan(int M, int N, int wn, int epilogue, char* out, int cap, bool i8);
-int gemm_asm_width_i8(int M, int N, int K, int epilogue, bool plain, bool has_v, bool v_ok, int frame_len);
 static bool gemm_asm_wanted(int epilogue) {
   return (g_gemm_asm & 1) && !((g_gemm_asm & 4) && epilogue == LL_EPI_BIAS_GELU) && !((g_gemm_asm & 8) && epilogue != LL_EPI_BIAS_GELU);
 }
@@ -590,14 +578,12 @@ extern "C" int ll_gemm_bf16(const ll_bf16* x, const ll_bf16* w, const ll_bf16* b
 
 // Small-M split-K (gemm_asm.hip): how many K-ranges the call would be cut into on this device (0 = the path is not taken: the
 // shape already fills half the device, N % 128, K too short, no device, or the generated kernels are switched off).
-static int device_cus();
 // ll_gemm_bf16 (LL_EPI_BIAS) that also leaves ssq[N / 128][M] (fp32): per row and 128-column n-tile the sum of squares of the bf16
 // outputs -- the statistics of the RMSNorm that follows the projection, applied by the consumer (ll_flash_attn_qnorm).
-int gemm_asm_ssq_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* out, float* ssq, int M, int N, int K, int ldx, int ldo, int gm,
-                        hipStream_t s);
 extern "C" int ll_gemm_ssq_planes(int M, int N, int K) {
   if (!gemm_asm_wanted(LL_EPI_BIAS)) return 0;
-  return gemm_asm_width(M, N, K, K, LL_EPI_BIAS, true, false, false, 0) == 128 && N / 128 <= 16 ? N / 128 : 0;
+  const GemmAsmPick p = gemm_asm_pick(GQ_BF16, M, N, K, K, LL_EPI_BIAS, true, false, false, 0, 0);      // the 128-wide bias row
+  return p.k && p.k->wn == 128 && N / 128 <= 16 ? N / 128 : 0;
 }
 extern "C" int ll_gemm_bf16_ssq(const ll_bf16* x, const ll_bf16* w, const ll_bf16* bias, ll_bf16* out, float* ssq, int M, int N, int K,
                                 int ldx, int ldo, ll_stream stream) {
@@ -675,33 +661,13 @@ extern "C" int ll_gemm_bf16_ksplit_t5norm(const ll_bf16* x, const ll_bf16* w, co
   return ll_t5_rmsnorm(out, norm_w, h_out, M, N, eps, stream);
 }
 
-// Split-K form of ll_gemm_bf16 (gemm_kernel_v4sk): same arguments plus a workspace.  Taken when N is a multiple of 256, K a
-// multiple of 128 and the 2 x (M / 256) x (N / 256) workgroups fit the device in one round; every other shape runs ll_gemm_bf16's
-// kernels (the workspace is then unused).  workspace: >= ll_gemm_splitk_workspace_bytes(M, N) bytes, 16-byte aligned, ZEROED
-// once by the caller before its first use (only the error word needs it: flags carry a per-launch epoch) and afterwards owned by
-// the launches of ONE stream.  ll_gemm_splitk_status() reports a timed-out hand-off.
-static int device_cus() {
-  static int cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus[dev] = n > 0 ? n : -1;
-  }
-  return cus[dev] > 0 ? cus[dev] : 0;
-}
-
 extern "C" int ll_gemm_plan_epi(int M, int N, int K, int int8, int epilogue, int plain, char* out, int cap) {
   LL_REQUIRE(out != nullptr && cap > 0, "ll_gemm_plan_epi: needs an output buffer");
-  if (!int8 && gemm_asm_wanted(epilogue)) {
+  if (gemm_asm_wanted(epilogue) && (!int8 || (g_gemm_asm & 16))) {      // bit 4: W8A8 calls on the generated kernels (launch_gemm<GQ_I8>; never the FP8 calls)
     // plain: 1 = an ordinary call, 0 = per-batch modulation vector (HIP kernels), 2 = the fused QKV call with its V redirect (B = 1)
-    const int wn = gemm_asm_width(M, N, K, K, epilogue, plain != 0, plain == 2, plain == 2 && (2 * (N / 3)) % 192 == 0, 1);
-    if (wn) { gemm_asm_plan(M, N, wn, epilogue, out, cap, false); ll_plan_append_knobs(out, cap); return LL_OK; }
-  }
-  if (int8 && (g_gemm_asm & 16) && gemm_asm_wanted(epilogue)) {      // bit 4: W8A8 calls on the generated kernels (launch_gemm<GQ_I8>; never the FP8 calls)
-    const int wn = gemm_asm_width_i8(M, N, K, epilogue, plain != 0, plain == 2, plain == 2 && (2 * (N / 3)) % 192 == 0, 1);
-    if (wn) { gemm_asm_plan(M, N, wn, epilogue, out, cap, true); ll_plan_append_knobs(out, cap); return LL_OK; }
+    const GemmAsmPick p = gemm_asm_pick(int8 ? GQ_I8 : GQ_BF16, M, N, K, K, epilogue, plain != 0, plain == 2, plain == 2 && (2 * (N / 3)) % 192 == 0,
+                                        1, int8 ? 0 : device_cus());
+    if (p.k) { gemm_asm_plan(p, out, cap); ll_plan_append_knobs(out, cap); return LL_OK; }
   }
   return ll_gemm_plan(M, N, K, int8, out, cap);
 }

@@ -1,259 +1,52 @@
 // Hand-scheduled bf16 GEMMs for the block linears on gfx950: 4 waves per 256 x WN output tile, one wave per SIMD, accumulators in
-// AGPRs, generated body (gen/gemm_asm_gen.py -> build/gemm_asm_<WN>_<EPI>.inc; structure, pipeline and CPU checks are described
-// there).  This file computes each workgroup's tile and scalar arguments, pins them to the registers the text expects and launches.
-// Replaces gemm_kernel_v5 / v2 for the shapes ll_gemm_bf16 routes here (tuning key gemm_asm); rounding points as gemm_common.h.
-#include "gemm_common.h"
+// AGPRs, generated body (gen/gemm_asm_gen.py -> build/gemm_asm_<WN>_<EPI>[_<form>].inc; structure, pipeline and CPU checks are
+// described there).  This file computes each workgroup's tile and scalar arguments, pins them to the registers the text expects and
+// launches.  Replaces gemm_kernel_v5 / v2 for the shapes ll_gemm_bf16 routes here (tuning key gemm_asm); rounding points as gemm_common.h.
+#include "gemm_asm.h"
 
-#define GA_NAME gemm_asm_224_gelu
-#define GA_WN 224
-#define GA_INC "build/gemm_asm_224_1.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_256_bias
-#define GA_WN 256
-#define GA_INC "build/gemm_asm_256_0.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_192_bias
-#define GA_WN 192
-#define GA_INC "build/gemm_asm_192_0.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_bias
-#define GA_WN 128
-#define GA_INC "build/gemm_asm_128_0.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_gate_res
-#define GA_WN 128
-#define GA_INC "build/gemm_asm_128_2.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_res
-#define GA_WN 128
-#define GA_INC "build/gemm_asm_128_3.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
+// the kernels, then their table: gemm_asm_kernels.def is the one list of both
+#define GA_EACH "gemm_asm_each.inl"
+#include "gemm_asm_kernels.def"
+static const GemmAsmKernel g_ga_kernels[] = {
+#define GA_TABLE
+#include "gemm_asm_kernels.def"
+#undef GA_TABLE
+};
+enum { GA_EPI_PARTIAL = 4, GA_EPI_SSQ = 5 };      // the generator's epilogue numbers past LL_EPI_*
 
-#define GA_NAME gemm_asmp_224_gelu
-#define GA_INC "build/gemm_asmp_224_1.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_192_bias
-#define GA_INC "build/gemm_asmp_192_0.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_128_bias
-#define GA_INC "build/gemm_asmp_128_0.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_128_gate_res
-#define GA_INC "build/gemm_asmp_128_2.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_128_res
-#define GA_INC "build/gemm_asmp_128_3.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-
-#define GA_NAME gemm_asm_128_bias_ssq
-#define GA_WN 128
-#define GA_INC "build/gemm_asm_128_5.inc"
-#define GA_SSQ 1
-#include "gemm_asm_kernel.inl"
-#undef GA_SSQ
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-
-#define GA_NAME gemm_asm_128_partial
-#define GA_WN 128
-#define GA_INC "build/gemm_asm_128_4.inc"
-#define GA_PARTIAL 1
-#include "gemm_asm_kernel.inl"
-#undef GA_PARTIAL
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-
-#define GA_NAME gemm_asmq_224_gelu
-#define GA_WN 224
-#define GA_INC "build/gemm_asmq_224_1.inc"
-#define GA_I8 1
-#include "gemm_asm_kernel.inl"
-#undef GA_I8
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asmq_192_bias
-#define GA_WN 192
-#define GA_INC "build/gemm_asmq_192_0.inc"
-#define GA_I8 1
-#include "gemm_asm_kernel.inl"
-#undef GA_I8
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asmq_128_bias
-#define GA_WN 128
-#define GA_INC "build/gemm_asmq_128_0.inc"
-#define GA_I8 1
-#include "gemm_asm_kernel.inl"
-#undef GA_I8
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asmq_128_gate_res
-#define GA_WN 128
-#define GA_INC "build/gemm_asmq_128_2.inc"
-#define GA_I8 1
-#include "gemm_asm_kernel.inl"
-#undef GA_I8
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asmq_128_res
-#define GA_WN 128
-#define GA_INC "build/gemm_asmq_128_3.inc"
-#define GA_I8 1
-#include "gemm_asm_kernel.inl"
-#undef GA_I8
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-
-// The bf16 kernels above once more on v_mfma_f32_16x16x32_bf16 (gen/gemm_asm_gen.py generate(..., mfma=16)): the same output tile per
-// wave, staging, tile walk and epilogue arithmetic; only the fragment and accumulator path differs.  The W8A8 and split-K partial
-// kernels have the 32-shape only.
-#define GA_NAME gemm_asm_224_gelu_m16
-#define GA_WN 224
-#define GA_INC "build/gemm_asm16_224_1.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_256_bias_m16
-#define GA_WN 256
-#define GA_INC "build/gemm_asm16_256_0.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_192_bias_m16
-#define GA_WN 192
-#define GA_INC "build/gemm_asm16_192_0.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_bias_m16
-#define GA_WN 128
-#define GA_INC "build/gemm_asm16_128_0.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_gate_res_m16
-#define GA_WN 128
-#define GA_INC "build/gemm_asm16_128_2.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_res_m16
-#define GA_WN 128
-#define GA_INC "build/gemm_asm16_128_3.inc"
-#include "gemm_asm_kernel.inl"
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asm_128_bias_ssq_m16
-#define GA_WN 128
-#define GA_INC "build/gemm_asm16_128_5.inc"
-#define GA_SSQ 1
-#include "gemm_asm_kernel.inl"
-#undef GA_SSQ
-#undef GA_NAME
-#undef GA_WN
-#undef GA_INC
-#define GA_NAME gemm_asmp_224_gelu_m16
-#define GA_INC "build/gemm_asmp16_224_1.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_192_bias_m16
-#define GA_INC "build/gemm_asmp16_192_0.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_128_bias_m16
-#define GA_INC "build/gemm_asmp16_128_0.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_128_gate_res_m16
-#define GA_INC "build/gemm_asmp16_128_2.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-#define GA_NAME gemm_asmp_128_res_m16
-#define GA_INC "build/gemm_asmp16_128_3.inc"
-#include "gemm_asm_kernel_p.inl"
-#undef GA_NAME
-#undef GA_INC
-
-int g_gemm_asm_persistent = 1;      // tuning key gemm_asm bit 5 (set from gemm.hip's ll_set_tuning)
-// tuning key gemm_asm_mfma16: which bf16 kernels run their 16x16x32 form, one bit per kernel (0 = every kernel on 32x32x16)
-enum { GA16_128_BIAS = 1, GA16_128_RES = 2, GA16_128_GATE_RES = 4, GA16_128_BIAS_SSQ = 8, GA16_192P = 16, GA16_192 = 32, GA16_224P = 64, GA16_224 = 128,
-       GA16_256 = 256 };
+int g_gemm_asm_persistent = 1;
 // the shipped mask (profiles/gemm_mfma16_ab.md; ll_set_tuning value -1 restores it): every bf16 kernel.  The family moves as one: the
 // suite holds its members to each other bit for bit (classic against persistent, the fused QKV projection on the 192-wide kernel
 // against the unfused one on the 128-wide, the row-sum kernel against the bias kernel), which needs one order of the fp32 sum.
 extern const int g_gemm_asm_mfma16_default = 511;
 int g_gemm_asm_mfma16 = g_gemm_asm_mfma16_default;
-static int gemm_asm_mfma16_bit(int wn, int epilogue, bool persistent) {
-  return wn == 224 ? (persistent ? GA16_224P : GA16_224) : wn == 192 ? (persistent ? GA16_192P : GA16_192) : wn == 256 ? GA16_256
-         : epilogue == LL_EPI_BIAS ? GA16_128_BIAS : epilogue == LL_EPI_BIAS_GATE_RES ? GA16_128_GATE_RES : GA16_128_RES;
-}
-static int gemm_asm_cus() {
-  static int cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus[dev] = n > 0 ? n : -1;
-  }
-  return cus[dev] > 0 ? cus[dev] : 0;
+
+// The 32-shape row of (kind, width, epilogue, form), or its MFMA-16 row where the tuning mask holds the row's bit; nullptr = no such
+// kernel.  (30 rows of 5 compares: nothing beside the launch it precedes.)
+static const GemmAsmKernel* ga_kernel(bool i8, int wn, int epilogue, bool persistent) {
+  const GemmAsmKernel* k32 = nullptr;
+  for (const GemmAsmKernel& k : g_ga_kernels)
+    if (k.i8 == i8 && k.wn == wn && k.epilogue == epilogue && k.persistent == persistent) {
+      if (!k.m16) k32 = &k;
+      else if (g_gemm_asm_mfma16 & k.mfma16_bit) return &k;
+    }
+  return k32;
 }
 
-// tile width of the generated kernel that covers this call, 0 = none (the caller takes the HIP kernels).
-// plain = no int8 scales, no per-batch modulation vector; v_ok = no V-cache output, or one the 192-wide kernel can redirect per
-// tile (one batch element, the V third starting on a tile boundary)
-int gemm_asm_width(int M, int N, int K, int ldx, int epilogue, bool plain, bool has_v, bool v_ok, int frame_len) {
-  if (!plain || M <= 0 || K % 64 != 0 || K < 256 || (ldx % 8) != 0) return 0;
+// dynamic LDS of a kernel of tile width wn.  gen/gemm_asm_gen.py Cfg.lds_bytes: 3 W slots of WN rows x 128 B + 2 X units of 8 KiB per wave
+static int ga_lds(int wn) { return 3 * wn * 128 + 4 * 2 * 8192; }
+
+// tile width of the generated kernel that covers this call, 0 = none
+static int ga_width(bool i8, int M, int N, int K, int ldx, int epilogue, bool plain, bool has_v, bool v_ok, int frame_len) {
+  const int kstep = i8 ? 128 : 64;      // elements of a K-step; the pipeline needs four.  Row offsets of a 256-row tile are 32-bit BYTE counts
+  if (!plain || M <= 0 || K % kstep != 0 || K < 4 * kstep) return 0;
+  if (i8 ? (long long)256 * K >= 0x7fffffffLL      // (W8A8 rows are dense: ldx = K)
+         : (ldx % 8) != 0 || (long long)256 * ldx * 2 >= 0x7fffffffLL || (long long)256 * K * 2 >= 0x7fffffffLL) return 0;
   if (epilogue == LL_EPI_BIAS_GATE_RES && frame_len <= 0) return 0;
-  if ((long long)256 * ldx * 2 >= 0x7fffffffLL || (long long)256 * K * 2 >= 0x7fffffffLL) return 0;
   if (has_v) return (v_ok && epilogue == LL_EPI_BIAS && N % 192 == 0) ? 192 : 0;
   if (epilogue == LL_EPI_BIAS_GELU) return N % 224 == 0 ? 224 : 0;
   if (epilogue == LL_EPI_BIAS && N > 2048 && N % 192 == 0) return 192;
+  if (i8) return N % 128 == 0 && N <= 2048 ? 128 : 0;      // W8A8: no 256-wide kernel, the 128-wide ones for any epilogue left
   if (epilogue == LL_EPI_BIAS && M <= 1024 && N >= 16384 && N % 256 == 0) return 256;      // umT5's gated FFN (512 x 20480 x 4096): 160 tiles of 256 x 256 in ONE round,
                                                                                              // half the L2 bytes per FLOP of the 128-wide kernel (which is L2-bound at ~29 B/clk/CU)
   if (N % 128 == 0 && (N <= 2048 || M <= 1024) &&      // wide outputs of few rows (umT5's gated FFN, 512 x 20480): the HIP choice there is 256 x 128 as well
@@ -261,100 +54,93 @@ int gemm_asm_width(int M, int N, int K, int ldx, int epilogue, bool plain, bool 
   return 0;
 }
 
-// 1 = launched; 0 = shape / epilogue not covered here (the caller takes the HIP kernels); < 0 = an LL_ERR_* code (attribute / launch failed)
+GemmAsmPick gemm_asm_pick(int kind, int M, int N, int K, int ldx, int epilogue, bool plain, bool has_v, bool v_ok, int frame_len, int cus) {
+  const bool i8 = kind == GQ_I8;
+  GemmAsmPick p{};
+  const int wn = ga_width(i8, M, N, K, ldx, epilogue, plain, has_v, v_ok, frame_len);
+  if (!wn) return p;
+  // the width fixes the epilogue of the 192 / 224 / 256 kernels; the 128-wide ones are bias, gate-res, or (everything else) res
+  const int epi = wn == 224 ? LL_EPI_BIAS_GELU : wn != 128 || epilogue == LL_EPI_BIAS ? LL_EPI_BIAS
+                  : epilogue == LL_EPI_BIAS_GATE_RES ? LL_EPI_BIAS_GATE_RES : LL_EPI_BIAS_RES;
+  p.ntm = (M + 255) / 256, p.ntn = N / wn, p.lds = ga_lds(wn);
+  // persistent form (tuning key gemm_asm bit 5, bf16 only): a launch with more tiles than CUs runs ONE workgroup per CU that walks its
+  // tiles and stages the next tile's first pieces under the current epilogue (FFN1: 760 tiles, QKV: 456, the recache forward's
+  // N = 1536 linears: 888) -- one pipeline fill per launch instead of one per round
+  const int pcus = cus & ~7;
+  if (!i8 && g_gemm_asm_persistent && pcus >= 8 && p.ntm * p.ntn > pcus) p.k = ga_kernel(i8, wn, epi, true);
+  p.grid = p.k ? pcus : p.ntm * p.ntn;
+  if (!p.k) p.k = ga_kernel(i8, wn, epi, false);
+  return p;
+}
+
+const char* gemm_asm_plan(const GemmAsmPick& p, char* out, int cap) {
+  const int wn = p.k->wn, tiles = p.ntm * p.ntn;
+  if (p.k->persistent)
+    snprintf(out, (size_t)cap, "%s<bf16> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d persistent workgroups "
+             "walk %d tiles, next tile staged under the epilogue", p.k->name, wn, p.grid, tiles);
+  else
+    snprintf(out, (size_t)cap, "%s<%s> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d workgroups", p.k->name,
+             p.k->i8 ? "i8" : "bf16", wn, tiles);
+  return out;
+}
+
+// The kernels' 22 common arguments in the wrappers' order (gemm_asm_kernel.inl), then the tail that only some rows read: sx, sw
+// (W8A8) or ssq (the row-sum kernel)
+struct GemmAsmArgs {
+  const void *x, *w;
+  const bf16* bias;
+  bf16* out;
+  const bf16 *res, *gate;
+  int M, N, K, ldx, ldo, frame_len, gate_stride, ntm, ntn, gm;
+  bf16* v_out;
+  int v_col0, v_C, v_shift, v_lo, v_hi;
+  const float *sx, *sw;
+  float* ssq;
+};
+
+// the one launch of a table row: 1 = launched, < 0 = an LL_ERR_* code
+static int ga_launch(const GemmAsmKernel& k, int grid, hipStream_t s, GemmAsmArgs& a, const char* what) {
+  const int lds = ga_lds(k.wn);
+  if (int rc = ll_lds_attr(k.fn, lds)) return rc;
+  void* args[] = {&a.x, &a.w, &a.bias, &a.out, &a.res, &a.gate, &a.M, &a.N, &a.K, &a.ldx, &a.ldo, &a.frame_len, &a.gate_stride, &a.ntm, &a.ntn,
+                  &a.gm, &a.v_out, &a.v_col0, &a.v_C, &a.v_shift, &a.v_lo, &a.v_hi, k.i8 ? (void*)&a.sx : (void*)&a.ssq, &a.sw};
+  if (hipLaunchKernel(k.fn, dim3(grid), dim3(256), args, (size_t)lds, s) != hipSuccess) return ll_check_launch(what);
+  return 1;
+}
+
+// ll_gemm_bf16 / ll_gemm_bf16_qkv (kind GQ_BF16) and ll_gemm_w8a8 / ll_gemm_w8a8_qkv (GQ_I8: int8 operands with row strides K, fp32
+// scales sx [M] / sw [N]; the same tile widths, epilogues and V-cache redirect.  Integer sums are exact and the epilogue applies
+// gemm_common.h's operations in its order, so the results are bit-identical to the HIP W8A8 kernels)
+static int ga_gemm(int kind, const void* x, const void* w, bf16* out, int M, int N, int K, int ldx, int ldo, int epilogue, const EpiArgs& ea,
+                   int gm, hipStream_t s) {
+  const bool has_v = ea.v_out != nullptr, i8 = kind == GQ_I8;
+  const GemmAsmPick p = gemm_asm_pick(kind, M, N, K, ldx, epilogue, ea.mod == nullptr && (i8 || ea.sx == nullptr), has_v,
+                                      has_v && ea.v_L == M && ea.v_col0 % 192 == 0 && ea.v_C > 0, ea.frame_len, i8 ? 0 : device_cus());
+  if (!p.k) return 0;
+  GemmAsmArgs a{x, w, ea.bias, out, ea.res, epilogue == LL_EPI_BIAS_GATE_RES ? ea.e + (size_t)ea.gate_idx * N : nullptr, M, N, K, ldx, ldo,
+                ea.frame_len, ea.nmod * N * 2, p.ntm, p.ntn, gm, ea.v_out, ea.v_col0, ea.v_C, ea.v_write_start - ea.v_roped_offset,
+                ea.v_roped_offset, ea.v_roped_offset + ea.v_write_len, ea.sx, ea.sw, nullptr};
+  return ga_launch(*p.k, p.grid, s, a, "gemm_asm");
+}
 int gemm_asm_launch(const bf16* x, const bf16* w, bf16* out, int M, int N, int K, int ldx, int ldo, int epilogue, const EpiArgs& ea,
                     int gm, hipStream_t s) {
-  const bool has_v = ea.v_out != nullptr;
-  const bool v_ok = has_v && ea.v_L == M && ea.v_col0 % 192 == 0 && ea.v_C > 0;
-  const int wn = gemm_asm_width(M, N, K, ldx, epilogue, ea.sx == nullptr && ea.mod == nullptr, has_v, v_ok, ea.frame_len);
-  if (!wn) return 0;
-  const void* fn = wn == 224 ? (const void*)gemm_asm_224_gelu
-                   : wn == 256 ? (const void*)gemm_asm_256_bias
-                   : wn == 192 ? (const void*)gemm_asm_192_bias
-                   : epilogue == LL_EPI_BIAS ? (const void*)gemm_asm_128_bias
-                   : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asm_128_gate_res : (const void*)gemm_asm_128_res;
-  const int lds = 3 * wn * 128 + 4 * 2 * 8192;      // gen/gemm_asm_gen.py Cfg.lds_bytes: 3 W slots of WN rows x 128 B + 2 X units of 8 KiB per wave
-  const int ntm = (M + 255) / 256, ntn = N / wn;
-  // persistent form (tuning key gemm_asm bit 5): a launch with more tiles than CUs runs ONE workgroup per CU that walks its tiles and
-  // stages the next tile's first pieces under the current epilogue (FFN1: 760 tiles, QKV: 456, the recache forward's N = 1536
-  // linears: 888) -- one pipeline fill per launch instead of one per round
-  const int cus = gemm_asm_cus() & ~7;
-  const void* pfn = wn == 224 ? (const void*)gemm_asmp_224_gelu
-                    : wn == 192 ? (const void*)gemm_asmp_192_bias
-                    : wn != 128 ? nullptr
-                    : epilogue == LL_EPI_BIAS ? (const void*)gemm_asmp_128_bias
-                    : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asmp_128_gate_res : (const void*)gemm_asmp_128_res;
-  const bool persistent = g_gemm_asm_persistent && pfn != nullptr && cus >= 8 && ntm * ntn > cus;
-  if (persistent) fn = pfn;
-  if (g_gemm_asm_mfma16 & gemm_asm_mfma16_bit(wn, epilogue, persistent)) {
-    if (persistent)
-      fn = wn == 224 ? (const void*)gemm_asmp_224_gelu_m16
-           : wn == 192 ? (const void*)gemm_asmp_192_bias_m16
-           : epilogue == LL_EPI_BIAS ? (const void*)gemm_asmp_128_bias_m16
-           : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asmp_128_gate_res_m16 : (const void*)gemm_asmp_128_res_m16;
-    else
-      fn = wn == 224 ? (const void*)gemm_asm_224_gelu_m16
-           : wn == 256 ? (const void*)gemm_asm_256_bias_m16
-           : wn == 192 ? (const void*)gemm_asm_192_bias_m16
-           : epilogue == LL_EPI_BIAS ? (const void*)gemm_asm_128_bias_m16
-           : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asm_128_gate_res_m16 : (const void*)gemm_asm_128_res_m16;
-  }
-  if (int rc = ll_lds_attr(fn, lds)) return rc;
-  const bf16* gate = epilogue == LL_EPI_BIAS_GATE_RES ? ea.e + (size_t)ea.gate_idx * N : nullptr;
-  const int gstride = ea.nmod * N * 2;
-  bf16* v_out = ea.v_out;
-  int v_col0 = ea.v_col0, v_C = ea.v_C, v_shift = ea.v_write_start - ea.v_roped_offset, v_lo = ea.v_roped_offset,
-      v_hi = ea.v_roped_offset + ea.v_write_len;
-  void* args[] = {(void*)&x, (void*)&w, (void*)&ea.bias, (void*)&out, (void*)&ea.res, (void*)&gate, (void*)&M, (void*)&N, (void*)&K,
-                  (void*)&ldx, (void*)&ldo, (void*)&ea.frame_len, (void*)&gstride, (void*)&ntm, (void*)&ntn, (void*)&gm,
-                  (void*)&v_out, (void*)&v_col0, (void*)&v_C, (void*)&v_shift, (void*)&v_lo, (void*)&v_hi};
-  if (hipLaunchKernel(fn, dim3(persistent ? cus : ntm * ntn), dim3(256), args, (size_t)lds, s) != hipSuccess) return ll_check_launch("gemm_asm");
-  return 1;
+  return ga_gemm(GQ_BF16, x, w, out, M, N, K, ldx, ldo, epilogue, ea, gm, s);
+}
+int gemm_asm_launch_i8(const int8_t* x, const int8_t* w, bf16* out, int M, int N, int K, int ldo, int epilogue, const EpiArgs& ea,
+                       int gm, hipStream_t s) {
+  if (ea.sx == nullptr || ea.sw == nullptr) return 0;
+  return ga_gemm(GQ_I8, x, w, out, M, N, K, K, ldo, epilogue, ea, gm, s);
 }
 
 // The bias kernel that also leaves per-row sums of squares of its outputs: ssq[N / 128][M] fp32 (plane = n-tile).  1 = launched,
 // 0 = not covered, < 0 = error.
 int gemm_asm_ssq_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* out, float* ssq, int M, int N, int K, int ldx, int ldo, int gm,
                         hipStream_t s) {
-  if (gemm_asm_width(M, N, K, ldx, LL_EPI_BIAS, true, false, false, 0) != 128) return 0;
-  const bool m16 = (g_gemm_asm_mfma16 & GA16_128_BIAS_SSQ) != 0;
-  const void* fn = m16 ? (const void*)gemm_asm_128_bias_ssq_m16 : (const void*)gemm_asm_128_bias_ssq;
-  const int lds = 3 * 128 * 128 + 4 * 2 * 8192;
-  if (int rc = ll_lds_attr(fn, lds)) return rc;
-  const int ntm = (M + 255) / 256, ntn = N / 128;
-  const bf16* nullb = nullptr;
-  bf16* nov = nullptr;
-  int zero = 0;
-  void* args[] = {(void*)&x, (void*)&w, (void*)&bias, (void*)&out, (void*)&nullb, (void*)&nullb, (void*)&M, (void*)&N, (void*)&K,
-                  (void*)&ldx, (void*)&ldo, (void*)&zero, (void*)&zero, (void*)&ntm, (void*)&ntn, (void*)&gm,
-                  (void*)&nov, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&ssq};
-  if (hipLaunchKernel(fn, dim3(ntm * ntn), dim3(256), args, (size_t)lds, s) != hipSuccess) return ll_check_launch(m16 ? "gemm_asm_128_bias_ssq_m16" : "gemm_asm_128_bias_ssq");
-  return 1;
-}
-
-const char* gemm_asm_plan(int M, int N, int wn, int epilogue, char* out, int cap, bool i8) {
-  const char* tail = wn == 224 ? "gelu" : wn == 256 ? "bias" : epilogue == LL_EPI_BIAS ? "bias" : epilogue == LL_EPI_BIAS_GATE_RES ? "gate_res" : "res";      // wn == 192: bias
-  const int tiles = ((M + 255) / 256) * (N / wn), cus = gemm_asm_cus() & ~7;
-  const bool persistent = !i8 && g_gemm_asm_persistent && wn != 256 && cus >= 8 && tiles > cus;
-  const char* m16 = !i8 && (g_gemm_asm_mfma16 & gemm_asm_mfma16_bit(wn, epilogue, persistent)) ? "_m16" : "";      // the kernel gemm_asm_launch takes
-  if (persistent)
-    snprintf(out, (size_t)cap, "gemm_asmp_%d_%s%s<bf16> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d persistent workgroups "
-             "walk %d tiles, next tile staged under the epilogue", wn, tail, m16, wn, cus, tiles);
-  else
-    snprintf(out, (size_t)cap, "gemm_asm%s_%d_%s%s<%s> tile 256x%d (4 waves x 64 rows, one wave per SIMD, generated schedule), %d workgroups", i8 ? "q" : "", wn,
-             tail, m16, i8 ? "i8" : "bf16", wn, tiles);
-  return out;
-}
-
-// tile width gemm_asm_launch_i8 takes for a W8A8 call (0 = not covered): the same rule as in that launcher
-int gemm_asm_width_i8(int M, int N, int K, int epilogue, bool plain, bool has_v, bool v_ok, int frame_len) {
-  if (!plain || M <= 0 || K % 128 != 0 || K < 512 || (long long)256 * K >= 0x7fffffffLL) return 0;
-  if (epilogue == LL_EPI_BIAS_GATE_RES && frame_len <= 0) return 0;
-  if (has_v) return (v_ok && epilogue == LL_EPI_BIAS && N % 192 == 0) ? 192 : 0;
-  if (epilogue == LL_EPI_BIAS_GELU) return N % 224 == 0 ? 224 : 0;
-  if (epilogue == LL_EPI_BIAS && N > 2048 && N % 192 == 0) return 192;
-  if (N % 128 == 0 && N <= 2048) return 128;
-  return 0;
+  const GemmAsmPick p = gemm_asm_pick(GQ_BF16, M, N, K, ldx, LL_EPI_BIAS, true, false, false, 0, 0);      // (cus = 0: no persistent row-sum kernel)
+  if (!p.k || p.k->wn != 128) return 0;
+  const GemmAsmKernel* k = ga_kernel(false, 128, GA_EPI_SSQ, false);
+  GemmAsmArgs a{x, w, bias, out, nullptr, nullptr, M, N, K, ldx, ldo, 0, 0, p.ntm, p.ntn, gm, nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, ssq};
+  return ga_launch(*k, p.grid, s, a, k->name);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -454,25 +240,19 @@ int gemm_ksplit_splits(int M, int N, int K, int cus) {
   if (S < 2 || tiles * S > 2 * cus) return 0;
   return S;
 }
-
 // 1 = launched (two launches), 0 = not covered, < 0 = an LL_ERR_* code
 int gemm_asm_ksplit_launch(const bf16* x, const bf16* w, const bf16* bias, bf16* out, int M, int N, int K, int ldx, int ldo,
                            int epilogue, const bf16* res, float* workspace, int splits, int gm, hipStream_t s, const bf16* norm_w,
                            float eps, bf16* h_out) {
   if (splits < 2 || (epilogue != LL_EPI_BIAS && epilogue != LL_EPI_BIAS_RES) || (ldx % 8) != 0) return 0;      // (ldo % 8 == 0: check_epilogue)
   if ((long long)256 * ldx * 2 >= 0x7fffffffLL || (long long)256 * K * 2 >= 0x7fffffffLL) return 0;
-  const int lds = 3 * 128 * 128 + 4 * 2 * 8192;
-  if (int rc = ll_lds_attr((const void*)gemm_asm_128_partial, lds)) return rc;
+  const GemmAsmKernel* k = ga_kernel(false, 128, GA_EPI_PARTIAL, false);
   const int ntm = (M + 255) / 256, ntn = N / 128, per = (K / 64 + splits - 1) / splits;
-  const bf16* nullb = nullptr;
-  bf16* ws = (bf16*)workspace;
-  bf16* nov = nullptr;
-  int zero = 0, ldw = N, flen = 0;
-  void* args[] = {(void*)&x, (void*)&w, (void*)&nullb, (void*)&ws, (void*)&nullb, (void*)&nullb, (void*)&M, (void*)&N, (void*)&K,
-                  (void*)&ldx, (void*)&ldw, (void*)&flen, (void*)&zero, (void*)&ntm, (void*)&ntn, (void*)&gm,
-                  (void*)&nov, (void*)&per, (void*)&zero, (void*)&zero, (void*)&zero, (void*)&zero};
-  if (hipLaunchKernel((const void*)gemm_asm_128_partial, dim3(ntm * ntn * splits), dim3(256), args, (size_t)lds, s) != hipSuccess)
-    return ll_check_launch("gemm_asm_128_partial");
+  // the partial kernel reuses three slots (GA_PARTIAL in gemm_asm_kernel.inl): Y is the fp32 workspace [splits][M][N], ldo = N counts
+  // FLOATS, and v_col0 carries the number of K-steps per split
+  GemmAsmArgs a{x, w, nullptr, (bf16*)workspace, nullptr, nullptr, M, N, K, ldx, /*ldo*/ N, 0, 0, ntm, ntn, gm, nullptr, /*v_col0*/ per, 0, 0, 0, 0,
+                nullptr, nullptr, nullptr};
+  if (int rc = ga_launch(*k, ntm * ntn * splits, s, a, k->name); rc != 1) return rc;
   const long long threads = (long long)M * (N / 8);
   dim3 grid((unsigned)((threads + 255) / 256)), block(256);
   if (norm_w != nullptr)       // (the caller checked: bias + residual, N <= 4096)
@@ -482,34 +262,5 @@ int gemm_asm_ksplit_launch(const bf16* x, const bf16* w, const bf16* bias, bf16*
     hipLaunchKernelGGL((gemm_ksplit_reduce_kernel<LL_EPI_BIAS_RES>), grid, block, 0, s, (const float*)workspace, splits, M, N, bias, res, out, ldo);
   else
     hipLaunchKernelGGL((gemm_ksplit_reduce_kernel<LL_EPI_BIAS>), grid, block, 0, s, (const float*)workspace, splits, M, N, bias, res, out, ldo);
-  return 1;
-}
-
-// W8A8 form of gemm_asm_launch (ll_gemm_w8a8 / ll_gemm_w8a8_qkv): int8 operands with row strides K, fp32 scales sx [M] / sw [N];
-// the same tile widths, epilogues and V-cache redirect.  Integer sums are exact and the epilogue applies gemm_common.h's operations
-// in its order, so the results are bit-identical to the HIP W8A8 kernels.  1 = launched, 0 = not covered.
-int gemm_asm_launch_i8(const int8_t* x, const int8_t* w, bf16* out, int M, int N, int K, int ldo, int epilogue, const EpiArgs& ea,
-                       int gm, hipStream_t s) {
-  if (ea.sx == nullptr || ea.sw == nullptr) return 0;
-  const bool has_v = ea.v_out != nullptr;
-  const int wn = gemm_asm_width_i8(M, N, K, epilogue, ea.mod == nullptr, has_v, has_v && ea.v_L == M && ea.v_col0 % 192 == 0 && ea.v_C > 0,
-                                   ea.frame_len);
-  if (!wn) return 0;
-  const void* fn = wn == 224 ? (const void*)gemm_asmq_224_gelu
-                   : wn == 192 ? (const void*)gemm_asmq_192_bias
-                   : epilogue == LL_EPI_BIAS ? (const void*)gemm_asmq_128_bias
-                   : epilogue == LL_EPI_BIAS_GATE_RES ? (const void*)gemm_asmq_128_gate_res : (const void*)gemm_asmq_128_res;
-  const int lds = 3 * wn * 128 + 4 * 2 * 8192;
-  if (int rc = ll_lds_attr(fn, lds)) return rc;
-  const int ntm = (M + 255) / 256, ntn = N / wn;
-  const bf16* gate = epilogue == LL_EPI_BIAS_GATE_RES ? ea.e + (size_t)ea.gate_idx * N : nullptr;
-  const int gstride = ea.nmod * N * 2;
-  bf16* v_out = ea.v_out;
-  int v_col0 = ea.v_col0, v_C = ea.v_C, v_shift = ea.v_write_start - ea.v_roped_offset, v_lo = ea.v_roped_offset,
-      v_hi = ea.v_roped_offset + ea.v_write_len, ldx = K;
-  void* args[] = {(void*)&x, (void*)&w, (void*)&ea.bias, (void*)&out, (void*)&ea.res, (void*)&gate, (void*)&M, (void*)&N, (void*)&K,
-                  (void*)&ldx, (void*)&ldo, (void*)&ea.frame_len, (void*)&gstride, (void*)&ntm, (void*)&ntn, (void*)&gm,
-                  (void*)&v_out, (void*)&v_col0, (void*)&v_C, (void*)&v_shift, (void*)&v_lo, (void*)&v_hi, (void*)&ea.sx, (void*)&ea.sw};
-  if (hipLaunchKernel(fn, dim3(ntm * ntn), dim3(256), args, (size_t)lds, s) != hipSuccess) return ll_check_launch("gemm_asm");
   return 1;
 }

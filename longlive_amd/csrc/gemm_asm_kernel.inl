@@ -1,4 +1,4 @@
-// included by gemm_asm.hip once per (tile width, epilogue) with GA_NAME / GA_WN / GA_INC defined; GA_PARTIAL: the split-K form that
+// included once per entry of gemm_asm_kernels.def (gemm_asm_each.inl) with GA_NAME / GA_WN / GA_INC defined; GA_PARTIAL: the split-K form that
 // stores fp32 accumulators; GA_I8: W8A8 operands (X, W int8 with row strides in BYTES = elements, K-steps of 128, sx / sw scales)
 __global__ __launch_bounds__(256, 1) void GA_NAME(const bf16* __restrict__ X, const bf16* __restrict__ W,
                                                   const bf16* __restrict__ bias, bf16* __restrict__ Y,

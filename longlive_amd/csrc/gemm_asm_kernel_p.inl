@@ -1,4 +1,4 @@
-// included by gemm_asm.hip once per (tile width, epilogue) with GA_NAME / GA_INC defined: the PERSISTENT form of the generated GEMM
+// included once per P entry of gemm_asm_kernels.def (gemm_asm_each.inl) with GA_NAME / GA_INC defined: the PERSISTENT form of the generated GEMM
 // (gen/gemm_asm_gen.py generate(persistent=True)).  The text maps tiles to (m-tile, n-tile) itself and computes every per-tile
 // scalar -- incl. the V-cache redirect of the fused QKV projection -- so this wrapper only pins the launch's arguments.
 __global__ __launch_bounds__(256, 1) void GA_NAME(const bf16* __restrict__ X, const bf16* __restrict__ W,

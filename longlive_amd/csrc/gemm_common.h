@@ -34,6 +34,19 @@ __device__ __forceinline__ bf16* epi_dest(const EpiArgs& ea, bf16* __restrict__ 
   return ea.v_out + ((size_t)bb * ea.v_S + ea.v_write_start + wi) * (size_t)ea.v_C + (n - ea.v_col0);
 }
 
+// compute units of the current device, asked once per device; 0 = no device
+inline int device_cus() {
+  static int cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+    cus[dev] = n > 0 ? n : -1;
+  }
+  return cus[dev] > 0 ? cus[dev] : 0;
+}
+
 // Host side of the V redirect, shared by every ll_gemm_*_qkv entry point: the checks of the insert window, and the fill of EpiArgs.
 static inline int check_v_insert(const char* fn, int M, int N, int B, int L, int S, int write_start, int roped_offset, int write_len,
                           const void* cache_v) {
