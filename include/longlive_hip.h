@@ -52,7 +52,8 @@ enum ll_epilogue {
  * 111 = MXFP4 weights over MXFP6 activations (ll_quantize_mx4, ll_gemm_mx4w6, ll_gemm_mx4w6_qkv, ll_gemm_plan_mx4w6); W4A4 block
  * linears (ll_gemm_mx4, ll_gemm_mx4_qkv, ll_ln_modulate_mx4, ll_ln_modulate_tab_mx4, ll_layernorm_affine_mx4, ll_gemm_plan_mx4) only
  * add entry points, so they keep 111; so does ll_conv_plan, and so do the VAE encoder's entry points (ll_conv_cl_down, ll_conv_cl_tdown,
- * ll_conv_down_plan, ll_pixels_to_cl, ll_vae_scale_tchw). */
+ * ll_conv_down_plan, ll_pixels_to_cl, ll_vae_scale_tchw), and so do the attention entry points with quantised output
+ * (ll_flash_attn_q_ok, ll_flash_attn_q, ll_flash_attn_q_plan, ll_flash_attn_mx_q): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -414,6 +415,31 @@ int ll_flash_attn_qnorm_ok(int H, int nkeys);
 int ll_flash_attn_qnorm(const ll_bf16* q, const float* ssq, const ll_bf16* norm_w, float eps, const ll_bf16* k, const ll_bf16* v,
                         ll_bf16* out, int B, int Lq, int H, int ldq, int ldo, int ldk, long long k_batch_stride, int key_start,
                         int nkeys, float scale, ll_stream stream);
+
+/* Attention whose epilogue writes what the NEXT GEMM reads in the block-scaled modes: instead of the bf16 rows [B, Lq, H*128] the
+ * codes and E8M0 scale bytes ll_quantize_mx / _mx6 / _mx4 would make of them (same layouts: codes [B*Lq][ldc bytes], H*128 codes of
+ * 8 / 6 / 4 bits per row, packed formats in 256-k super-blocks; scales [B*Lq][lds bytes], one byte per 32 channels).  Contract: the
+ * pair is bit-identical to ll_quantize_<fmt>(ll_flash_attn(...)) (ll_flash_attn_mx for the _mx_q form) under the same tuning -- the
+ * kernel rounds O / l to bf16 as its bf16 twin does and applies the format's rule to the rounded values.  A scale block is 32 channels
+ * of one row and a head is 128, so a workgroup owns whole blocks; head h owns blocks 4 (h & 1) + (0..3) of super-block h >> 1, hence
+ * the packed formats need an even H.  Rows of the buffers outside [0, B*Lq) and bytes outside the H heads' are not written.
+ *   ll_flash_attn_q_ok: 1 exactly when the generated gfx950 kernel takes the launch under the current tuning: the key ranges are
+ *       one contiguous range after merging adjacent ones, that range is long enough for it (tuning key attn_asm_min_keys, at least
+ *       two key tiles), H is even for LL_QFMT_MX6 / MX4.  Otherwise 0, and the caller runs ll_flash_attn + ll_quantize_<fmt>:
+ *   ll_flash_attn_q returns LL_ERR_INVALID_ARG where ll_flash_attn_q_ok is 0 (no fall-back inside the library).  ldc: a multiple of
+ *       16 bytes, lds: a multiple of 4.
+ *   ll_flash_attn_q_plan: the kernel and grid of such a launch, or that it is not covered (host only).
+ *   ll_flash_attn_mx_q: ll_flash_attn_mx with the same output forms; every launch ll_flash_attn_mx takes is covered (even H for the
+ *       packed formats). */
+enum ll_qfmt { LL_QFMT_MX = 1, LL_QFMT_MX6 = 2, LL_QFMT_MX4 = 3 };
+int ll_flash_attn_q_ok(int fmt, int H, int seg0_start, int seg0_len, int seg1_start, int seg1_len);
+int ll_flash_attn_q_plan(int fmt, int Lq, int H, int B, int seg0_start, int seg0_len, int seg1_start, int seg1_len, char* out, int cap);
+int ll_flash_attn_q(int fmt, const ll_bf16* q, const ll_bf16* k, const ll_bf16* v, uint8_t* codes, uint8_t* scales, int B, int Lq, int H,
+                    int ldq, int ldc, int lds, int ldk, long long k_batch_stride, int seg0_start, int seg0_len, int seg1_start,
+                    int seg1_len, float scale, ll_stream stream);
+int ll_flash_attn_mx_q(int fmt, const ll_bf16* q, const uint8_t* kq, const uint8_t* ks, const uint8_t* vq, const uint8_t* vs,
+                       uint8_t* codes, uint8_t* scales, int B, int Lq, int H, int head_dim, int ldq, int ldc, int lds, int S, int S32,
+                       int seg0_start, int seg0_len, int seg1_start, int seg1_len, float scale, ll_stream stream);
 
 /* ---- embeddings / head / scheduler ------------------------------------------------------------------------------ */
 

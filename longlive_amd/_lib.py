@@ -54,6 +54,10 @@ SIGNATURES = {
     "ll_gemm_bf16_ssq": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ll_flash_attn_qnorm_ok": [_i, _i],
     "ll_flash_attn_qnorm": [_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _i, _i, _ll, _i, _i, _f, _p],
+    "ll_flash_attn_q_ok": [_i] * 6,
+    "ll_flash_attn_q_plan": [_i] * 8 + [C.c_char_p, _i],
+    "ll_flash_attn_q": [_i] + [_p] * 5 + [_i] * 7 + [_ll] + [_i] * 4 + [_f, _p],
+    "ll_flash_attn_mx_q": [_i] + [_p] * 7 + [_i] * 13 + [_f, _p],
     "ll_conv_plan": [_i] * 10 + [C.c_char_p, _i],
     "ll_conv_cl": [_p] * 6 + [_i] * 10 + [_p],
     "ll_conv_cl_rms_ok": [_i] * 7,

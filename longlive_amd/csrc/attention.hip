@@ -778,3 +778,61 @@ extern "C" int ll_flash_attn_qnorm(const ll_bf16* q, const float* ssq, const ll_
                                   ldq, ldo, ldk, k_batch_stride, key_start, nkeys, scale * 1.4426950408889634f, g_attn_xcd,
                                   (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Attention that emits what the output projection reads in the block-scaled modes: the codes + E8M0 scales of the bf16 rows
+// ll_flash_attn would have written (mx.h / mx6.h / mx4.h), so the stand-alone ll_quantize_mx* pass over them disappears.  A scale block
+// is 32 channels of one row and a head is 128: the four blocks of a (row, head) live in the workgroup that computes the head.  Only the
+// generated kernel has this epilogue: ll_flash_attn_q_ok says whether a launch is covered.
+int flash_attn_asm_q_launch(int fmt, const bf16* q, const bf16* k, const bf16* v, uint8_t* codes, int ldc, uint8_t* scales, int lds, int B,
+                            int Lq, int H, int ldq, int ldk, long long k_batch_stride, int kstart, int nkeys, float c, int xcd,
+                            hipStream_t stream);
+static int qfmt_bits(int fmt) { return fmt == LL_QFMT_MX ? 8 : fmt == LL_QFMT_MX6 ? 6 : fmt == LL_QFMT_MX4 ? 4 : 0; }
+static const char* qfmt_name(int fmt) { return fmt == LL_QFMT_MX ? "mx" : fmt == LL_QFMT_MX6 ? "mx6" : "mx4"; }
+// one contiguous key range (after merging adjacent ones) that the generated kernel takes; packed formats pair heads in a super-block
+static bool attn_q_covered(int fmt, int H, int ldk, int s0, int n0, int s1, int n1, int* start, int* nkeys) {
+  if (!qfmt_bits(fmt) || H < 1 || n0 <= 0 || n1 < 0 || s0 < 0 || s1 < 0) return false;
+  if (n1 > 0 && s1 == s0 + n0) { n0 += n1; n1 = 0; }
+  if (n1 > 0 || (fmt != LL_QFMT_MX && (H & 1))) return false;
+  if (start) *start = s0;
+  if (nkeys) *nkeys = n0;
+  return attn_asm_eligible(n0, ldk);
+}
+extern "C" int ll_flash_attn_q_ok(int fmt, int H, int seg0_start, int seg0_len, int seg1_start, int seg1_len) {
+  return attn_q_covered(fmt, H, H * 128, seg0_start, seg0_len, seg1_start, seg1_len, nullptr, nullptr) ? 1 : 0;
+}
+extern "C" int ll_flash_attn_q_plan(int fmt, int Lq, int H, int B, int seg0_start, int seg0_len, int seg1_start, int seg1_len, char* out,
+                                    int cap) {
+  LL_REQUIRE(out != nullptr && cap > 0, "ll_flash_attn_q_plan: needs an output buffer");
+  LL_REQUIRE(qfmt_bits(fmt) != 0, "ll_flash_attn_q_plan: fmt=%d is none of LL_QFMT_MX / MX6 / MX4", fmt);
+  if (ll_flash_attn_q_ok(fmt, H, seg0_start, seg0_len, seg1_start, seg1_len))
+    snprintf(out, (size_t)cap, "flash_attn_asm_%s_kernel (4 waves x 64 rows, one wave per SIMD, generated schedule, %d-bit codes + E8M0 "
+             "scales from the epilogue), %d workgroups of 256 query rows%s", qfmt_name(fmt), qfmt_bits(fmt), ((Lq + 255) / 256) * H * B,
+             g_attn_xcd ? ", XCD-aware placement" : ""), ll_plan_append_knobs(out, cap);
+  else
+    snprintf(out, (size_t)cap, "not covered by the generated kernel: ll_flash_attn + ll_quantize_%s", qfmt_name(fmt));
+  return LL_OK;
+}
+extern "C" int ll_flash_attn_q(int fmt, const ll_bf16* q, const ll_bf16* k, const ll_bf16* v, uint8_t* codes, uint8_t* scales, int B, int Lq,
+                               int H, int ldq, int ldc, int lds, int ldk, long long k_batch_stride, int seg0_start, int seg0_len,
+                               int seg1_start, int seg1_len, float scale, ll_stream stream) {
+  const int bits = qfmt_bits(fmt);
+  LL_REQUIRE(bits != 0, "ll_flash_attn_q: fmt=%d is none of LL_QFMT_MX / MX6 / MX4", fmt);
+  LL_REQUIRE(q != nullptr && k != nullptr && v != nullptr && codes != nullptr && scales != nullptr, "ll_flash_attn_q: q, k, v, codes and "
+             "scales are required");
+  LL_REQUIRE(B >= 0 && Lq >= 0 && H > 0, "ll_flash_attn_q: B=%d Lq=%d H=%d", B, Lq, H);
+  LL_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldq >= H * 128 && ldk >= H * 128, "ll_flash_attn_q: row strides ldq=%d ldk=%d (>= H*128, "
+             "multiples of 8)", ldq, ldk);
+  LL_REQUIRE(ldc % 16 == 0 && ldc >= H * 16 * bits && lds % 4 == 0 && lds >= H * 4, "ll_flash_attn_q: code row stride %d bytes (>= %d, a "
+             "multiple of 16) or scale row stride %d bytes (>= %d, a multiple of 4)", ldc, H * 16 * bits, lds, H * 4);
+  LL_REQUIRE(seg1_len <= 0 || seg1_start >= seg0_start + seg0_len || seg1_start + seg1_len <= seg0_start, "ll_flash_attn_q: key ranges "
+             "[%d, +%d) and [%d, +%d) overlap", seg0_start, seg0_len, seg1_start, seg1_len);
+  int kstart = 0, nkeys = 0;
+  LL_REQUIRE(attn_q_covered(fmt, H, ldk, seg0_start, seg0_len, seg1_start, seg1_len, &kstart, &nkeys), "ll_flash_attn_q: key ranges "
+             "[%d, +%d) [%d, +%d) x %d heads in format %s are not covered by the generated kernel under the current tuning (ask "
+             "ll_flash_attn_q_ok first and run ll_flash_attn + ll_quantize_%s instead)", seg0_start, seg0_len, seg1_start, seg1_len, H,
+             qfmt_name(fmt), qfmt_name(fmt));
+  if (B == 0 || Lq == 0) return LL_OK;
+  return flash_attn_asm_q_launch(fmt, (const bf16*)q, (const bf16*)k, (const bf16*)v, codes, ldc, scales, lds, B, Lq, H, ldq, ldk,
+                                 k_batch_stride, kstart, nkeys, scale * 1.4426950408889634f, g_attn_xcd, (hipStream_t)stream);
+}

@@ -27,6 +27,8 @@
 
 #include "common.h"
 #include "mx.h"
+#include "mx4.h"
+#include "mx6.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4v;
@@ -156,10 +158,14 @@ __device__ __forceinline__ float fp8x4_sum(uint32_t w) {
     if (tid < 128) *reinterpret_cast<uint32_t*>((ST) + MXA_KB + MXA_VB + tid * 4) = sr;                             \
   }
 
+// OUTF: 0 = bf16 rows O [.., ldo elements]; LL_QFMT_MX / MX6 / MX4 = the quantiser's codes of those rows, O as bytes with ldo BYTES per
+// row, and their E8M0 scale bytes sc [.., ldsc bytes] (ll_flash_attn_mx_q)
+template <int OUTF>
 __global__ __launch_bounds__(MXA_NW * 64, 2) void flash_attn_mx_kernel(const bf16* __restrict__ Q, const uint8_t* __restrict__ kq,
                                                                        const uint8_t* __restrict__ ks, const uint8_t* __restrict__ vq,
                                                                        const uint8_t* __restrict__ vs, bf16* __restrict__ O, int Lq,
-                                                                       int ldq, int ldo, int H, int S32, MxSegs sg, float c) {
+                                                                       int ldq, int ldo, int H, int S32, MxSegs sg, float c,
+                                                                       uint8_t* __restrict__ sc, int ldsc) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 stages][K^ | V^ | K^ scales | V^ scales]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -322,18 +328,68 @@ __global__ __launch_bounds__(MXA_NW * 64, 2) void flash_attn_mx_kernel(const bf1
 
   // ---- epilogue: O^T[d][q] / l -> out[q][head * 128 + d]; lane holds d = 32 db + 8 g4 + 4 h + (0..3) -------------------------
   const int qr = q0 + r;
-  if (qr < Lq) {
+  if constexpr (OUTF == 0) {
+    if (qr < Lq) {
+      const float inv = 1.0f / l_run;
+      bf16* op = O + ((size_t)b * Lq + qr) * ldo + head * 128 + 4 * h;
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          bf16x4 w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w[j] = (bf16)(o[db][4 * g4 + j] * inv);
+          *reinterpret_cast<bf16x4*>(op + 32 * db + 8 * g4) = w;
+        }
+    }
+  } else {
+    // The same bf16 values, quantised per 32-channel block db: the lane (r, 1 - h) holds the block's other 16 values (one lane ^ 32
+    // step for the maximum); the pieces of g4 = 0, 1 and of g4 = 2, 3 are exchanged so that lane h stores channels 16 h .. 16 h + 15 of
+    // the block in one piece.  Every lane takes part in the exchanges; only rows < Lq store.
+    const bool live = qr < Lq;
     const float inv = 1.0f / l_run;
-    bf16* op = O + ((size_t)b * Lq + qr) * ldo + head * 128 + 4 * h;
+    const size_t row = (size_t)b * Lq + (live ? qr : 0);
+    uint8_t* cp = reinterpret_cast<uint8_t*>(O) + row * ldo +
+                  (OUTF == LL_QFMT_MX ? head * 128 + 16 * h
+                                      : OUTF == LL_QFMT_MX6 ? (head >> 1) * MX6_SUPER_BYTES + 24 * (head & 1) + 12 * h
+                                                            : (head >> 1) * MX4_SUPER_BYTES + 16 * (head & 1) + 8 * h);
+    uint32_t scw = 0;
 #pragma unroll
-    for (int db = 0; db < 4; ++db)
+    for (int db = 0; db < 4; ++db) {
+      float x[16], mx = 0.f;
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        bf16x4 w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = (bf16)(o[db][4 * g4 + j] * inv);
-        *reinterpret_cast<bf16x4*>(op + 32 * db + 8 * g4) = w;
+      for (int i = 0; i < 16; ++i) {
+        x[i] = (float)(bf16)(o[db][i] * inv);
+        mx = fmaxf(mx, fabsf(x[i]));
       }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const int e = OUTF == LL_QFMT_MX ? mx_scale_exp(mx) : OUTF == LL_QFMT_MX6 ? mx6_scale_exp(mx) : mx4_scale_exp(mx);
+      scw |= (uint32_t)(e + 127) << (8 * db);
+      uint32_t w[4];
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4)
+        w[g4] = OUTF == LL_QFMT_MX    ? mx_code4(x[4 * g4], x[4 * g4 + 1], x[4 * g4 + 2], x[4 * g4 + 3], e)
+                : OUTF == LL_QFMT_MX6 ? mx6_pack4(x[4 * g4], x[4 * g4 + 1], x[4 * g4 + 2], x[4 * g4 + 3], e)
+                                      : mx4_pack4(x[4 * g4], x[4 * g4 + 1], x[4 * g4 + 2], x[4 * g4 + 3], e);
+      if constexpr (OUTF == LL_QFMT_MX4) {             // 16-bit pieces
+        const uint32_t lo2 = w[0] | (w[1] << 16), hi2 = w[2] | (w[3] << 16);
+        const uint32_t got = __shfl_xor(h ? lo2 : hi2, 32, 64), mine = h ? hi2 : lo2;
+        const uint32_t a = h ? got : mine, bq = h ? mine : got;      // the h = 0 / h = 1 lane's pieces of this half's two g4
+        if (live) *reinterpret_cast<uint2*>(cp + 32 * db) = make_uint2((a & 0xffffu) | (bq << 16), (a >> 16) | (bq & 0xffff0000u));
+      } else {
+        const uint32_t g0 = __shfl_xor(h ? w[0] : w[2], 32, 64), g1 = __shfl_xor(h ? w[1] : w[3], 32, 64);
+        const uint32_t pa = h ? g0 : w[0], pb = h ? w[2] : g0, pc = h ? g1 : w[1], pd = h ? w[3] : g1;
+        if constexpr (OUTF == LL_QFMT_MX) {
+          if (live) *reinterpret_cast<uint4*>(cp + 32 * db) = make_uint4(pa, pb, pc, pd);
+        } else if (live) {                             // four 24-bit pieces -> three dwords
+          uint32_t* d = reinterpret_cast<uint32_t*>(cp + 48 * db);
+          d[0] = pa | (pb << 24);
+          d[1] = (pb >> 8) | (pc << 16);
+          d[2] = (pc >> 16) | (pd << 8);
+        }
+      }
+    }
+    if (live && h == 0) *reinterpret_cast<uint32_t*>(sc + row * ldsc + head * 4) = scw;
   }
 }
 
@@ -401,8 +457,40 @@ extern "C" int ll_flash_attn_mx(const ll_bf16* q, const uint8_t* kq, const uint8
   if (B == 0 || Lq == 0) return LL_OK;
   const MxSegs sg = mx_segs(seg0_start, seg0_len, seg1_start, seg1_len);
   const dim3 grid((Lq + MXA_NW * 32 - 1) / (MXA_NW * 32), H, B), block(MXA_NW * 64);
-  if (int rc = ll_lds_attr((const void*)flash_attn_mx_kernel, 2 * MXA_STAGE)) return rc;
-  hipLaunchKernelGGL(flash_attn_mx_kernel, grid, block, 2 * MXA_STAGE, (hipStream_t)stream, (const bf16*)q, kq, ks, vq, vs, (bf16*)out, Lq,
-                     ldq, ldo, H, S32, sg, scale * 1.4426950408889634f);
+  if (int rc = ll_lds_attr((const void*)flash_attn_mx_kernel<0>, 2 * MXA_STAGE)) return rc;
+  hipLaunchKernelGGL(flash_attn_mx_kernel<0>, grid, block, 2 * MXA_STAGE, (hipStream_t)stream, (const bf16*)q, kq, ks, vq, vs, (bf16*)out, Lq,
+                     ldq, ldo, H, S32, sg, scale * 1.4426950408889634f, (uint8_t*)nullptr, 0);
   return ll_check_launch("ll_flash_attn_mx");
+}
+
+// ll_flash_attn_mx with the codes + E8M0 scales of its bf16 rows as output (include/longlive_hip.h: ll_flash_attn_q's contract)
+extern "C" int ll_flash_attn_mx_q(int fmt, const ll_bf16* q, const uint8_t* kq, const uint8_t* ks, const uint8_t* vq, const uint8_t* vs,
+                                  uint8_t* codes, uint8_t* scales, int B, int Lq, int H, int head_dim, int ldq, int ldc, int lds, int S,
+                                  int S32, int seg0_start, int seg0_len, int seg1_start, int seg1_len, float scale, ll_stream stream) {
+  const int bits = fmt == LL_QFMT_MX ? 8 : fmt == LL_QFMT_MX6 ? 6 : fmt == LL_QFMT_MX4 ? 4 : 0;
+  LL_REQUIRE(bits != 0, "ll_flash_attn_mx_q: fmt=%d is none of LL_QFMT_MX / MX6 / MX4", fmt);
+  LL_REQUIRE(q != nullptr && codes != nullptr && scales != nullptr, "ll_flash_attn_mx_q: q, codes and scales are required");
+  LL_REQUIRE(kq != nullptr && ks != nullptr && vq != nullptr && vs != nullptr, "ll_flash_attn_mx_q: shadow codes and scales of K and V are required");
+  LL_REQUIRE(head_dim == 128, "ll_flash_attn_mx_q: head_dim=%d (the kernel is specialised for 128)", head_dim);
+  LL_REQUIRE(B >= 0 && Lq >= 0 && H > 0, "ll_flash_attn_mx_q: B=%d Lq=%d H=%d", B, Lq, H);
+  LL_REQUIRE(fmt == LL_QFMT_MX || (H & 1) == 0, "ll_flash_attn_mx_q: the packed formats pair heads in 256-k super-blocks: H=%d must be even", H);
+  LL_REQUIRE(ldq % 8 == 0 && ldq >= H * 128, "ll_flash_attn_mx_q: row stride ldq=%d (>= H*128, a multiple of 8)", ldq);
+  LL_REQUIRE(ldc % 16 == 0 && ldc >= H * 16 * bits && lds % 4 == 0 && lds >= H * 4, "ll_flash_attn_mx_q: code row stride %d bytes (>= %d, a "
+             "multiple of 16) or scale row stride %d bytes (>= %d, a multiple of 4)", ldc, H * 16 * bits, lds, H * 4);
+  if (int rc = mx_attn_check_segs("ll_flash_attn_mx_q", S, S32, seg0_start, seg0_len, seg1_start, seg1_len)) return rc;
+  LL_REQUIRE(scale > 0.f && scale <= 3.0e38f, "ll_flash_attn_mx_q: scale=%g must be positive and finite", (double)scale);
+  if (B == 0 || Lq == 0) return LL_OK;
+  const MxSegs sg = mx_segs(seg0_start, seg0_len, seg1_start, seg1_len);
+  const dim3 grid((Lq + MXA_NW * 32 - 1) / (MXA_NW * 32), H, B), block(MXA_NW * 64);
+#define LL_MXQ_LAUNCH(F)                                                                                                           \
+  {                                                                                                                                \
+    if (int rc = ll_lds_attr((const void*)flash_attn_mx_kernel<F>, 2 * MXA_STAGE)) return rc;                                      \
+    hipLaunchKernelGGL(flash_attn_mx_kernel<F>, grid, block, 2 * MXA_STAGE, (hipStream_t)stream, (const bf16*)q, kq, ks, vq, vs,   \
+                       (bf16*)codes, Lq, ldq, ldc, H, S32, sg, scale * 1.4426950408889634f, scales, lds);                          \
+  }
+  if (fmt == LL_QFMT_MX) LL_MXQ_LAUNCH(LL_QFMT_MX)
+  else if (fmt == LL_QFMT_MX6) LL_MXQ_LAUNCH(LL_QFMT_MX6)
+  else LL_MXQ_LAUNCH(LL_QFMT_MX4)
+#undef LL_MXQ_LAUNCH
+  return ll_check_launch("ll_flash_attn_mx_q");
 }

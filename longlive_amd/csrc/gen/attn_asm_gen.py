@@ -56,6 +56,10 @@ S_DBG, S_WG = 56, 58
 S_SSQ, S_SSQ_STRIDE, S_NPART, S_NW, S_INVC, S_EPS = 80, 82, 83, 84, 86, 87      # s[80:81] sums at the workgroup's first row (fp32, bytes); bytes between
                                              # n-tile planes; planes; s[84:85] norm weight at the head's first channel (bf16); 1 / C; eps (fp32 bits)
 S_C2 = 44                                    # (c, c) in s[44:45]: packed-multiply operand
+# Quantised-output forms (flash_attn_asm_<mx|mx6|mx4>_kernel): S_O / S_LDO are the CODE base (the workgroup's first row at the head's
+# first code byte) and the code row stride in bytes; the E8M0 scale bytes go to
+S_SC, S_SCLD = 88, 90                        # s[88:89] scale base (first row, the head's four bytes); scale row stride in bytes
+S_QK, S_QSB, S_QHI = 38, 39, 51              # epilogue constants: code offset (add3 operand), sign bit of a code, 0xffff0000
 NPART_MAX = 16                               # planes summed (absent ones read as +0: x + 0 is exact), in plane order
 import os as _os
 
@@ -416,9 +420,12 @@ def ret_dispatch(g: Gen, ret_labels):
 
 
 # ---- the kernel -------------------------------------------------------------------------------------------------------
-def generate(dma: str = "buffer", prefix: str = "LL", diag: bool = False, qnorm: bool = False) -> str:
+def generate(dma: str = "buffer", prefix: str = "LL", diag: bool = False, qnorm: bool = False, out=None) -> str:
+    """out: None = bf16 rows; "mx" / "mx6" / "mx4" = the block-scaled codes + E8M0 scales of those rows (gen_epilogue_q); only the text
+    after LL_EPILOGUE differs."""
     global DMA, PFX, DIAG
     assert dma == "buffer"
+    assert out is None or (out in OUT_FORMS and not qnorm), out
     DMA, PFX, DIAG = dma, prefix, diag
     g = Gen()
     I = g.I
@@ -627,7 +634,10 @@ def generate(dma: str = "buffer", prefix: str = "LL", diag: bool = False, qnorm:
         I(f"global_store_dwordx4 {vreg(V_T)}, {vreg(V_T + 2, 4)}, {sreg(S_DBG, 2)}")
         I(f"global_store_dwordx4 {vreg(V_T)}, {vreg(V_T + 6, 4)}, {sreg(S_DBG, 2)} offset:16")
         I("s_mov_b64 exec, -1")
-    gen_epilogue(g)
+    if out is None:
+        gen_epilogue(g)
+    else:
+        gen_epilogue_q(g, out)
     pstamp(g, 6)
     I("s_waitcnt vmcnt(0)")
     pstamp(g, 7)
@@ -820,10 +830,8 @@ def gen_tile(g: Gen, u: int):
     stamp(g, S_ACC + 4)
 
 
-def gen_epilogue(g: Gen):
-    """O^T / l -> bf16 rows.  A lane (r, h) holds, for its query, d = 32 db + 8 g4 + 4 h + (0..3) in registers 4 g4 .. 4 g4 + 3 of
-    o[qb][db].  v_permlane32_swap of the packed words of g4 = k (vdst) and k + 1 (src) gives every lane 16 contiguous bytes
-    (d = 32 db + 8 (k + h) .. +7): 8 x 16-byte stores per q-block (T21)."""
+def gen_row_sums(g: Gen):
+    """l -> 1 / l per q-block (both halves of the wave hold half of every tile's keys); returns the registers that hold it"""
     I = g.I
     if LSUM:
         for qb in range(2):                           # every register of LACC[qb] holds the lane's query's row sum: take register 0
@@ -843,8 +851,17 @@ def gen_epilogue(g: Gen):
         for qb in range(2):
             I(f"v_add_f32 {vreg(V_L + 4 * qb)}, {vreg(V_L + 4 * qb)}, {vreg(V_T + qb)}")
             I(f"v_rcp_f32 {vreg(V_L + 4 * qb)}, {vreg(V_L + 4 * qb)}")
+    return [(V_LACC + 16 * qb) if LSUM else (V_L + 4 * qb) for qb in range(2)]
+
+
+def gen_epilogue(g: Gen):
+    """O^T / l -> bf16 rows.  A lane (r, h) holds, for its query, d = 32 db + 8 g4 + 4 h + (0..3) in registers 4 g4 .. 4 g4 + 3 of
+    o[qb][db].  v_permlane32_swap of the packed words of g4 = k (vdst) and k + 1 (src) gives every lane 16 contiguous bytes
+    (d = 32 db + 8 (k + h) .. +7): 8 x 16-byte stores per q-block (T21)."""
+    I = g.I
+    invs = gen_row_sums(g)
     for qb in range(2):
-        inv = (V_LACC + 16 * qb) if LSUM else (V_L + 4 * qb)
+        inv = invs[qb]
         # output row address: O base + row * ldo + (4 h elements -> the swap moves it to 8 (k + h)) ; 64-bit
         I(f"v_mul_lo_u32 {vreg(V_T + 2)}, {vreg(V_ROW + qb)}, {sreg(S_LDO)}")
         I(f"v_lshl_add_u32 {vreg(V_T + 2)}, {vreg(V_H)}, 4, {vreg(V_T + 2)}")            # + 16 h bytes
@@ -871,6 +888,137 @@ def gen_epilogue(g: Gen):
                 I(f"s_mov_b64 exec, {sreg(S_M0, 2)}")
                 I(f"global_store_dwordx4 {vreg(V_T + 2)}, {vreg(V_T + 10, 4)}, {sreg(S_O, 2)} offset:{64 * db + 16 * kp}")
                 I("s_mov_b64 exec, -1")
+
+
+# ---- quantised-output epilogues ---------------------------------------------------------------------------------------
+# What mx.h / mx6.h / mx4.h compute, per format: mb mantissa bits, emin the exponent of the smallest normal code, bump the addend that
+# carries into the fp32 exponent exactly when the frexp mantissa of amax exceeds the format's threshold (0.875 / 0.9375 / 0.75),
+# sub = the distance from that exponent field to the E8M0 byte, bits per code, bytes per 32-code block.
+OUT_FORMS = {
+    "mx": dict(mb=3, emin=-6, bump=0x1FFFFF, sub=8, bits=8, blk=32),
+    "mx6": dict(mb=3, emin=0, bump=0x0FFFFF, sub=2, bits=6, blk=24),
+    "mx4": dict(mb=1, emin=0, bump=0x3FFFFF, sub=2, bits=4, blk=16),
+}
+
+
+def gen_epilogue_q(g: Gen, fmt: str):
+    """O^T / l -> bf16 (the plain form's v_mul_f32 + v_cvt_pk_bf16_f32) -> the quantiser's bytes of those bf16 values.  A lane (r, h)
+    holds 16 of the 32 channels of block db, d = 32 db + 8 g4 + 4 h + (0..3); lane (r, 1 - h) holds the others: the block maximum is an
+    in-lane chain and one v_permlane32_swap.  Integer restatement of mx*_scale_exp / mx*_code:
+      byte = max(((amax_bits + bump) >> 23) - sub, 0), 127 for amax = 0;   v = x * 2^(127 - byte)  (exact; field 254 - byte >= 1);
+      field' = max(exponent field of v, 127 + emin);  t = |v| + 2^(field' - 127 + 23 - mb): the fp32 add rounds |v| to a multiple of the
+      code step, nearest even, and leaves n = |v| / step (0 .. 2^(mb + 1)) in t's low bits, so
+      code = (field' - 127 - emin + 1) << mb + n - (1 << mb) = (t >> (23 - mb)) + (t & 31) - ((127 + emin + 23 - mb) << mb)
+      (a subnormal code has field' = 127 + emin and n < 2^mb; n = 2^(mb + 1) carries into the exponent), | the sign bit of v.
+    Saturation never binds under the scale rule.  The words of g4 = 0, 1 and those of g4 = 2, 3 are exchanged between the halves, so
+    the lower half-wave stores channels 0-15 of the block and the upper 16-31, one contiguous store each.  The scale dword of the
+    (row, head) is stored by the lower half."""
+    I = g.I
+    F = OUT_FORMS[fmt]
+    mb, emin, bits = F["mb"], F["emin"], F["bits"]
+    X, TW, TM, TT, TA, TN, TS, WD = 0, 16, 17, 18, 19, 20, 21, 24      # the score buffers are dead: 16 values, temporaries, 4 code words
+    AM, AM2, EB, ML, SCW, C127, ADR, ADS, U0, U1 = 28, 29, 30, 32, 34, 35, 36, 37, 38, 39
+    invs = gen_row_sums(g)
+    I(f"s_mov_b32 {sreg(S_QK)}, {hex(-((127 + emin + 23 - mb) << mb) & 0xffffffff)}")
+    I(f"s_mov_b32 {sreg(S_QSB)}, {1 << (bits - 1)}")
+    I(f"s_mov_b32 {sreg(S_QHI)}, 0xffff0000")
+    I(f"v_mov_b32 {vreg(C127)}, 0x7f")
+    for qb in range(2):
+        inv = invs[qb]
+        I(f"v_mul_lo_u32 {vreg(ADR)}, {vreg(V_ROW + qb)}, {sreg(S_LDO)}")
+        if fmt == "mx6":
+            I(f"v_mad_u32_u24 {vreg(ADR)}, {vreg(V_H)}, 12, {vreg(ADR)}")
+        else:
+            I(f"v_lshl_add_u32 {vreg(ADR)}, {vreg(V_H)}, {4 if fmt == 'mx' else 3}, {vreg(ADR)}")
+        I(f"v_mul_lo_u32 {vreg(ADS)}, {vreg(V_ROW + qb)}, {sreg(S_SCLD)}")
+        I(f"v_cmp_lt_u32_e64 {sreg(S_M0, 2)}, {vreg(V_ROW + qb)}, {sreg(S_ROWS)}")
+        for db in range(4):
+            # the 16 bf16 values of the lane, widened
+            for i in range(0, 16, 2):
+                a0 = A_O + 64 * qb + 16 * db + i
+                I(f"v_accvgpr_read_b32 {vreg(X + i)}, {areg(a0)}")
+                I(f"v_accvgpr_read_b32 {vreg(X + i + 1)}, {areg(a0 + 1)}")
+                I(f"v_mul_f32 {vreg(X + i)}, {vreg(X + i)}, {vreg(inv)}")
+                I(f"v_mul_f32 {vreg(X + i + 1)}, {vreg(X + i + 1)}, {vreg(inv)}")
+                I(f"v_cvt_pk_bf16_f32 {vreg(TW)}, {vreg(X + i)}, {vreg(X + i + 1)}")
+                I(f"v_lshlrev_b32 {vreg(X + i)}, 16, {vreg(TW)}")
+                I(f"v_and_b32 {vreg(X + i + 1)}, 0xffff0000, {vreg(TW)}")
+            # block maximum over both lanes of the pair
+            I(f"v_max3_f32 {vreg(AM)}, |{vreg(X)}|, |{vreg(X + 1)}|, |{vreg(X + 2)}|")
+            for i in range(3, 15, 2):
+                I(f"v_max3_f32 {vreg(AM)}, {vreg(AM)}, |{vreg(X + i)}|, |{vreg(X + i + 1)}|")
+            I(f"v_max_f32_e64 {vreg(AM)}, {vreg(AM)}, |{vreg(X + 15)}|")
+            I(f"v_mov_b32 {vreg(AM2)}, {vreg(AM)}")
+            I("s_nop 1")
+            I(f"v_permlane32_swap_b32 {vreg(AM)}, {vreg(AM2)}")
+            I(f"v_max_f32 {vreg(AM)}, {vreg(AM)}, {vreg(AM2)}")
+            # E8M0 byte, the multiplier 2^(127 - byte)
+            I(f"v_add_u32 {vreg(EB)}, {hex(F['bump'])}, {vreg(AM)}")
+            I(f"v_lshrrev_b32 {vreg(EB)}, 23, {vreg(EB)}")
+            I(f"v_add_u32 {vreg(EB)}, {-F['sub']}, {vreg(EB)}")
+            I(f"v_max_i32 {vreg(EB)}, 0, {vreg(EB)}")
+            I(f"v_cmp_eq_u32_e64 {sreg(S_M1, 2)}, {vreg(AM)}, 0")
+            I(f"v_cndmask_b32_e64 {vreg(EB)}, {vreg(EB)}, {vreg(C127)}, {sreg(S_M1, 2)}")
+            if db == 0:
+                I(f"v_mov_b32 {vreg(SCW)}, {vreg(EB)}")
+            else:
+                I(f"v_lshl_or_b32 {vreg(SCW)}, {vreg(EB)}, {8 * db}, {vreg(SCW)}")
+            I(f"v_sub_u32 {vreg(ML)}, 0xfe, {vreg(EB)}")
+            I(f"v_lshlrev_b32 {vreg(ML)}, 23, {vreg(ML)}")
+            I(f"v_mov_b32 {vreg(ML + 1)}, {vreg(ML)}")
+            for i in range(0, 16, 2):
+                I(f"v_pk_mul_f32 {vreg(X + i, 2)}, {vreg(X + i, 2)}, {vreg(ML, 2)}")
+            # codes, packed four to a word (register order 0, 2, 1, 3: see the exchange below)
+            for g4 in range(4):
+                wd = WD + (g4 if fmt == "mx4" else (0, 2, 1, 3)[g4])
+                for j in range(4):
+                    x = X + 4 * g4 + j
+                    I(f"v_and_b32 {vreg(TM)}, 0x7f800000, {vreg(x)}")
+                    I(f"v_max_u32 {vreg(TM)}, {hex((127 + emin) << 23)}, {vreg(TM)}")
+                    I(f"v_add_u32 {vreg(TM)}, {hex((23 - mb) << 23)}, {vreg(TM)}")
+                    I(f"v_add_f32_e64 {vreg(TT)}, |{vreg(x)}|, {vreg(TM)}")
+                    I(f"v_lshrrev_b32 {vreg(TA)}, {23 - mb}, {vreg(TT)}")
+                    I(f"v_and_b32 {vreg(TN)}, 31, {vreg(TT)}")
+                    I(f"v_add3_u32 {vreg(TA)}, {vreg(TA)}, {vreg(TN)}, {sreg(S_QK)}")
+                    I(f"v_lshrrev_b32 {vreg(TS)}, {32 - bits}, {vreg(x)}")
+                    I(f"v_and_or_b32 {vreg(TA)}, {vreg(TS)}, {sreg(S_QSB)}, {vreg(TA)}")
+                    if j == 0:
+                        I(f"v_mov_b32 {vreg(wd)}, {vreg(TA)}")
+                    else:
+                        I(f"v_lshl_or_b32 {vreg(wd)}, {vreg(TA)}, {bits * j}, {vreg(wd)}")
+            off = (32 if fmt == "mx" else 2 * F["blk"]) * db      # packed rows interleave the blocks of a head pair (mx6.h / mx4.h)
+            if fmt == "mx4":                          # 16-bit pieces: (g4 0, 1) and (g4 2, 3) to a word, exchanged, then re-paired by half
+                I(f"v_lshl_or_b32 {vreg(U0)}, {vreg(WD + 1)}, 16, {vreg(WD)}")
+                I(f"v_lshl_or_b32 {vreg(U1)}, {vreg(WD + 3)}, 16, {vreg(WD + 2)}")
+                I("s_nop 1")
+                I(f"v_permlane32_swap_b32 {vreg(U0)}, {vreg(U1)}")       # now U0 = the h = 0 lane's pieces of this half's two g4, U1 = the h = 1 lane's
+                I(f"v_and_b32 {vreg(TM)}, 0xffff, {vreg(U0)}")
+                I(f"v_lshl_or_b32 {vreg(WD)}, {vreg(U1)}, 16, {vreg(TM)}")
+                I(f"v_lshrrev_b32 {vreg(TT)}, 16, {vreg(U0)}")
+                I(f"v_and_or_b32 {vreg(WD + 1)}, {vreg(U1)}, {sreg(S_QHI)}, {vreg(TT)}")
+            else:
+                I("s_nop 1")
+                I(f"v_permlane32_swap_b32 {vreg(WD)}, {vreg(WD + 1)}")  # (g4 0 | g4 2): the upper half takes g4 2, 3; WD .. WD + 3 then hold the
+                I(f"v_permlane32_swap_b32 {vreg(WD + 2)}, {vreg(WD + 3)}")  # pieces h = 0, h = 1 of the first g4 and h = 0, h = 1 of the second
+                if fmt == "mx6":                      # four 24-bit pieces -> three dwords
+                    I(f"v_lshl_or_b32 {vreg(U0)}, {vreg(WD + 1)}, 24, {vreg(WD)}")
+                    I(f"v_lshrrev_b32 {vreg(TM)}, 8, {vreg(WD + 1)}")
+                    I(f"v_lshl_or_b32 {vreg(U0 + 1)}, {vreg(WD + 2)}, 16, {vreg(TM)}")
+                    I(f"v_lshrrev_b32 {vreg(TT)}, 16, {vreg(WD + 2)}")
+                    I(f"v_lshl_or_b32 {vreg(U0 + 2)}, {vreg(WD + 3)}, 8, {vreg(TT)}")
+            I(f"s_mov_b64 exec, {sreg(S_M0, 2)}")
+            if fmt == "mx":
+                I(f"global_store_dwordx4 {vreg(ADR)}, {vreg(WD, 4)}, {sreg(S_O, 2)} offset:{off}")
+            elif fmt == "mx6":
+                I(f"global_store_dwordx3 {vreg(ADR)}, {vreg(U0, 3)}, {sreg(S_O, 2)} offset:{off}")
+            else:
+                I(f"global_store_dwordx2 {vreg(ADR)}, {vreg(WD, 2)}, {sreg(S_O, 2)} offset:{off}")
+            I("s_mov_b64 exec, -1")
+        I(f"s_mov_b32 {sreg(S_T0)}, {sreg(S_M0)}")                                 # rows < S_ROWS of the lower half-wave
+        I(f"s_mov_b32 {sreg(S_T1)}, 0")
+        I(f"s_mov_b64 exec, {sreg(S_T0, 2)}")
+        I(f"global_store_dword {vreg(ADS)}, {vreg(SCW)}, {sreg(S_SC, 2)}")
+        I("s_mov_b64 exec, -1")
 
 
 def f32bits(x):
@@ -1031,7 +1179,12 @@ if __name__ == "__main__":
     qnorm = "--qnorm" in sys.argv
     if qnorm:
         sys.argv.remove("--qnorm")
-    txt = generate(mode, "LL" + mode[0].upper() + ("D" if diag else "") + ("N" if qnorm else ""), diag, qnorm)
+    out = None
+    if "--out" in sys.argv:                           # mx | mx6 | mx4: the quantised-output forms
+        k = sys.argv.index("--out")
+        out = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
+    txt = generate(mode, "LL" + mode[0].upper() + ("D" if diag else "") + ("N" if qnorm else "") + (out or "").upper(), diag, qnorm, out)
     probs = lint(txt)
     for p in probs[:40]:
         print("LINT:", p, file=sys.stderr)

@@ -84,6 +84,8 @@ class _QuantMode(NamedTuple):
     gemm_qkv: Callable                 # (x, w, bias, cache_v, write_start, roped_offset, write_len, B, L)
     mx_out: bool                       # FFN1's GELU epilogue writes the codes + scales FFN2 reads, never the bf16 hidden
     granule: int                       # dim and ffn_dim must be multiples of it
+    afmt: Optional[ops.QFormat] = None  # the activations' block-scaled format (ops.MX, MX6, MX4: what the attention kernels can emit per
+                                       # head); None for bf16 and for per-row scales, which span all heads of a row
 
 
 def _op(name: str) -> Callable:
@@ -93,7 +95,7 @@ def _op(name: str) -> Callable:
 def _quant_mode(wq: str, xq: str, act: str, gemm: str, mx_out: bool, granule: int) -> _QuantMode:
     """The regular naming: weights by ops.<wq>, activations by ops.<xq> or the ops.*_<act> producers, ops.gemm_<gemm>[_qkv_v_insert]."""
     return _QuantMode(_op(wq), _op(xq), _op("ln_modulate_" + act), _op("ln_modulate_tab_" + act), _op("layernorm_affine_" + act),
-                      _op("gemm_" + gemm), _op(f"gemm_{gemm}_qkv_v_insert"), mx_out, granule)
+                      _op("gemm_" + gemm), _op(f"gemm_{gemm}_qkv_v_insert"), mx_out, granule, getattr(ops, act.upper()) if act.startswith("mx") else None)
 
 
 def _rowwise(gemm: str) -> Callable:       # the per-row-scale GEMMs take codes and scales as separate arguments
@@ -201,6 +203,10 @@ class CausalWanModelHIP(nn.Module):
         self.fuse_v_insert = True             # the QKV projection's epilogue writes V into the KV cache (A/B switch)
         self.use_modulation_f32 = True        # LN + modulate from the fp32 table (1 + scale, shift: ops.modulation_table_f32) beside the
                                               # bf16 one the gate epilogues read: same bits, fewer instructions per row (A/B switch)
+        self.fuse_attn_quant = False          # block-scaled modes: self- and cross-attention write the codes + scales their output
+                                              # projections read (ops.flash_attn(..., out_fmt=)), no quantiser launch between: same bits.
+                                              # Off by default: faster end to end in mxfp8 and mxfp4_a6, not in mxfp6 and mxfp4_a4
+                                              # (profiles/attn_qout_fps.md)
         self.fuse_cross_qnorm = True          # cross-attention q: RMSNorm statistics from the projection's epilogue, applied in the attention
                                               # kernel's Q prologue (no RMSNorm launch) where both generated kernels cover the call (A/B switch)
         self._packed = None
@@ -421,6 +427,7 @@ class CausalWanModelHIP(nn.Module):
         plan = plan_update(current_start, L, G, E, S, self.sink_size * fs, self.local_attn_size,
                            sa.max_attention_size, sink_recache_after_switch)
         amx = self.attn_quant == "mxfp8"
+        ofmt = m.afmt if self.fuse_attn_quant else None
         if amx:
             shadow, stale = self._mx_shadow(kvc)
         else:
@@ -449,12 +456,14 @@ class CausalWanModelHIP(nn.Module):
         # (a forward that runs beside another one on a second stream -- the pipelines' context-pass overlap -- times its launches
         #  under another tag: bench.py's roofline describes the kernel running alone on the device)
         if amx:
-            att = ops.flash_attn_mx(q_buf, shadow, plan.segments, tag="flash_attn_self_mx_co" if co_running else "flash_attn_self_mx")
+            att = ops.flash_attn_mx(q_buf, shadow, plan.segments, tag="flash_attn_self_mx_co" if co_running else "flash_attn_self_mx",
+                                    out_fmt=ofmt)
         else:
-            att = ops.flash_attn(q_buf, kvc["k"], kvc["v"], plan.segments, tag="flash_attn_self_co" if co_running else "flash_attn_self")
+            att = ops.flash_attn(q_buf, kvc["k"], kvc["v"], plan.segments, tag="flash_attn_self_co" if co_running else "flash_attn_self",
+                                 out_fmt=ofmt)
         if cache_done_event is not None:
             cache_done_event.record(torch.cuda.current_stream())
-        self._lin(att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
+        self._lin(att if ofmt is not None else att.view(B, L, C), pk, "o", sa.o.weight, sa.o.bias, ops.EPI_BIAS_GATE_RES, out=xs, res=xs, e=e0,
                   mod=mod, gate_idx=2, rows_per_batch=L, frame_len=fs)
         # --- cross attention (causal_model.py:460; model.py:159-194) ---
         xn = m.layernorm_affine(xs, blk.norm3.weight, blk.norm3.bias, c.eps)
@@ -474,8 +483,8 @@ class CausalWanModelHIP(nn.Module):
         if fuse_qn:
             atc = ops.flash_attn_qnorm(qraw.view(B, L, Hh, D), ssq, ca.norm_q.weight, c.eps, cac["k"], cac["v"], c.text_len, tag="flash_attn_cross_qn")
         else:
-            atc = ops.flash_attn(qc.view(B, L, Hh, D), cac["k"], cac["v"], [(0, c.text_len)], tag="flash_attn_cross")
-        self._lin(atc.view(B, L, C), pk, "co", ca.o.weight, ca.o.bias, ops.EPI_BIAS_RES, out=xs, res=xs)
+            atc = ops.flash_attn(qc.view(B, L, Hh, D), cac["k"], cac["v"], [(0, c.text_len)], tag="flash_attn_cross", out_fmt=ofmt)
+        self._lin(atc if isinstance(atc, tuple) else atc.view(B, L, C), pk, "co", ca.o.weight, ca.o.bias, ops.EPI_BIAS_RES, out=xs, res=xs)
         # --- FFN (causal_model.py:462-468) ---
         h2 = m.ln_modulate_tab(xs, tab32, 3, 4, F, c.eps) if tab32 is not None else m.ln_modulate(xs, e0, mod, 3, 4, F, c.eps)
         ff = self._lin(h2, pk, "f1", blk.ffn[0].weight, blk.ffn[0].bias, ops.EPI_BIAS_GELU,

@@ -414,9 +414,13 @@ def linear_small(x, w, bias, act_in: int = 0, act_out: int = 0):
     return out
 
 
-def flash_attn(q, k, v, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None):
+def flash_attn(q, k, v, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None, out_fmt: Optional["QFormat"] = None):
     """q [B,Lq,H,128] (contiguous); k,v [B,Sk,H,128]; keys = concatenation of up to two row ranges
-    [(start, end), ...] of k/v.  Returns [B,Lq,H,128]."""
+    [(start, end), ...] of k/v.  Returns [B,Lq,H,128], or with out_fmt (MX, MX6, MX4) the (codes, scales) of those rows as
+    out_fmt.empty((B, Lq, H*128)) shapes them: the bytes quantize_<fmt>(flash_attn(...)) gives, written by the attention kernel's
+    epilogue where flash_attn_q_ok says so and by the two launches otherwise."""
+    if out_fmt is not None:
+        return _flash_attn_q(out_fmt, q, k, v, segments, scale, tag)
     _chk(q, "q"); _chk(k, "k"); _chk(v, "v")
     B, Lq, H, D = q.shape
     assert D == 128, "kernel is specialised for head_dim 128"
@@ -448,6 +452,50 @@ def flash_attn(q, k, v, segments, out=None, scale: Optional[float] = None, tag: 
 
 def flash_attn_qnorm_ok(H: int, nkeys: int) -> bool:
     return bool(_lib.load().ll_flash_attn_qnorm_ok(H, nkeys))
+
+
+_QFMT_ID = {"mx": 1, "mx6": 2, "mx4": 3}      # include/longlive_hip.h: enum ll_qfmt
+
+
+def _qfmt_id(fmt) -> int:
+    assert fmt.name in _QFMT_ID, f"attention emits the block-scaled formats only (MX, MX6, MX4), not {fmt.name}"
+    return _QFMT_ID[fmt.name]
+
+
+def flash_attn_q_ok(fmt, H: int, segments) -> bool:
+    """Does the generated attention kernel write fmt's codes + scales itself for these key ranges (under the current tuning)?"""
+    s0, e0, s1, e1 = _segs2(segments, 1 << 30)
+    return bool(_lib.load().ll_flash_attn_q_ok(_qfmt_id(fmt), H, s0, e0 - s0, s1, e1 - s1))
+
+
+def flash_attn_q_plan(fmt, Lq: int, H: int, B: int, segments) -> str:
+    """Kernel and grid of a flash_attn(..., out_fmt=fmt) call, or that it takes two launches (host only)."""
+    import ctypes
+    s0, e0, s1, e1 = _segs2(segments, 1 << 30)
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load().ll_flash_attn_q_plan(_qfmt_id(fmt), Lq, H, B, s0, e0 - s0, s1, e1 - s1, buf, 512), "ll_flash_attn_q_plan")
+    return buf.value.decode()
+
+
+def _flash_attn_q(fmt, q, k, v, segments, scale, tag):
+    B, Lq, H, D = q.shape
+    if not flash_attn_q_ok(fmt, H, segments):
+        return _quantize(fmt, flash_attn(q, k, v, segments, scale=scale, tag=tag).view(B, Lq, H * D))
+    _chk(q, "q"); _chk(k, "k"); _chk(v, "v")
+    assert D == 128, "kernel is specialised for head_dim 128"
+    Sk = k.shape[1]
+    assert k.shape == (B, Sk, H, D) and v.shape == k.shape
+    s0, e0, s1, e1 = _segs2(segments, Sk)
+    codes, scales = fmt.empty((B, Lq, H * D), q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    tag = tag or "flash_attn"
+    t0 = _t0(tag)
+    _lib.check(_lib.load().ll_flash_attn_q(_qfmt_id(fmt), q.data_ptr(), k.data_ptr(), v.data_ptr(), codes.data_ptr(), scales.data_ptr(), B, Lq,
+                                           H, H * D, codes.shape[-1], scales.shape[-1], H * D, Sk * H * D, s0, e0 - s0, s1, e1 - s1, scale,
+                                           _stream()), "ll_flash_attn_q")
+    _t1(tag, t0, 4.0 * B * H * Lq * ((e0 - s0) + (e1 - s1)) * D)     # algorithmic FLOPs: QK^T + PV
+    return codes, scales
 
 
 def flash_attn_qnorm(q, ssq, norm_w, eps: float, k, v, nkeys: int, out=None, scale: Optional[float] = None, tag: Optional[str] = None):
@@ -1071,21 +1119,34 @@ def _segs2(segments, S):
     return s0, e0, s1, e1
 
 
-def flash_attn_mx(q, shadow: dict, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None):
+def flash_attn_mx(q, shadow: dict, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None,
+                  out_fmt: Optional[QFormat] = None):
     """flash_attn over the MX shadow of the cache: q [B,Lq,H,128] bf16 (quantised per row in the kernel), keys = up to two slot
-    ranges [(start, end), ...].  Returns [B,Lq,H,128] bf16."""
+    ranges [(start, end), ...].  Returns [B,Lq,H,128] bf16, or with out_fmt (MX, MX6, MX4) the (codes, scales) of those rows: the
+    bytes quantize_<fmt>(flash_attn_mx(...)) gives, from the kernel's epilogue (two launches for a packed format over an odd H)."""
     _chk(q, "q")
     B, Lq, H, D = q.shape
     assert D == 128, "kernel is specialised for head_dim 128"
     S, S32 = shadow["S"], shadow["kq"].shape[1]
     assert shadow["kq"].shape == (B, S32, H, D) and shadow["vq"].shape == (B, H, S32 // 32, D, 32), (q.shape, shadow["kq"].shape)
     s0, e0, s1, e1 = _segs2(segments, S)
-    out = torch.empty_like(q) if out is None else _chk(out, "out")
-    assert out.shape == q.shape
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     lib = _lib.load()
     tag = tag or "flash_attn_mx"
+    if out_fmt is not None:
+        if _qfmt_id(out_fmt) != 1 and H % 2:
+            return _quantize(out_fmt, flash_attn_mx(q, shadow, segments, scale=scale, tag=tag).view(B, Lq, H * D))
+        codes, scales = out_fmt.empty((B, Lq, H * D), q.device)
+        t0 = _t0(tag)
+        _lib.check(lib.ll_flash_attn_mx_q(_qfmt_id(out_fmt), q.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(),
+                                          shadow["vq"].data_ptr(), shadow["vs"].data_ptr(), codes.data_ptr(), scales.data_ptr(), B, Lq, H, D,
+                                          H * D, codes.shape[-1], scales.shape[-1], S, S32, s0, e0 - s0, s1, e1 - s1, scale, _stream()),
+                   "ll_flash_attn_mx_q")
+        _t1(tag, t0, 4.0 * B * H * Lq * ((e0 - s0) + (e1 - s1)) * D)
+        return codes, scales
+    out = torch.empty_like(q) if out is None else _chk(out, "out")
+    assert out.shape == q.shape
     t0 = _t0(tag)
     _lib.check(lib.ll_flash_attn_mx(q.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(), shadow["vq"].data_ptr(),
                                     shadow["vs"].data_ptr(), out.data_ptr(), B, Lq, H, D, H * D, H * D, S, S32, s0, e0 - s0, s1, e1 - s1,

@@ -846,6 +846,7 @@ class Machine:
         self._issue(w, "vm", complete)
 
     def i_global_store_dwordx4(self, w, i): self._vstore(w, i, self._gaddr(w, i, i.ops[0], i.ops[2]), i.ops[1], 16)
+    def i_global_store_dwordx3(self, w, i): self._vstore(w, i, self._gaddr(w, i, i.ops[0], i.ops[2]), i.ops[1], 12)
     def i_global_store_dwordx2(self, w, i): self._vstore(w, i, self._gaddr(w, i, i.ops[0], i.ops[2]), i.ops[1], 8)
     def i_global_store_dword(self, w, i): self._vstore(w, i, self._gaddr(w, i, i.ops[0], i.ops[2]), i.ops[1], 4)
 
