@@ -17,7 +17,7 @@
 //                 V row = 256 B; 16-B chunk c of key r at position c ^ ((r & 3) << 2) -> tr_b16 reads conflict-free
 #include <stdio.h>
 
-#include "common.h"
+#include "attention_common.h"
 
 #define KT 64                       // keys per tile
 #define TILE_B (KT * 128 * 2)       // 16 KiB
@@ -663,70 +663,78 @@ __device__ __forceinline__ float xrow_sum4(float x) {
   return c2 + d;
 }
 
-#ifndef LL_ATTN_VARIANT_DEFAULT
-#define LL_ATTN_VARIANT_DEFAULT 2
-#endif
-static int g_attn_variant = LL_ATTN_VARIANT_DEFAULT;   // 0: simple kernel, 1: software-pipelined, 2: + ping-pong wave groups for long key ranges
-static int g_attn_pp_min_keys = 16 * KT;   // key ranges at least this long run the ping-pong loop (cross-attention's 512 keys: one-barrier loop)
-void ll_set_attn_pp_min_internal(int v) { g_attn_pp_min_keys = v; }
-static int g_attn_xcd = 1;
-static int g_attn_asm = 1;        // tuning key attn_asm (DEFAULT 1; 0 = flash_attn_pipe_kernel<8, 1>): long contiguous key ranges run flash_attn_asm_kernel
-                                  // (attention_asm.hip: 4 waves x 64 rows, one wave per SIMD, generated hand-scheduled body)
-void ll_set_attn_asm_internal(int v) { g_attn_asm = v; }
-int flash_attn_asm_launch(const bf16* q, const bf16* k, const bf16* v, bf16* out, int B, int Lq, int H, int ldq, int ldo, int ldk,
-                          long long k_batch_stride, int kstart, int nkeys, float c, int xcd, int form, hipStream_t stream);
-static int g_attn_asm_min_keys = 8 * KT;    // the generated kernel from 512 keys on (cross-attention: 22.7 vs 26.8 us, profiles/r03_cross_attn_asm.txt)
-void ll_set_attn_asm_min_internal(int v) { g_attn_asm_min_keys = v; }
-static bool attn_asm_eligible(int nkeys, int ldk) {
-  // (the generated kernel needs at least two key tiles: its first tile is a special case and so is its last; whatever the tuning
-  //  key says, shorter ranges stay on the HIP kernels -- tests/test_attn_asm_emu.py::test_two_tiles_is_the_shortest_range)
-  const int min_keys = g_attn_asm_min_keys > 2 * KT ? g_attn_asm_min_keys : 2 * KT;
-  return g_attn_asm && g_attn_variant >= 2 && nkeys >= min_keys && (long long)nkeys * ldk * 2 < 0x7fffffffLL;
-}
-void ll_set_attn_xcd_internal(int v) { g_attn_xcd = v; }   // 0: simple kernel, 1: software-pipelined kernel (single key range)
-void ll_set_attn_variant_internal(int v) { g_attn_variant = v; }
+AttnTuning g_attn = {LL_ATTN_VARIANT_DEFAULT, 16 * KT, 1, 1, 8 * KT};
 
-static int flash_attn_pipe_launch(const ll_bf16* q, const ll_bf16* k, const ll_bf16* v, ll_bf16* out, int B,
-                                         int Lq, int H, int ldq, int ldo, int ldk, long long k_batch_stride, int kstart,
-                                         int nkeys, float c, ll_stream stream) {
-  constexpr int NW = 8;
-  {
-    (void)ll_lds_attr((const void*)flash_attn_pipe_kernel<NW, 0>, (int)((PIPE_KSTAGES + PIPE_VSTAGES) * TILE_B));
-    (void)ll_lds_attr((const void*)flash_attn_pipe_kernel<NW, 1>, (int)((PIPE_KSTAGES + PIPE_VSTAGES + 2) * TILE_B));
+// What a call runs.  gen = the row of the generated kernels' table that takes it (attention_asm.hip), nullptr = fn is a HIP kernel here.
+struct AttnRoute {
+  const void* fn;
+  const char* name;           // the device symbol, as the plans print it
+  const char* form;           // the plans' words on the kernel's structure; nullptr: none (and no placement)
+  const AttnAsmKernel* gen;
+  dim3 grid, block;
+  int rows, lds;              // query rows per workgroup, dynamic LDS bytes
+  bool covered;               // want != ATTN_BF16: the generated kernel takes the call (only it has those forms; false = no route)
+};
+enum { ATTN_BF16, ATTN_QNORM, ATTN_QFMT };      // bf16 rows out of normed q; the q RMSNorm prologue; codes + scales out (fmt = LL_QFMT_*)
+
+// The one route decision, for launch, plan and _ok alike (host only, no HIP call).  k = attn_merge's ranges, ldk the key row stride.
+static AttnRoute attn_pick(const AttnKeys& k, int Lq, int H, int B, int ldk, int want, int fmt = 0) {
+  AttnRoute r{};
+  // The generated kernel: one key range of at least two key tiles (its first tile is a special case and so is its last; whatever the
+  // tuning key says, shorter ranges stay on the HIP kernels -- tests/test_attn_asm_emu.py::test_two_tiles_is_the_shortest_range)
+  // whose row offsets fit 32-bit byte counts
+  const int min_keys = g_attn.asm_min_keys > 2 * KT ? g_attn.asm_min_keys : 2 * KT;
+  const bool gen = g_attn.asm_on && g_attn.variant >= 2 && k.n1 == 0 && k.n0 >= min_keys && (long long)k.n0 * ldk * 2 < 0x7fffffffLL;
+  if (want != ATTN_BF16) {
+    // one plane of sums per 128 channels, at most 16 planes (NPART_MAX); the packed formats pair heads in a super-block
+    r.covered = gen && H >= 1 && (want == ATTN_QNORM ? H <= 16 : fmt == LL_QFMT_MX || !(H & 1));
+    if (!r.covered) return r;
   }
-  int nqt = (Lq + NW * 32 - 1) / (NW * 32);
-  dim3 grid(nqt * H, 1, B), block(NW * 64);
-  if (attn_asm_eligible(nkeys, ldk))
-    return flash_attn_asm_launch((const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, B, Lq, H, ldq, ldo, ldk, k_batch_stride,
-                                 kstart, nkeys, c, g_attn_xcd, g_attn_asm, (hipStream_t)stream);
-  if (g_attn_variant >= 2 && nkeys >= g_attn_pp_min_keys)   // short ranges (cross-attention, 512 keys): the one-barrier loop is faster
-    hipLaunchKernelGGL((flash_attn_pipe_kernel<NW, 1>), grid, block, (PIPE_KSTAGES + PIPE_VSTAGES + 2) * TILE_B,
-                       (hipStream_t)stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, Lq, ldq, ldo, ldk,
-                       k_batch_stride, kstart, nkeys, c, nqt, g_attn_xcd);
+  if (gen) {
+    r.gen = fa_kernel(want == ATTN_QNORM, want == ATTN_QFMT ? qfmt_bits(fmt) : 0);
+    r.fn = r.gen->fn, r.name = r.gen->name, r.form = "4 waves x 64 rows, one wave per SIMD, generated schedule";
+    r.rows = FA_ROWS, r.block = dim3(256), r.lds = FA_LDS;
+  } else if (g_attn.variant >= 1 && k.n1 == 0) {
+    // short ranges (cross-attention, 512 keys): the one-barrier loop is faster
+    const bool pp = g_attn.variant >= 2 && k.n0 >= g_attn.pp_min_keys;
+    r.fn = pp ? (const void*)flash_attn_pipe_kernel<8, 1> : (const void*)flash_attn_pipe_kernel<8, 0>;
+    r.name = pp ? "flash_attn_pipe_kernel<8, 1>" : "flash_attn_pipe_kernel<8, 0>", r.form = pp ? "ping-pong wave groups" : "one-barrier loop";
+    r.rows = 256, r.block = dim3(512), r.lds = (PIPE_KSTAGES + PIPE_VSTAGES + (pp ? 2 : 0)) * TILE_B;
+  } else {
+    r.fn = (const void*)flash_attn_kernel<4>, r.name = "flash_attn_kernel<4>";
+    r.rows = 128, r.block = dim3(256), r.lds = 4 * TILE_B;
+  }
+  const int nqt = (Lq + r.rows - 1) / r.rows;
+  r.grid = r.form ? dim3(nqt * H, 1, B) : dim3(nqt, H, B);      // (head, q-tile) pairs in x where the kernel places them itself
+  return r;
+}
+
+// "<symbol> (<structure>), N workgroups of R query rows": a route as the plans print it; qbits != 0 = the codes a quantised-output form writes
+static void attn_plan(const AttnRoute& r, int qbits, char* out, int cap) {
+  char codes[64] = "";
+  if (qbits) snprintf(codes, sizeof codes, ", %d-bit codes + E8M0 scales from the epilogue", qbits);
+  const int nwg = (int)(r.grid.x * r.grid.y * r.grid.z);
+  if (r.form)
+    snprintf(out, (size_t)cap, "%s (%s%s), %d workgroups of %d query rows%s", r.name, r.form, codes, nwg, r.rows,
+             g_attn.xcd ? ", XCD-aware placement" : "");
   else
-    hipLaunchKernelGGL((flash_attn_pipe_kernel<NW, 0>), grid, block, (PIPE_KSTAGES + PIPE_VSTAGES) * TILE_B,
-                       (hipStream_t)stream, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)out, Lq, ldq, ldo, ldk,
-                       k_batch_stride, kstart, nkeys, c, nqt, g_attn_xcd);
-  return ll_check_launch("ll_flash_attn(pipe)");
+    snprintf(out, (size_t)cap, "%s, %d workgroups of %d query rows", r.name, nwg, r.rows);
+  if (r.gen) ll_plan_append_knobs(out, cap);
+}
+
+// the one launch of the HIP kernels here (args in the kernel's order)
+static int attn_launch(const AttnRoute& r, void** args, ll_stream stream, const char* what) {
+  if (int rc = ll_lds_attr(r.fn, r.lds)) return rc;
+  (void)hipLaunchKernel(r.fn, r.grid, r.block, args, (size_t)r.lds, (hipStream_t)stream);
+  return ll_check_launch(what);
 }
 
 // Which kernel instance ll_flash_attn launches for these key ranges under the current tuning (host only).
 extern "C" int ll_flash_attn_plan(int Lq, int H, int B, int seg0_len, int seg1_len, int seg_adjacent, char* out, int cap) {
   LL_REQUIRE(out != nullptr && cap > 0, "ll_flash_attn_plan: needs an output buffer");
-  int n0 = seg0_len, n1 = seg1_len;
-  if (n1 > 0 && seg_adjacent) { n0 += n1; n1 = 0; }
-  if (g_attn_variant >= 1 && n1 == 0) {
-    int nqt = (Lq + 255) / 256;
-    bool pp = g_attn_variant >= 2 && n0 >= g_attn_pp_min_keys;
-    if (attn_asm_eligible(n0, H * 128))
-      snprintf(out, (size_t)cap, "%s (4 waves x 64 rows, one wave per SIMD, generated schedule), %d workgroups of 256 query rows%s",
-               "flash_attn_asm_kernel", nqt * H * B, g_attn_xcd ? ", XCD-aware placement" : ""), ll_plan_append_knobs(out, cap);
-    else
-      snprintf(out, (size_t)cap, "flash_attn_pipe_kernel<8, %d> (%s), %d workgroups of 256 query rows%s", pp ? 1 : 0,
-               pp ? "ping-pong wave groups" : "one-barrier loop", nqt * H * B, g_attn_xcd ? ", XCD-aware placement" : "");
-  } else {
-    snprintf(out, (size_t)cap, "flash_attn_kernel<4>, %d workgroups of 128 query rows", ((Lq + 127) / 128) * H * B);
-  }
+  // (lengths only: the second range sits at the first one's end, or one slot past it)
+  const AttnKeys ks = attn_merge(0, seg0_len, seg0_len + (seg_adjacent ? 0 : 1), seg1_len);
+  attn_plan(attn_pick(ks, Lq, H, B, H * 128, ATTN_BF16), 0, out, cap);
   return LL_OK;
 }
 
@@ -736,34 +744,31 @@ extern "C" int ll_flash_attn(const ll_bf16* q, const ll_bf16* k, const ll_bf16* 
   LL_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldk % 8 == 0, "ll_flash_attn: row strides must be multiples of 8 elements");
   LL_REQUIRE(ldq >= H * 128 && ldo >= H * 128 && ldk >= H * 128, "ll_flash_attn: row stride smaller than H*128");
   LL_REQUIRE(seg0_len > 0 && seg1_len >= 0 && seg0_start >= 0 && seg1_start >= 0, "ll_flash_attn: needs a non-empty first key range");
-  LL_REQUIRE(seg1_len == 0 || seg1_start >= seg0_start + seg0_len || seg1_start + seg1_len <= seg0_start, "ll_flash_attn: key ranges "
-             "[%d, +%d) and [%d, +%d) overlap (their shared keys would be counted twice)", seg0_start, seg0_len, seg1_start, seg1_len);
+  if (int rc = attn_check_ranges("ll_flash_attn", seg0_start, seg0_len, seg1_start, seg1_len, LL_ATTN_TWICE)) return rc;
   if (B == 0 || Lq == 0 || H == 0) return LL_OK;
-  Segs sg;
-  sg.s0 = seg0_start; sg.n0 = seg0_len; sg.s1 = seg1_start; sg.n1 = seg1_len;
-  if (sg.n1 > 0 && sg.s1 == sg.s0 + sg.n0) { sg.n0 += sg.n1; sg.n1 = 0; }   // contiguous: one range
-  sg.nt0 = (sg.n0 + KT - 1) / KT;
-  sg.nt = sg.nt0 + (sg.n1 + KT - 1) / KT;
-  float c = scale * 1.4426950408889634f;
-  if (g_attn_variant >= 1 && sg.n1 == 0)
-    return flash_attn_pipe_launch(q, k, v, out, B, Lq, H, ldq, ldo, ldk, k_batch_stride, sg.s0, sg.n0, c, stream);
-  constexpr int NW = 4;
-  dim3 grid((Lq + NW * 32 - 1) / (NW * 32), H, B), block(NW * 64);
-  hipLaunchKernelGGL(flash_attn_kernel<NW>, grid, block, 4 * TILE_B, (hipStream_t)stream, (const bf16*)q, (const bf16*)k,
-                     (const bf16*)v, (bf16*)out, Lq, ldq, ldo, ldk, k_batch_stride, sg, c);
-  return ll_check_launch("ll_flash_attn");
+  AttnKeys ks = attn_merge(seg0_start, seg0_len, seg1_start, seg1_len);
+  const AttnRoute r = attn_pick(ks, Lq, H, B, ldk, ATTN_BF16);
+  float c = scale * LL_LOG2E;
+  if (r.gen) {
+    AttnAsmArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, out, 0, ldq, ldo, ldk, k_batch_stride, ks.s0, ks.n0, c, 0, g_attn.xcd};
+    return fa_launch(*r.gen, a, B, Lq, H, (hipStream_t)stream, "ll_flash_attn(asm)");
+  }
+  if (r.form) {
+    int nqt = (int)r.grid.x / H;
+    void* args[] = {&q, &k, &v, &out, &Lq, &ldq, &ldo, &ldk, &k_batch_stride, &ks.s0, &ks.n0, &c, &nqt, &g_attn.xcd};
+    return attn_launch(r, args, stream, "ll_flash_attn(pipe)");
+  }
+  const int nt0 = (ks.n0 + KT - 1) / KT;
+  Segs sg{ks.s0, ks.n0, ks.s1, ks.n1, nt0, nt0 + (ks.n1 + KT - 1) / KT};
+  void* args[] = {&q, &k, &v, &out, &Lq, &ldq, &ldo, &ldk, &k_batch_stride, &sg, &c};
+  return attn_launch(r, args, stream, "ll_flash_attn");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Cross-attention with the q RMSNorm folded into the attention kernel (wan/modules/model.py:172,189: q = norm_q(self.q(x)), then
 // attention over the text keys): q is the RAW q projection, ssq[nplanes][B * Lq] its per-row sums of squares per 128-column plane
 // (ll_gemm_bf16_ssq).  Only the generated kernel has this prologue: ll_flash_attn_qnorm_ok says whether a launch is covered.
-int flash_attn_asm_qn_launch(const bf16* q, const float* ssq, int nplanes, const bf16* nw, float eps, const bf16* k, const bf16* v,
-                             bf16* out, int B, int Lq, int H, int ldq, int ldo, int ldk, long long k_batch_stride, int kstart, int nkeys,
-                             float c, int xcd, hipStream_t stream);
-extern "C" int ll_flash_attn_qnorm_ok(int H, int nkeys) {
-  return (attn_asm_eligible(nkeys, H * 128) && H >= 1 && H <= 16) ? 1 : 0;      // one plane per 128 channels, at most 16 planes (NPART_MAX)
-}
+extern "C" int ll_flash_attn_qnorm_ok(int H, int nkeys) { return attn_pick(AttnKeys{0, nkeys, 0, 0}, 0, H, 0, H * 128, ATTN_QNORM).covered ? 1 : 0; }
 extern "C" int ll_flash_attn_qnorm(const ll_bf16* q, const float* ssq, const ll_bf16* norm_w, float eps, const ll_bf16* k,
                                    const ll_bf16* v, ll_bf16* out, int B, int Lq, int H, int ldq, int ldo, int ldk,
                                    long long k_batch_stride, int key_start, int nkeys, float scale, ll_stream stream) {
@@ -771,12 +776,13 @@ extern "C" int ll_flash_attn_qnorm(const ll_bf16* q, const float* ssq, const ll_
   LL_REQUIRE(ldo % 4 == 0 && ldk % 8 == 0 && ldo >= H * 128 && ldk >= H * 128, "ll_flash_attn_qnorm: bad row strides");
   LL_REQUIRE(ssq != nullptr && norm_w != nullptr, "ll_flash_attn_qnorm: ssq and norm_w are required");
   LL_REQUIRE(key_start >= 0 && nkeys > 0, "ll_flash_attn_qnorm: needs a non-empty key range");
-  LL_REQUIRE(ll_flash_attn_qnorm_ok(H, nkeys), "ll_flash_attn_qnorm: %d keys x %d heads is not covered by the generated kernel under the "
+  const AttnRoute r = attn_pick(AttnKeys{key_start, nkeys, 0, 0}, Lq, H, B, H * 128, ATTN_QNORM);      // (as ll_flash_attn_qnorm_ok asks it)
+  LL_REQUIRE(r.covered, "ll_flash_attn_qnorm: %d keys x %d heads is not covered by the generated kernel under the "
              "current tuning (ask ll_flash_attn_qnorm_ok first and run ll_rmsnorm + ll_flash_attn instead)", nkeys, H);
   if (B == 0 || Lq == 0) return LL_OK;
-  return flash_attn_asm_qn_launch((const bf16*)q, ssq, H, (const bf16*)norm_w, eps, (const bf16*)k, (const bf16*)v, (bf16*)out, B, Lq, H,
-                                  ldq, ldo, ldk, k_batch_stride, key_start, nkeys, scale * 1.4426950408889634f, g_attn_xcd,
-                                  (hipStream_t)stream);
+  AttnAsmArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, out, 0, ldq, ldo, ldk, k_batch_stride, key_start, nkeys, scale * LL_LOG2E, 0,
+                g_attn.xcd, nullptr, 0, ssq, H, (long long)B * Lq, (const bf16*)norm_w, 1.0f / (float)(H * 128), eps};
+  return fa_launch(*r.gen, a, B, Lq, H, (hipStream_t)stream, "ll_flash_attn_qnorm(asm)");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -784,31 +790,24 @@ extern "C" int ll_flash_attn_qnorm(const ll_bf16* q, const float* ssq, const ll_
 // ll_flash_attn would have written (mx.h / mx6.h / mx4.h), so the stand-alone ll_quantize_mx* pass over them disappears.  A scale block
 // is 32 channels of one row and a head is 128: the four blocks of a (row, head) live in the workgroup that computes the head.  Only the
 // generated kernel has this epilogue: ll_flash_attn_q_ok says whether a launch is covered.
-int flash_attn_asm_q_launch(int fmt, const bf16* q, const bf16* k, const bf16* v, uint8_t* codes, int ldc, uint8_t* scales, int lds, int B,
-                            int Lq, int H, int ldq, int ldk, long long k_batch_stride, int kstart, int nkeys, float c, int xcd,
-                            hipStream_t stream);
-static int qfmt_bits(int fmt) { return fmt == LL_QFMT_MX ? 8 : fmt == LL_QFMT_MX6 ? 6 : fmt == LL_QFMT_MX4 ? 4 : 0; }
-static const char* qfmt_name(int fmt) { return fmt == LL_QFMT_MX ? "mx" : fmt == LL_QFMT_MX6 ? "mx6" : "mx4"; }
-// one contiguous key range (after merging adjacent ones) that the generated kernel takes; packed formats pair heads in a super-block
-static bool attn_q_covered(int fmt, int H, int ldk, int s0, int n0, int s1, int n1, int* start, int* nkeys) {
-  if (!qfmt_bits(fmt) || H < 1 || n0 <= 0 || n1 < 0 || s0 < 0 || s1 < 0) return false;
-  if (n1 > 0 && s1 == s0 + n0) { n0 += n1; n1 = 0; }
-  if (n1 > 0 || (fmt != LL_QFMT_MX && (H & 1))) return false;
-  if (start) *start = s0;
-  if (nkeys) *nkeys = n0;
-  return attn_asm_eligible(n0, ldk);
+// The route of such a call from its raw arguments: covered = one contiguous key range (after merging adjacent ones) that the generated
+// kernel takes; ks = that range
+static AttnRoute attn_q_pick(int fmt, int Lq, int H, int B, int ldk, int s0, int n0, int s1, int n1, AttnKeys* ks = nullptr) {
+  if (!qfmt_bits(fmt) || n0 <= 0 || n1 < 0 || s0 < 0 || s1 < 0) return AttnRoute{};
+  const AttnKeys m = attn_merge(s0, n0, s1, n1);
+  if (ks) *ks = m;
+  return attn_pick(m, Lq, H, B, ldk, ATTN_QFMT, fmt);
 }
 extern "C" int ll_flash_attn_q_ok(int fmt, int H, int seg0_start, int seg0_len, int seg1_start, int seg1_len) {
-  return attn_q_covered(fmt, H, H * 128, seg0_start, seg0_len, seg1_start, seg1_len, nullptr, nullptr) ? 1 : 0;
+  return attn_q_pick(fmt, 0, H, 0, H * 128, seg0_start, seg0_len, seg1_start, seg1_len).covered ? 1 : 0;
 }
 extern "C" int ll_flash_attn_q_plan(int fmt, int Lq, int H, int B, int seg0_start, int seg0_len, int seg1_start, int seg1_len, char* out,
                                     int cap) {
   LL_REQUIRE(out != nullptr && cap > 0, "ll_flash_attn_q_plan: needs an output buffer");
   LL_REQUIRE(qfmt_bits(fmt) != 0, "ll_flash_attn_q_plan: fmt=%d is none of LL_QFMT_MX / MX6 / MX4", fmt);
-  if (ll_flash_attn_q_ok(fmt, H, seg0_start, seg0_len, seg1_start, seg1_len))
-    snprintf(out, (size_t)cap, "flash_attn_asm_%s_kernel (4 waves x 64 rows, one wave per SIMD, generated schedule, %d-bit codes + E8M0 "
-             "scales from the epilogue), %d workgroups of 256 query rows%s", qfmt_name(fmt), qfmt_bits(fmt), ((Lq + 255) / 256) * H * B,
-             g_attn_xcd ? ", XCD-aware placement" : ""), ll_plan_append_knobs(out, cap);
+  const AttnRoute r = attn_q_pick(fmt, Lq, H, B, H * 128, seg0_start, seg0_len, seg1_start, seg1_len);
+  if (r.covered)
+    attn_plan(r, qfmt_bits(fmt), out, cap);
   else
     snprintf(out, (size_t)cap, "not covered by the generated kernel: ll_flash_attn + ll_quantize_%s", qfmt_name(fmt));
   return LL_OK;
@@ -825,14 +824,15 @@ extern "C" int ll_flash_attn_q(int fmt, const ll_bf16* q, const ll_bf16* k, cons
              "multiples of 8)", ldq, ldk);
   LL_REQUIRE(ldc % 16 == 0 && ldc >= H * 16 * bits && lds % 4 == 0 && lds >= H * 4, "ll_flash_attn_q: code row stride %d bytes (>= %d, a "
              "multiple of 16) or scale row stride %d bytes (>= %d, a multiple of 4)", ldc, H * 16 * bits, lds, H * 4);
-  LL_REQUIRE(seg1_len <= 0 || seg1_start >= seg0_start + seg0_len || seg1_start + seg1_len <= seg0_start, "ll_flash_attn_q: key ranges "
-             "[%d, +%d) and [%d, +%d) overlap", seg0_start, seg0_len, seg1_start, seg1_len);
-  int kstart = 0, nkeys = 0;
-  LL_REQUIRE(attn_q_covered(fmt, H, ldk, seg0_start, seg0_len, seg1_start, seg1_len, &kstart, &nkeys), "ll_flash_attn_q: key ranges "
+  if (int rc = attn_check_ranges("ll_flash_attn_q", seg0_start, seg0_len, seg1_start, seg1_len, "")) return rc;
+  AttnKeys ks{};
+  const AttnRoute r = attn_q_pick(fmt, Lq, H, B, ldk, seg0_start, seg0_len, seg1_start, seg1_len, &ks);
+  LL_REQUIRE(r.covered, "ll_flash_attn_q: key ranges "
              "[%d, +%d) [%d, +%d) x %d heads in format %s are not covered by the generated kernel under the current tuning (ask "
              "ll_flash_attn_q_ok first and run ll_flash_attn + ll_quantize_%s instead)", seg0_start, seg0_len, seg1_start, seg1_len, H,
              qfmt_name(fmt), qfmt_name(fmt));
   if (B == 0 || Lq == 0) return LL_OK;
-  return flash_attn_asm_q_launch(fmt, (const bf16*)q, (const bf16*)k, (const bf16*)v, codes, ldc, scales, lds, B, Lq, H, ldq, ldk,
-                                 k_batch_stride, kstart, nkeys, scale * 1.4426950408889634f, g_attn_xcd, (hipStream_t)stream);
+  AttnAsmArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, codes, 0, ldq, ldc, ldk, k_batch_stride, ks.s0, ks.n0, scale * LL_LOG2E, 0,
+                g_attn.xcd, scales, lds};
+  return fa_launch(*r.gen, a, B, Lq, H, (hipStream_t)stream, "ll_flash_attn_q(asm)");
 }

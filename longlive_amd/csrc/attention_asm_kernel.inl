@@ -1,4 +1,4 @@
-// included by attention_asm.hip once per staging form with LL_ASM_NAME / LL_ASM_INC defined
+// included once per kernel (attention_asm_each.inl; tools/attn_asm_diag.hip) with LL_ASM_NAME / LL_ASM_INC defined
 __global__ __launch_bounds__(256, 1) void LL_ASM_NAME(const bf16* __restrict__ Q, const bf16* __restrict__ Kc,
                                                                 const bf16* __restrict__ Vc,
 #ifdef LL_ASM_QOUT

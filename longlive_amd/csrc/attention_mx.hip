@@ -25,7 +25,7 @@
 // masked to -inf.  Adjacent segments are merged first (as ll_flash_attn does).
 #include <stdio.h>
 
-#include "common.h"
+#include "attention_common.h"
 #include "mx.h"
 #include "mx4.h"
 #include "mx6.h"
@@ -396,12 +396,11 @@ __global__ __launch_bounds__(MXA_NW * 64, 2) void flash_attn_mx_kernel(const bf1
 // ---------------------------------------------------------------------------------------------------------------
 // Host side
 static MxSegs mx_segs(int s0, int n0, int s1, int n1) {
+  const AttnKeys k = attn_merge(s0, n0, s1, n1);      // adjacent: one range (as ll_flash_attn)
   MxSegs sg;
-  if (n1 > 0 && s1 == s0 + n0) { n0 += n1; n1 = 0; }     // adjacent: one range (as ll_flash_attn)
-  if (n1 <= 0) { s1 = 0; n1 = 0; }
-  sg.a0 = s0; sg.e0 = s0 + n0; sg.a1 = s1; sg.e1 = s1 + n1;
+  sg.a0 = k.s0; sg.e0 = k.s0 + k.n0; sg.a1 = k.s1; sg.e1 = k.s1 + k.n1;
   sg.nt0 = (sg.e0 - (sg.a0 & ~31) + MXA_KT - 1) / MXA_KT;
-  sg.nt = sg.nt0 + (n1 > 0 ? (sg.e1 - (sg.a1 & ~31) + MXA_KT - 1) / MXA_KT : 0);
+  sg.nt = sg.nt0 + (k.n1 > 0 ? (sg.e1 - (sg.a1 & ~31) + MXA_KT - 1) / MXA_KT : 0);
   return sg;
 }
 
@@ -411,9 +410,7 @@ static int mx_attn_check_segs(const char* fn, int S, int S32, int s0, int n0, in
              s0, n0, S);
   LL_REQUIRE(n1 >= 0 && (n1 == 0 || (s1 >= 0 && s1 + n1 <= S)), "%s: second key range [%d, +%d) outside the cache of %d slots", fn, s1,
              n1, S);
-  LL_REQUIRE(n1 == 0 || s1 >= s0 + n0 || s1 + n1 <= s0, "%s: key ranges [%d, +%d) and [%d, +%d) overlap (their shared keys would be "
-             "counted twice)", fn, s0, n0, s1, n1);
-  return LL_OK;
+  return attn_check_ranges(fn, s0, n0, s1, n1, LL_ATTN_TWICE);
 }
 
 extern "C" int ll_kv_shadow_mx(const ll_bf16* k, const ll_bf16* v, uint8_t* kq, uint8_t* ks, uint8_t* vq, uint8_t* vs, int B, int S,
@@ -442,55 +439,61 @@ extern "C" int ll_flash_attn_mx_plan(int Lq, int H, int B, int seg0_start, int s
   return LL_OK;
 }
 
+// The kernel instance per output form: index 0 = bf16 rows, LL_QFMT_MX / MX6 / MX4 = the codes + E8M0 scales of those rows
+static const void* flash_attn_mx_instance(int fmt) {
+  static const void* const t[] = {(const void*)flash_attn_mx_kernel<0>, (const void*)flash_attn_mx_kernel<LL_QFMT_MX>,
+                                  (const void*)flash_attn_mx_kernel<LL_QFMT_MX6>, (const void*)flash_attn_mx_kernel<LL_QFMT_MX4>};
+  return t[fmt];
+}
+
+// The one body of ll_flash_attn_mx (qout = false, fmt = 0: out = bf16 rows of stride ldo elements, no scales) and ll_flash_attn_mx_q
+// (out = the code rows of stride ldo BYTES, scales of stride lds): the checks in the entries' order and words, one launch.
+static int mx_attn_call(const char* fn, bool qout, int fmt, const ll_bf16* q, const uint8_t* kq, const uint8_t* ks, const uint8_t* vq,
+                        const uint8_t* vs, void* out, uint8_t* scales, int B, int Lq, int H, int head_dim, int ldq, int ldo, int lds, int S,
+                        int S32, int s0, int n0, int s1, int n1, float scale, ll_stream stream) {
+  const int bits = qfmt_bits(fmt);
+  if (qout) {
+    LL_REQUIRE(bits != 0, "%s: fmt=%d is none of LL_QFMT_MX / MX6 / MX4", fn, fmt);
+    LL_REQUIRE(q != nullptr && out != nullptr && scales != nullptr, "%s: q, codes and scales are required", fn);
+  } else {
+    LL_REQUIRE(q != nullptr && out != nullptr, "%s: q and out are required", fn);
+  }
+  LL_REQUIRE(kq != nullptr && ks != nullptr && vq != nullptr && vs != nullptr, "%s: shadow codes and scales of K and V are required", fn);
+  LL_REQUIRE(head_dim == 128, "%s: head_dim=%d (the kernel is specialised for 128)", fn, head_dim);
+  LL_REQUIRE(B >= 0 && Lq >= 0 && H > 0, "%s: B=%d Lq=%d H=%d", fn, B, Lq, H);
+  if (qout) {
+    LL_REQUIRE(fmt == LL_QFMT_MX || (H & 1) == 0, "%s: the packed formats pair heads in 256-k super-blocks: H=%d must be even", fn, H);
+    LL_REQUIRE(ldq % 8 == 0 && ldq >= H * 128, "%s: row stride ldq=%d (>= H*128, a multiple of 8)", fn, ldq);
+    LL_REQUIRE(ldo % 16 == 0 && ldo >= H * 16 * bits && lds % 4 == 0 && lds >= H * 4, "%s: code row stride %d bytes (>= %d, a "
+               "multiple of 16) or scale row stride %d bytes (>= %d, a multiple of 4)", fn, ldo, H * 16 * bits, lds, H * 4);
+  } else {
+    LL_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldq >= H * 128 && ldo >= H * 128, "%s: row strides ldq=%d ldo=%d (>= H*128, "
+               "multiples of 8 / 4)", fn, ldq, ldo);
+  }
+  if (int rc = mx_attn_check_segs(fn, S, S32, s0, n0, s1, n1)) return rc;
+  LL_REQUIRE(scale > 0.f && scale <= 3.0e38f, "%s: scale=%g must be positive and finite%s", fn, (double)scale,
+             qout ? "" : " (the tile maximum is taken before the multiplication by scale * log2 e)");
+  if (B == 0 || Lq == 0) return LL_OK;
+  MxSegs sg = mx_segs(s0, n0, s1, n1);
+  float c = scale * LL_LOG2E;
+  const void* k = flash_attn_mx_instance(fmt);
+  if (int rc = ll_lds_attr(k, 2 * MXA_STAGE)) return rc;
+  void* args[] = {&q, &kq, &ks, &vq, &vs, &out, &Lq, &ldq, &ldo, &H, &S32, &sg, &c, &scales, &lds};
+  (void)hipLaunchKernel(k, dim3((Lq + MXA_NW * 32 - 1) / (MXA_NW * 32), H, B), dim3(MXA_NW * 64), args, 2 * MXA_STAGE, (hipStream_t)stream);
+  return ll_check_launch(fn);
+}
+
 extern "C" int ll_flash_attn_mx(const ll_bf16* q, const uint8_t* kq, const uint8_t* ks, const uint8_t* vq, const uint8_t* vs, ll_bf16* out,
                                 int B, int Lq, int H, int head_dim, int ldq, int ldo, int S, int S32, int seg0_start, int seg0_len,
                                 int seg1_start, int seg1_len, float scale, ll_stream stream) {
-  LL_REQUIRE(q != nullptr && out != nullptr, "ll_flash_attn_mx: q and out are required");
-  LL_REQUIRE(kq != nullptr && ks != nullptr && vq != nullptr && vs != nullptr, "ll_flash_attn_mx: shadow codes and scales of K and V are required");
-  LL_REQUIRE(head_dim == 128, "ll_flash_attn_mx: head_dim=%d (the kernel is specialised for 128)", head_dim);
-  LL_REQUIRE(B >= 0 && Lq >= 0 && H > 0, "ll_flash_attn_mx: B=%d Lq=%d H=%d", B, Lq, H);
-  LL_REQUIRE(ldq % 8 == 0 && ldo % 4 == 0 && ldq >= H * 128 && ldo >= H * 128, "ll_flash_attn_mx: row strides ldq=%d ldo=%d (>= H*128, "
-             "multiples of 8 / 4)", ldq, ldo);
-  if (int rc = mx_attn_check_segs("ll_flash_attn_mx", S, S32, seg0_start, seg0_len, seg1_start, seg1_len)) return rc;
-  LL_REQUIRE(scale > 0.f && scale <= 3.0e38f, "ll_flash_attn_mx: scale=%g must be positive and finite (the tile maximum is taken before "
-             "the multiplication by scale * log2 e)", (double)scale);
-  if (B == 0 || Lq == 0) return LL_OK;
-  const MxSegs sg = mx_segs(seg0_start, seg0_len, seg1_start, seg1_len);
-  const dim3 grid((Lq + MXA_NW * 32 - 1) / (MXA_NW * 32), H, B), block(MXA_NW * 64);
-  if (int rc = ll_lds_attr((const void*)flash_attn_mx_kernel<0>, 2 * MXA_STAGE)) return rc;
-  hipLaunchKernelGGL(flash_attn_mx_kernel<0>, grid, block, 2 * MXA_STAGE, (hipStream_t)stream, (const bf16*)q, kq, ks, vq, vs, (bf16*)out, Lq,
-                     ldq, ldo, H, S32, sg, scale * 1.4426950408889634f, (uint8_t*)nullptr, 0);
-  return ll_check_launch("ll_flash_attn_mx");
+  return mx_attn_call("ll_flash_attn_mx", false, 0, q, kq, ks, vq, vs, out, nullptr, B, Lq, H, head_dim, ldq, ldo, 0, S, S32, seg0_start,
+                      seg0_len, seg1_start, seg1_len, scale, stream);
 }
 
 // ll_flash_attn_mx with the codes + E8M0 scales of its bf16 rows as output (include/longlive_hip.h: ll_flash_attn_q's contract)
 extern "C" int ll_flash_attn_mx_q(int fmt, const ll_bf16* q, const uint8_t* kq, const uint8_t* ks, const uint8_t* vq, const uint8_t* vs,
                                   uint8_t* codes, uint8_t* scales, int B, int Lq, int H, int head_dim, int ldq, int ldc, int lds, int S,
                                   int S32, int seg0_start, int seg0_len, int seg1_start, int seg1_len, float scale, ll_stream stream) {
-  const int bits = fmt == LL_QFMT_MX ? 8 : fmt == LL_QFMT_MX6 ? 6 : fmt == LL_QFMT_MX4 ? 4 : 0;
-  LL_REQUIRE(bits != 0, "ll_flash_attn_mx_q: fmt=%d is none of LL_QFMT_MX / MX6 / MX4", fmt);
-  LL_REQUIRE(q != nullptr && codes != nullptr && scales != nullptr, "ll_flash_attn_mx_q: q, codes and scales are required");
-  LL_REQUIRE(kq != nullptr && ks != nullptr && vq != nullptr && vs != nullptr, "ll_flash_attn_mx_q: shadow codes and scales of K and V are required");
-  LL_REQUIRE(head_dim == 128, "ll_flash_attn_mx_q: head_dim=%d (the kernel is specialised for 128)", head_dim);
-  LL_REQUIRE(B >= 0 && Lq >= 0 && H > 0, "ll_flash_attn_mx_q: B=%d Lq=%d H=%d", B, Lq, H);
-  LL_REQUIRE(fmt == LL_QFMT_MX || (H & 1) == 0, "ll_flash_attn_mx_q: the packed formats pair heads in 256-k super-blocks: H=%d must be even", H);
-  LL_REQUIRE(ldq % 8 == 0 && ldq >= H * 128, "ll_flash_attn_mx_q: row stride ldq=%d (>= H*128, a multiple of 8)", ldq);
-  LL_REQUIRE(ldc % 16 == 0 && ldc >= H * 16 * bits && lds % 4 == 0 && lds >= H * 4, "ll_flash_attn_mx_q: code row stride %d bytes (>= %d, a "
-             "multiple of 16) or scale row stride %d bytes (>= %d, a multiple of 4)", ldc, H * 16 * bits, lds, H * 4);
-  if (int rc = mx_attn_check_segs("ll_flash_attn_mx_q", S, S32, seg0_start, seg0_len, seg1_start, seg1_len)) return rc;
-  LL_REQUIRE(scale > 0.f && scale <= 3.0e38f, "ll_flash_attn_mx_q: scale=%g must be positive and finite", (double)scale);
-  if (B == 0 || Lq == 0) return LL_OK;
-  const MxSegs sg = mx_segs(seg0_start, seg0_len, seg1_start, seg1_len);
-  const dim3 grid((Lq + MXA_NW * 32 - 1) / (MXA_NW * 32), H, B), block(MXA_NW * 64);
-#define LL_MXQ_LAUNCH(F)                                                                                                           \
-  {                                                                                                                                \
-    if (int rc = ll_lds_attr((const void*)flash_attn_mx_kernel<F>, 2 * MXA_STAGE)) return rc;                                      \
-    hipLaunchKernelGGL(flash_attn_mx_kernel<F>, grid, block, 2 * MXA_STAGE, (hipStream_t)stream, (const bf16*)q, kq, ks, vq, vs,   \
-                       (bf16*)codes, Lq, ldq, ldc, H, S32, sg, scale * 1.4426950408889634f, scales, lds);                          \
-  }
-  if (fmt == LL_QFMT_MX) LL_MXQ_LAUNCH(LL_QFMT_MX)
-  else if (fmt == LL_QFMT_MX6) LL_MXQ_LAUNCH(LL_QFMT_MX6)
-  else LL_MXQ_LAUNCH(LL_QFMT_MX4)
-#undef LL_MXQ_LAUNCH
-  return ll_check_launch("ll_flash_attn_mx_q");
+  return mx_attn_call("ll_flash_attn_mx_q", true, fmt, q, kq, ks, vq, vs, codes, scales, B, Lq, H, head_dim, ldq, ldc, lds, S, S32,
+                      seg0_start, seg0_len, seg1_start, seg1_len, scale, stream);
 }

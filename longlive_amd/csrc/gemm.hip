@@ -24,6 +24,7 @@
 #include <string.h>
 #include <atomic>
 
+#include "attention_common.h"
 #include "gemm_asm.h"
 #include "gemm_common.h"
 #include "mx.h"
@@ -191,11 +192,6 @@ static int g_gemm_variant_wide = 0;  // like gemm_variant, but only for N >= 409
 static int g_gemm_lds_epi = 1;
 static int g_gemm_asm = 35;        // generated kernels where they cover the call (bits 0, 1), persistent form for multi-round launches (bit 5)
 static int g_gemm_group_m = 4;     // m-tiles per group in the workgroup -> tile walk (tile_of); <= 1: N fastest (round 1's order)
-void ll_set_attn_variant_internal(int v);
-void ll_set_attn_xcd_internal(int v);
-void ll_set_attn_pp_min_internal(int v);
-void ll_set_attn_asm_min_internal(int v);
-void ll_set_attn_asm_internal(int v);
 void ll_set_conv_halo_internal(int v);
 extern "C" int ll_set_tuning(const char* key, int value) {
   if (!strcmp(key, "gemm_variant")) { g_gemm_variant = value; return LL_OK; }
@@ -208,11 +204,11 @@ extern "C" int ll_set_tuning(const char* key, int value) {
     g_gemm_lds_epi = value;
     return LL_OK;
   }
-  if (!strcmp(key, "attn_variant")) { ll_set_attn_variant_internal(value); return LL_OK; }
-  if (!strcmp(key, "attn_xcd")) { ll_set_attn_xcd_internal(value); return LL_OK; }
-  if (!strcmp(key, "attn_pp_min_keys")) { ll_set_attn_pp_min_internal(value); return LL_OK; }
-  if (!strcmp(key, "attn_asm_min_keys")) { ll_set_attn_asm_min_internal(value); return LL_OK; }
-  if (!strcmp(key, "attn_asm")) { ll_set_attn_asm_internal(value); return LL_OK; }
+  if (!strcmp(key, "attn_variant")) { g_attn.variant = value; return LL_OK; }
+  if (!strcmp(key, "attn_xcd")) { g_attn.xcd = value; return LL_OK; }
+  if (!strcmp(key, "attn_pp_min_keys")) { g_attn.pp_min_keys = value; return LL_OK; }
+  if (!strcmp(key, "attn_asm_min_keys")) { g_attn.asm_min_keys = value; return LL_OK; }
+  if (!strcmp(key, "attn_asm")) { g_attn.asm_on = value; return LL_OK; }
   if (!strcmp(key, "conv_halo")) { ll_set_conv_halo_internal(value); return LL_OK; }
   if (!strcmp(key, "gemm_asm_mfma16")) {
     if (value < -1 || value > 511) { ll_set_error("ll_set_tuning: gemm_asm_mfma16=%d (a mask of 9 bits, one per kernel; -1 = the default)", value); return LL_ERR_INVALID_ARG; }
