@@ -53,7 +53,8 @@ enum ll_epilogue {
  * linears (ll_gemm_mx4, ll_gemm_mx4_qkv, ll_ln_modulate_mx4, ll_ln_modulate_tab_mx4, ll_layernorm_affine_mx4, ll_gemm_plan_mx4) only
  * add entry points, so they keep 111; so does ll_conv_plan, and so do the VAE encoder's entry points (ll_conv_cl_down, ll_conv_cl_tdown,
  * ll_conv_down_plan, ll_pixels_to_cl, ll_vae_scale_tchw), and so do the attention entry points with quantised output
- * (ll_flash_attn_q_ok, ll_flash_attn_q, ll_flash_attn_q_plan, ll_flash_attn_mx_q): 111 covers them too. */
+ * (ll_flash_attn_q_ok, ll_flash_attn_q, ll_flash_attn_q_plan, ll_flash_attn_mx_q), and so does the uint8 video intake
+ * (ll_pixels_u8_to_cl): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -542,6 +543,13 @@ int ll_conv_down_plan(int kind, int T, int H, int W, int Cin, int Cout, char* ou
  * Cpad in {8, 16, 32}.  encoder.conv1 (vae.py:288, 3 -> 96) then runs on ll_conv_cl with zero-padded weights. */
 int ll_pixels_to_cl(const void* px, int is_f32, long long stride_c, long long stride_t, ll_bf16* out, int T, int H, int W, int Cpad,
                     ll_stream stream);
+
+/* Encoder input from video frames: uint8 px [T,H,W,3] (rows and pixels contiguous, stride_t in BYTES >= H*W*3) -> channels-last bf16
+ * [T,H,W,Cpad], channels >= 3 zero, Cpad in {8, 16, 32}, out 16-byte aligned.  Value, as a bit pattern:
+ *   out = bf16_rne(fsub_rn(fdiv_rn((float)u, 127.5f), 1.0f)),
+ * what `(u.float() / 127.5 - 1).to(torch.bfloat16)` gives: 0 -> -1 and 255 -> +1 exactly, no FMA contraction.  Bytes of px outside the
+ * T frames of H*W*3 bytes are never read. */
+int ll_pixels_u8_to_cl(const uint8_t* px, long long stride_t, ll_bf16* out, int T, int H, int W, int Cpad, ll_stream stream);
 
 /* Latent scaling of WanVAE_.encode (vae.py:537-539) with scale = [bf16(mean), bf16(1 / bf16(std))] (utils/wan_wrapper.py:83-84), the
  * layout change and .float() (wan_wrapper.py:87): channels-last mu [T,h,w,ld] (first z_dim channels) -> fp32 [T,z_dim,h,w] =

@@ -70,6 +70,7 @@ SIGNATURES = {
     "ll_conv_cl_tdown": [_p] * 5 + [_i] * 7 + [_p],
     "ll_conv_down_plan": [_i] * 6 + [C.c_char_p, _i],
     "ll_pixels_to_cl": [_p, _i, _ll, _ll, _p, _i, _i, _i, _i, _p],
+    "ll_pixels_u8_to_cl": [_p, _ll, _p, _i, _i, _i, _i, _p],
     "ll_vae_scale_tchw": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ll_t5_rmsnorm": [_p, _p, _p, _i, _i, _f, _p],
     "ll_t5_gated_gelu": [_p, _p, _ll, _i, _p],

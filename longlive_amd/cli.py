@@ -11,6 +11,9 @@ here is host logic; the models are longlive_amd's HIP modules (generator, VAE de
 
 Extra key, because this repository cannot ship checkpoints: `synthetic: true` (or `--synthetic`) runs random-init weights
 (longlive_amd.synth) and a hash tokenizer, optionally shrunk by `synthetic_overrides: {num_layers, t5_layers, lat_h, lat_w}`.
+
+Extra keys, both modes: `input_video: <path>` continues a clip -- every prompt of the data file continues the same one -- and
+`input_frames: <int>` caps how many of its frames are used (the LAST 1 + 4k frames that fit).
 """
 from __future__ import annotations
 
@@ -211,6 +214,55 @@ def write_video(path: str, frames: torch.Tensor, fps: int = 16) -> str:
     return path
 
 
+def select_clip_frames(total: int, cap: Optional[int] = None) -> slice:
+    """Which frames of a `total`-frame clip are continued: the last 1 + 4k with the largest k that fits the clip and the cap (the
+    VAE encoder takes 1 frame, then 4 per latent).  The END of the clip is what gets continued, so frames are dropped at the front."""
+    if isinstance(total, bool) or int(total) < 1:
+        raise ValueError(f"input_video: the clip holds {total} frames, at least 1 is needed")
+    room = int(total)
+    if cap is not None:
+        if isinstance(cap, bool) or int(cap) < 1:
+            raise ValueError(f"input_frames: {cap!r} must be an integer >= 1")
+        room = min(room, int(cap))
+    used = 1 + 4 * ((room - 1) // 4)
+    return slice(int(total) - used, int(total))
+
+
+def read_input_video(path: str) -> torch.Tensor:
+    """uint8 [T, H, W, 3] RGB frames of `path`: an .avi as write_avi_rgb24 writes it, a .pt holding such a tensor, anything else
+    through torchvision.io.read_video when torchvision + PyAV exist."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".avi":
+        frames = read_avi_rgb24(path)
+    elif ext == ".pt":
+        frames = torch.load(path, map_location="cpu", weights_only=True)      # a bare tensor: nothing is unpickled
+    else:
+        try:
+            from torchvision.io import read_video as tv_read        # noqa: WPS433 (optional dependency)
+            import av                                               # noqa: F401  (what torchvision's reader needs)
+        except ImportError:
+            raise RuntimeError(f"input_video: cannot read {path!r} without torchvision + PyAV; the formats read without them "
+                               f"are an uncompressed RGB24 .avi (write_avi_rgb24) and a .pt holding a uint8 [T, H, W, 3] tensor") from None
+        frames = tv_read(path, pts_unit="sec", output_format="THWC")[0]
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        what = f"{frames.dtype} {tuple(frames.shape)}" if torch.is_tensor(frames) else type(frames).__name__
+        raise ValueError(f"input_video: {path!r} holds {what}, expected uint8 frames [T, H, W, 3]")
+    return frames
+
+
+def load_clip(config, lat_h: int, lat_w: int) -> Optional[torch.Tensor]:
+    """The frames the yaml's `input_video` / `input_frames` keys select (host, uint8 [1 + 4k, H, W, 3]); None without the key.  The
+    clip must already have the configured pixel size: nothing is resized."""
+    path = config.get("input_video")
+    if not path:
+        return None
+    frames = read_input_video(str(path))
+    if tuple(frames.shape[1:3]) != (8 * lat_h, 8 * lat_w):
+        raise ValueError(f"input_video: {path!r} is {frames.shape[2]}x{frames.shape[1]} (W x H), the configured size is "
+                         f"{8 * lat_w}x{8 * lat_h}; clips are not resized")
+    return frames[select_clip_frames(frames.shape[0], config.get("input_frames"))].contiguous()
+
+
 # ---- tokenizers --------------------------------------------------------------------------------------------------------
 class HashTokenizer:
     """Stand-in for HuggingfaceTokenizer when no tokenizer files exist (synthetic mode): whitespace words -> crc32 ids,
@@ -260,6 +312,15 @@ def hf_tokenizer(path: str, seq_len: int = 512):
 
 
 # ---- model construction --------------------------------------------------------------------------------------------------
+def wan_config(config, synthetic: bool):
+    """The generator's shape: LongLive-1.3B, in synthetic mode shrunk by `synthetic_overrides`."""
+    from . import synth
+    mk = config.model_kwargs
+    ov = config.get("synthetic_overrides", Config()) if synthetic else Config()
+    wkw = {k: ov.get(k) for k in ("num_layers", "lat_h", "lat_w") if ov.get(k) is not None}
+    return synth.longlive_1_3b(local_attn_size=mk.local_attn_size, sink_size=mk.sink_size, **wkw)
+
+
 def build_models(config, device, synthetic: bool):
     from . import synth
     from .checkpoint import load_generator
@@ -268,15 +329,17 @@ def build_models(config, device, synthetic: bool):
     from .wan_wrapper import WanDiffusionWrapper
     mk = config.model_kwargs
     ov = config.get("synthetic_overrides", Config()) if synthetic else Config()
-    wkw = {k: ov.get(k) for k in ("num_layers", "lat_h", "lat_w") if ov.get(k) is not None}
-    wcfg = synth.longlive_1_3b(local_attn_size=mk.local_attn_size, sink_size=mk.sink_size, **wkw)
+    wcfg = wan_config(config, synthetic)
     lora_enabled = False
     if synthetic:
         tcfg = synth.T5Config(vocab_size=4096, num_layers=ov.get("t5_layers", 24))
         gen = WanDiffusionWrapper(timestep_shift=mk.timestep_shift, local_attn_size=mk.local_attn_size, sink_size=mk.sink_size,
                                   cfg=wcfg, device=device, state_dict=synth.synth_state_dict(wcfg, seed=0, device=device))
         vae = WanVAEWrapper(device=device)
-        vae.load_state_dict(synth.synth_vae_state_dict(synth.VaeConfig(), seed=5, device=device))
+        vsd = synth.synth_vae_state_dict(synth.VaeConfig(), seed=5, device=device)
+        if config.get("input_video"):               # a clip to continue needs the encoder half too
+            vsd.update(synth.synth_vae_encoder_state_dict(synth.VaeConfig(), seed=6, device=device))
+        vae.load_state_dict(vsd)
         enc = WanTextEncoder(tcfg, device=device, tokenizer=HashTokenizer(tcfg.vocab_size, tcfg.text_len))
         enc.load_state_dict(synth.synth_t5_state_dict(tcfg, seed=7, device=device))
     else:
@@ -326,7 +389,7 @@ def _dist_env():
 
 def run(mode: str, config, synthetic: bool = False, device: Optional[torch.device] = None) -> List[Dict]:
     """The body of inference.py (mode 'inference') / interactive_inference.py (mode 'interactive').  Returns one record per
-    written video: {"path", "idx", "frames", "seconds"}."""
+    written video: {"path", "idx", "frames", "seconds"}, and "input_frames" when the yaml's `input_video` gave a clip to continue."""
     from .pipeline import CausalInferencePipeline, InteractiveCausalInferencePipeline
     local_rank, rank, world = _dist_env()
     if device is None:
@@ -334,6 +397,8 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         device = torch.device("cuda", local_rank)
     torch.manual_seed(replica_seed(int(config.seed), local_rank))                 # set_seed(config.seed + local_rank)
     synthetic = synthetic or bool(config.get("synthetic", False))
+    shape = wan_config(config, synthetic)
+    clip = load_clip(config, shape.lat_h, shape.lat_w)         # read and checked before any model is built
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
     gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6, W4A6 or W4A4
     gen.model.set_attn_quant(attn_quant_mode(config.get("attn_quant", "none")))   # self-attention: bf16 or MXFP8
@@ -352,6 +417,11 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     # makedirs before the other ranks' first write (the reference has dist.barrier() there, inference.py:153-156)
     os.makedirs(config.output_folder, exist_ok=True)
     model_type = model_type_of(config, lora_enabled)
+    extra, more = {}, {}
+    if clip is not None:                            # every prompt continues the same clip: encoded once
+        latent = vae.encode_frames_to_latent(clip.unsqueeze(0).to(device))
+        more["initial_latent"] = latent.expand(config.num_samples, *latent.shape[1:])
+        extra["input_frames"] = int(clip.shape[0])
     records = []
     for i, idx in enumerate(rank_indices(len(dataset), rank, world)):
         item = dataset[idx]
@@ -361,12 +431,12 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         if interactive:
             prompts_list = [[p] * config.num_samples for p in item["prompts_list"]]
             video = pipeline.inference(noise=noise, text_prompts_list=prompts_list, switch_frame_indices=switch,
-                                       return_latents=False, profile=config.get("profile", False))
+                                       return_latents=False, profile=config.get("profile", False), **more)
             first_prompt = item["prompts_list"][0]
         else:
             prompt = item.get("extended_prompts") or item["prompts"]
             video, _ = pipeline.inference(noise=noise, text_prompts=[prompt] * config.num_samples, return_latents=True,
-                                          profile=config.get("profile", False))
+                                          profile=config.get("profile", False), **more)
             first_prompt = item["prompts"]
         torch.cuda.synchronize(device)
         dt = time.perf_counter() - t0
@@ -375,7 +445,7 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         for seed_idx in range(config.num_samples):
             name = output_name(rank, idx, seed_idx, model_type, config.save_with_index, first_prompt, interactive)
             path = write_video(os.path.join(config.output_folder, name), frames[seed_idx], fps=16)
-            records.append({"path": path, "idx": idx, "frames": int(frames.shape[1]), "seconds": dt})
+            records.append({"path": path, "idx": idx, "frames": int(frames.shape[1]), "seconds": dt, **extra})
         if config.inference_iter != -1 and i >= config.inference_iter:
             break
     return records

@@ -664,6 +664,49 @@ __global__ __launch_bounds__(256) void pixels_to_cl_kernel(const TI* __restrict_
   for (int q = 1; q < CPAD / 8; ++q) o[q] = z;
 }
 
+// Encoder input from video frames: uint8 [T, H, W, 3] (frame stride st in BYTES, rows and pixels contiguous) -> channels-last bf16
+// [T, H, W, CPAD], channels >= 3 zero, value bf16(float(u) / 127.5f - 1.0f): a correctly rounded divide, then a subtract, then one
+// rounding to bf16 (the Makefile's -ffp-contract=off keeps them apart), i.e. `(u.float() / 127.5 - 1).to(bfloat16)`.  Memory bound:
+// a lane owns `groups`-indexed runs of 4 pixels = 12 bytes of one frame, read as three dwords where the address is dword aligned
+// (12 g always is, so that is a property of the frame's base) and as bytes otherwise and on a frame's last, partial group; each
+// pixel leaves as CPAD / 8 16-byte stores.
+template <int CPAD>
+__global__ __launch_bounds__(256) void pixels_u8_to_cl_kernel(const uint8_t* __restrict__ px, bf16* __restrict__ out, long long st,
+                                                              long long hw, long long groups, long long total) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;      // group of 4 pixels
+  if (i >= total) return;
+  long long t = i / groups, p0 = (i - t * groups) * 4;
+  const int n = (int)(hw - p0 < 4 ? hw - p0 : 4);               // pixels of this group inside the frame
+  const uint8_t* s = px + t * st + p0 * 3;
+  uint32_t w[3] = {0u, 0u, 0u};
+  if (n == 4 && (reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+    w[0] = s4[0]; w[1] = s4[1]; w[2] = s4[2];
+  } else {
+#pragma unroll
+    for (int b = 0; b < 12; ++b)
+      if (b < 3 * n) w[b >> 2] |= (uint32_t)s[b] << (8 * (b & 3));
+  }
+  bf16x8 z;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) z[j] = (bf16)0.f;
+  bf16x8* o = reinterpret_cast<bf16x8*>(out + (t * hw + p0) * CPAD);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j >= n) break;
+    bf16x8 v = z;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int b = 3 * j + c;
+      const float u = (float)((w[b >> 2] >> (8 * (b & 3))) & 255u);
+      v[c] = (bf16)(u / 127.5f - 1.0f);
+    }
+    o[j * (CPAD / 8)] = v;
+#pragma unroll
+    for (int q = 1; q < CPAD / 8; ++q) o[j * (CPAD / 8) + q] = z;
+  }
+}
+
 // Latent scaling of WanVAE_.encode (vae.py:537-539) under bf16 + the layout change + .float() (utils/wan_wrapper.py:87):
 // channels-last mu [T, h, w, ld] (first C channels) -> fp32 [T, C, h, w] = float(bf16(bf16(mu - mean) * inv_std)).
 __global__ __launch_bounds__(256) void vae_scale_tchw_kernel(const bf16* __restrict__ mu, const bf16* __restrict__ mean,
@@ -1001,6 +1044,22 @@ extern "C" int ll_pixels_to_cl(const void* px, int is_f32, long long stride_c, l
   else { if (Cpad == 8) PX_LAUNCH(bf16, 8); else if (Cpad == 16) PX_LAUNCH(bf16, 16); else PX_LAUNCH(bf16, 32); }
 #undef PX_LAUNCH
   return ll_check_launch("ll_pixels_to_cl");
+}
+
+extern "C" int ll_pixels_u8_to_cl(const uint8_t* px, long long stride_t, ll_bf16* out, int T, int H, int W, int Cpad, ll_stream stream) {
+  LL_REQUIRE(px != nullptr && out != nullptr, "ll_pixels_u8_to_cl: null operand");
+  LL_REQUIRE(Cpad == 8 || Cpad == 16 || Cpad == 32, "ll_pixels_u8_to_cl: Cpad=%d must be 8, 16 or 32", Cpad);
+  LL_REQUIRE(T > 0 && H > 0 && W > 0, "ll_pixels_u8_to_cl: empty input %d x %d x %d", T, H, W);
+  const long long hw = (long long)H * W, groups = (hw + 3) / 4, total = groups * T;
+  LL_REQUIRE(stride_t >= 3 * hw, "ll_pixels_u8_to_cl: stride_t=%lld bytes must span a %d x %d x 3 frame", stride_t, H, W);
+  LL_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "ll_pixels_u8_to_cl: out must be 16-byte aligned");
+  LL_REQUIRE((total + 255) / 256 <= 0x7fffffffll, "ll_pixels_u8_to_cl: %d x %d x %d is more than one launch covers", T, H, W);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define PX_LAUNCH(CP) hipLaunchKernelGGL((pixels_u8_to_cl_kernel<CP>), grid, block, 0, s, px, (bf16*)out, stride_t, hw, groups, total)
+  if (Cpad == 8) PX_LAUNCH(8); else if (Cpad == 16) PX_LAUNCH(16); else PX_LAUNCH(32);
+#undef PX_LAUNCH
+  return ll_check_launch("ll_pixels_u8_to_cl");
 }
 
 extern "C" int ll_vae_scale_tchw(const ll_bf16* mu, const ll_bf16* mean, const ll_bf16* inv_std, float* out, int T, int z_dim, int h,

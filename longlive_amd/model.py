@@ -166,6 +166,8 @@ def _kv_commit(cache: dict, G: int, E: int) -> None:
 class CausalWanModelHIP(nn.Module):
     """Drop-in for the KV-cache inference branch of CausalWanModel."""
 
+    rope_frames = 1024      # rows of the frame-axis RoPE table (model.py:29-36): the longest timeline, in latent frames
+
     def __init__(self, cfg: WanConfig, device="cuda", dtype=bf16):
         super().__init__()
         assert dtype == bf16, "the HIP path computes in bf16 (inference.py:134)"
@@ -343,7 +345,7 @@ class CausalWanModelHIP(nn.Module):
                                1.0 / torch.pow(10000.0, torch.arange(0, dim, 2, dtype=torch.float64).div(dim)))
 
         if self._rope_f is None:
-            a = angles(1024, d - 4 * (d // 6))
+            a = angles(self.rope_frames, d - 4 * (d // 6))
             assert a.shape[1] == nf
             self._rope_f = torch.stack([a.cos(), a.sin()], -1).float().contiguous().to(device)
         key = (hp, wp)

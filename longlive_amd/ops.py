@@ -787,6 +787,27 @@ def pixels_to_cl(px, channel_dim: int, cpad: int = 8, out=None):
     return out
 
 
+def pixels_u8_to_cl(frames, cpad: int = 8, out=None):
+    """Video frames uint8 [T, H, W, 3] (any view whose frames are contiguous) -> channels-last bf16 [T, H, W, cpad], channels >= 3
+    zero, values `(u.float() / 127.5 - 1).to(bfloat16)` bit for bit."""
+    if not frames.is_cuda:
+        raise RuntimeError("frames: expected a device tensor (longlive_amd has no CPU path)")
+    if frames.dtype != torch.uint8:
+        raise RuntimeError(f"frames: expected uint8, got {frames.dtype}")
+    assert frames.dim() == 4 and frames.shape[3] == 3, f"frames: {tuple(frames.shape)} is not [T, H, W, 3]"
+    T, H, W, _ = frames.shape
+    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W or (T > 1 and frames.stride(0) < 3 * H * W):
+        frames = frames.contiguous()
+    if out is None:
+        out = torch.empty(T, H, W, cpad, dtype=bf16, device=frames.device)
+    _chk(out, "out")
+    assert out.shape == (T, H, W, cpad)
+    lib = _lib.load()
+    stride_t = frames.stride(0) if T > 1 else 3 * H * W          # uint8: elements are bytes
+    _lib.check(lib.ll_pixels_u8_to_cl(frames.data_ptr(), stride_t, out.data_ptr(), T, H, W, cpad, _stream()), "ll_pixels_u8_to_cl")
+    return out
+
+
 def vae_scale_tchw(mu, mean, inv_std):
     """Channels-last mu [T, h, w, ld] (first z channels) -> fp32 [T, z, h, w] = float(bf16(bf16(mu - mean) * inv_std))."""
     _chk(mu, "mu"); _chk(mean, "mean"); _chk(inv_std, "inv_std")

@@ -167,18 +167,91 @@ class CausalInferencePipeline(nn.Module):
         self.generator.model.local_attn_size = self.local_attn_size
         self._set_all_modules_max_attention_size(self.local_attn_size)
 
+    # ---- continuing a clip ("Continuing a clip") -----------------------------------------------------
+    ROPE_FRAMES = 1024      # fallback for generators that do not state their frame-axis RoPE table's length (model.rope_frames)
+
+    def _check_prefix(self, noise: torch.Tensor, initial_latent) -> Optional[torch.Tensor]:
+        """Validate `initial_latent` [B, n, 16, h, w] against `noise` [B, T, 16, h, w] BEFORE any launch and return it cast once to
+        noise.dtype (None stays None: today's path).  The cast values are what is stored, prefilled and returned."""
+        if initial_latent is None:
+            return None
+        if not torch.is_tensor(initial_latent) or initial_latent.dim() != 5:
+            raise ValueError(f"initial_latent: expected a tensor [B, n, 16, h, w], got "
+                             f"{tuple(initial_latent.shape) if torch.is_tensor(initial_latent) else type(initial_latent).__name__}")
+        n, T = int(initial_latent.shape[1]), int(noise.shape[1])
+        if n < 1:
+            raise ValueError("initial_latent: holds no frame (n = 0); pass None to start a new clip")
+        if initial_latent.shape[0] != noise.shape[0] or tuple(initial_latent.shape[2:]) != tuple(noise.shape[2:]):
+            raise ValueError(f"initial_latent: {tuple(initial_latent.shape)} does not share batch / channels / height / width with "
+                             f"noise {tuple(noise.shape)}")
+        if initial_latent.device != noise.device:
+            raise ValueError(f"initial_latent: on {initial_latent.device}, noise on {noise.device}")
+        rope = int(getattr(self.generator.model, "rope_frames", self.ROPE_FRAMES))      # the kernel refuses frames beyond its table
+        if n + T > rope:
+            raise ValueError(f"initial_latent: {n} given + {T} new frames = {n + T} exceed the {rope}-frame RoPE table")
+        return initial_latent.to(noise.dtype)
+
+    def _prefix_blocks(self, n: int):
+        """(start, frames) of the prefill blocks of an n-frame prefix: a short block leads (the encoder gives 1 + k latents for
+        1 + 4k frames; the reference's roll-out assumes 1 + nf * k), whole blocks follow."""
+        nf = self.num_frame_per_block
+        sizes = ([n % nf] if n % nf else []) + [nf] * (n // nf)
+        out, start = [], 0
+        for f in sizes:
+            out.append((start, f))
+            start += f
+        return out
+
+    def _prefill(self, prefix: torch.Tensor, cond):
+        """Yield (start, block) for every prefix block after its clean-context pass -- the one thing a generated block leaves in
+        the caches -- has been queued.  Passes in a row on the aux stream are ordered by that stream.  The main stream JOINS the aux
+        stream behind the last one: the first pass of a run also fills the cross-attention K/V of every layer but the last, and it
+        does so AFTER recording that layer's event (the event marks the last access to the self-attention cache), so the per-layer
+        events alone would let the first denoising forward read text K/V that are still being written.  Generated blocks never meet
+        this: their cross-attention caches were filled by a denoising forward on the main stream."""
+        for start, f in self._prefix_blocks(prefix.shape[1]):
+            block = prefix[:, start:start + f]
+            self._clean_context_pass(block, cond, start)
+            yield start, block
+        self._join_context()
+
+    def _prefill_profiled(self, prefix, cond, noise, prof):
+        """inference()'s prefill: the "prefill" phase of last_profile, the prefix blocks also handed to the side decoder (returned;
+        None without a prefix: nothing is created, queued or timed).  `_prefill` ends with the main stream joined to the aux
+        stream, so the phase's closing event sees the passes and the time is their own, profiled or not."""
+        if prefix is None:
+            return None
+        prof.start("prefill")
+        side = self._side_decoder(noise)
+        for _, block in self._prefill(prefix, cond):
+            if side is not None:
+                side.push(block)
+        prof.stop("prefill")
+        return side
+
     # ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def stream(self, noise: torch.Tensor, text_prompts, output: Optional[torch.Tensor] = None):
+    def stream(self, noise: torch.Tensor, text_prompts, output: Optional[torch.Tensor] = None,
+               initial_latent: Optional[torch.Tensor] = None):
         """Generator form of `inference`: yields (start_frame, denoised_latents[B, F, 16, h, w]) after every
-        autoregressive block, so frames can be consumed (decoded / displayed / timed) while generation goes on."""
-        batch_size, num_output_frames = noise.shape[:2]
-        assert num_output_frames % self.num_frame_per_block == 0
+        autoregressive block, so frames can be consumed (decoded / displayed / timed) while generation goes on.
+        initial_latent [B, n, 16, h, w]: the clip to continue.  Its blocks are yielded first, like any other block, and the new
+        blocks follow at starts n, n + nf, ...; `output`, when given, holds n + T frames."""
+        prefix = self._check_prefix(noise, initial_latent)
+        n = 0 if prefix is None else prefix.shape[1]
+        batch_size, num_new_frames = noise.shape[:2]
+        assert num_new_frames % self.num_frame_per_block == 0
         cond = self._encode(text_prompts)
-        self._setup(noise, num_output_frames)
+        self._setup(noise, n + num_new_frames)
         nf = self.num_frame_per_block
-        for start in range(0, num_output_frames, nf):
-            denoised = self._denoise_block(noise[:, start:start + nf], cond, start, batch_size, nf)
+        if prefix is not None:
+            if output is not None:
+                output[:, :n] = prefix
+            for start, block in self._prefill(prefix, cond):
+                yield start, block
+        for off in range(0, num_new_frames, nf):
+            start = n + off
+            denoised = self._denoise_block(noise[:, off:off + nf], cond, start, batch_size, nf)
             if output is not None:
                 output[:, start:start + nf] = denoised
             self._clean_context_pass(denoised, cond, start)
@@ -187,10 +260,12 @@ class CausalInferencePipeline(nn.Module):
 
     @torch.no_grad()
     def stream_video(self, noise: torch.Tensor, text_prompts, output: Optional[torch.Tensor] = None,
-                     overlap_decode: bool = False):
+                     overlap_decode: bool = False, initial_latent: Optional[torch.Tensor] = None):
         """Live form of `inference`: yields (start_frame, pixels[B, T', 3, H, W] in [0, 1]) after every block, decoding
         each block with the VAE's streaming cache (WanVAE_.cached_decode, wan/modules/vae.py:571-593) -- the first block
         gives 1 + 4 (F - 1) frames, later ones 4 F.  The concatenation equals `inference(...)`'s video bit for bit.
+        initial_latent: the clip to continue (`stream`); its blocks are decoded and yielded first, so the decoder's streaming cache is
+        warm when the first new block arrives.
 
         overlap_decode: block i is decoded on a second HIP stream while block i + 1 is generated on the caller's stream (the
         decoder's staging-bound convolutions run beside the power-bound DiT kernels); block i's pixels are then yielded after
@@ -202,7 +277,7 @@ class CausalInferencePipeline(nn.Module):
         pending = None                                   # (start, pixels, event) of the block being decoded on the side stream
         side = None
         try:
-            for start, latents in self.stream(noise, text_prompts, output=output):
+            for start, latents in self.stream(noise, text_prompts, output=output, initial_latent=initial_latent):
                 if not (overlap_decode and latents.is_cuda):
                     video = self.vae.decode_to_pixel(latents, use_cache=True)
                     yield start, (video * 0.5 + 0.5).clamp(0, 1)
@@ -236,26 +311,33 @@ class CausalInferencePipeline(nn.Module):
 
     @torch.no_grad()
     def inference(self, noise: torch.Tensor, text_prompts: List[str], return_latents: bool = False,
-                  profile: bool = False, low_memory: bool = False):
+                  profile: bool = False, low_memory: bool = False, initial_latent: Optional[torch.Tensor] = None):
         """noise [B, T, 16, H/8, W/8] -> video [B, T', 3, H, W] in [0,1] (None without a VAE) and, with
-        return_latents, the denoised latents [B, T, 16, H/8, W/8]."""
-        batch_size, num_output_frames = noise.shape[:2]
-        assert num_output_frames % self.num_frame_per_block == 0
-        num_blocks = num_output_frames // self.num_frame_per_block
+        return_latents, the denoised latents [B, T, 16, H/8, W/8].
+        initial_latent [B, n, 16, H/8, W/8]: the clip to continue.  `noise` then holds only the T NEW frames; the latents and the
+        video cover all n + T frames (1 + 4 (n + T - 1) pixel frames), `[:, :n]` being the prefix itself."""
+        prefix = self._check_prefix(noise, initial_latent)
+        n = 0 if prefix is None else prefix.shape[1]
+        batch_size, num_new_frames = noise.shape[:2]
+        assert num_new_frames % self.num_frame_per_block == 0
+        num_blocks = num_new_frames // self.num_frame_per_block
         cond = self._encode(text_prompts)
-        output = torch.zeros_like(noise)      # low_memory (CPU staging) is pointless with 288 GB of HBM: ignored
+        # low_memory (CPU staging) is pointless with 288 GB of HBM: ignored
+        output = torch.zeros_like(noise) if prefix is None else _timeline(noise, prefix)
 
         prof = _Profiler(profile)
         prof.start("init")
-        self._setup(noise, num_output_frames)
+        self._setup(noise, n + num_new_frames)
         prof.stop("init")
+        side = self._prefill_profiled(prefix, cond, noise, prof)
         prof.start("diffusion")
-        start = 0
-        side = self._side_decoder(noise)
+        start = n
+        if prefix is None:
+            side = self._side_decoder(noise)
         for _ in range(num_blocks):
             nf = self.num_frame_per_block
             prof.block_start()
-            denoised = self._denoise_block(noise[:, start:start + nf], cond, start, batch_size, nf)
+            denoised = self._denoise_block(noise[:, start - n:start - n + nf], cond, start, batch_size, nf)
             output[:, start:start + nf] = denoised
             self._clean_context_pass(denoised, cond, start)
             if side is not None:
@@ -304,6 +386,14 @@ class CausalInferencePipeline(nn.Module):
         for _, module in model.named_modules():
             if hasattr(module, "max_attention_size"):
                 module.max_attention_size = target
+
+
+def _timeline(noise: torch.Tensor, prefix: torch.Tensor) -> torch.Tensor:
+    """The latents of a continued clip: [B, n + T, ...] like `noise`, the prefix in front, the new frames still zero."""
+    n = prefix.shape[1]
+    out = noise.new_zeros([noise.shape[0], n + noise.shape[1], *noise.shape[2:]])
+    out[:, :n] = prefix
+    return out
 
 
 def _mk(args, name, default):

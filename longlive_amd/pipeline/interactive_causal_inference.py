@@ -2,11 +2,11 @@
 pipeline/interactive_causal_inference.py::InteractiveCausalInferencePipeline (:20-432)."""
 from __future__ import annotations
 
-from typing import List
+from typing import List, Optional
 
 import torch
 
-from .causal_inference import CausalInferencePipeline, _Profiler
+from .causal_inference import CausalInferencePipeline, _Profiler, _timeline
 
 
 class InteractiveCausalInferencePipeline(CausalInferencePipeline):
@@ -48,8 +48,14 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
 
     @torch.no_grad()
     def inference(self, noise: torch.Tensor, *, text_prompts_list: List[List[str]], switch_frame_indices: List[int],
-                  return_latents: bool = False, low_memory: bool = False, profile: bool = False):
-        """Switch to prompt segment i+1 at the first block whose start frame >= switch_frame_indices[i] (:237)."""
+                  return_latents: bool = False, low_memory: bool = False, profile: bool = False,
+                  initial_latent: Optional[torch.Tensor] = None):
+        """Switch to prompt segment i+1 at the first block whose start frame >= switch_frame_indices[i] (:237).
+        initial_latent [B, n, 16, h, w]: the clip to continue (CausalInferencePipeline.inference), prefilled under
+        text_prompts_list[0].  Frame numbers -- the switch indices too -- count on the n + T timeline and only GENERATED blocks
+        switch: an index <= n switches at the first generated block, whose recache then re-encodes prefix frames under the new prompt."""
+        prefix = self._check_prefix(noise, initial_latent)
+        n = 0 if prefix is None else prefix.shape[1]
         batch_size, num_output_frames = noise.shape[:2]
         assert len(text_prompts_list) >= 1, "text_prompts_list must not be empty"
         assert len(switch_frame_indices) == len(text_prompts_list) - 1, (
@@ -57,16 +63,18 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
         assert num_output_frames % self.num_frame_per_block == 0
         num_blocks = num_output_frames // self.num_frame_per_block
         cond_list = [self._encode(p) for p in text_prompts_list]
-        output = torch.zeros_like(noise)
+        output = torch.zeros_like(noise) if prefix is None else _timeline(noise, prefix)
 
         prof = _Profiler(profile)
         prof.start("init")
-        self._setup(noise, num_output_frames)
+        self._setup(noise, n + num_output_frames)
         prof.stop("init")
+        side = self._prefill_profiled(prefix, cond_list[0], noise, prof)
         prof.start("diffusion")
-        seg, start, switch_blocks = 0, 0, []
+        seg, start, switch_blocks = 0, n, []
         next_switch = switch_frame_indices[0] if switch_frame_indices else None
-        side = self._side_decoder(noise)
+        if prefix is None:
+            side = self._side_decoder(noise)
         for blk in range(num_blocks):
             nf = self.num_frame_per_block
             prof.block_start()
@@ -76,7 +84,7 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
                 switch_blocks.append(blk)
                 next_switch = switch_frame_indices[seg] if seg < len(switch_frame_indices) else None
             cond = cond_list[seg]
-            denoised = self._denoise_block(noise[:, start:start + nf], cond, start, batch_size, nf)
+            denoised = self._denoise_block(noise[:, start - n:start - n + nf], cond, start, batch_size, nf)
             output[:, start:start + nf] = denoised
             self._clean_context_pass(denoised, cond, start)
             if side is not None:

@@ -355,8 +355,12 @@ class WanVAEEncoderHIP(_VaeHalfHIP):
 
     def _encoder_step(self, px, channel_dim: int):   # Encoder3d.forward (vae.py:318-366) + conv1's mu rows
         c1 = self._convs["encoder.conv1"]
-        T, H, W = px.shape[1 - channel_dim], px.shape[2], px.shape[3]
-        x = ops.pixels_to_cl(px, channel_dim, self.cpad, out=c1.input(T, H, W, px.device))
+        if px.dtype == torch.uint8:                 # video frames [T, H, W, 3]: normalised, rounded and laid out by one kernel
+            T, H, W = px.shape[:3]
+            x = ops.pixels_u8_to_cl(px, self.cpad, out=c1.input(T, H, W, px.device))
+        else:
+            T, H, W = px.shape[1 - channel_dim], px.shape[2], px.shape[3]
+            x = ops.pixels_to_cl(px, channel_dim, self.cpad, out=c1.input(T, H, W, px.device))
         nxt = self._consumer(-1)
         if nxt is None:
             x = c1(x)
@@ -383,14 +387,17 @@ class WanVAEEncoderHIP(_VaeHalfHIP):
     def encode(self, x: torch.Tensor, keep_cache: bool = False, channel_dim: int = 0) -> torch.Tensor:
         """x [3, T, H, W] (or [T, 3, H, W] with channel_dim = 1), fp32 or bf16 pixels in [-1, 1] of one video -> fp32 [T', 16, H/8, W/8]
         scaled latent means; T' = 1 + (T - 1) // 4 on a fresh cache (frames beyond 1 + 4k are dropped, vae.py:521), T // 4 when
-        keep_cache continues a stream (the mirror of the decoder's streaming decode; the reference has no such flag)."""
+        keep_cache continues a stream (the mirror of the decoder's streaming decode; the reference has no such flag).
+        A uint8 x is video frames [T, H, W, 3] (channel_dim is not read): the same latents as (x.float() / 127.5 - 1) laid out [3, T, H, W]."""
         if not x.is_cuda:
             raise RuntimeError("WanVAEEncoderHIP.encode: expected a device tensor (longlive_amd has no CPU path)")
+        if x.dtype == torch.uint8 and (x.dim() != 4 or x.shape[3] != 3):
+            raise RuntimeError(f"WanVAEEncoderHIP.encode: uint8 input must be frames [T, H, W, 3], got {tuple(x.shape)}")
         if not self._packed:
             self._pack()
         if not keep_cache:
             self.clear_cache()
-        tdim = 1 - channel_dim
+        tdim = 0 if x.dtype == torch.uint8 else 1 - channel_dim
         T = x.shape[tdim]
         outs: List[torch.Tensor] = []
         i = 0
@@ -468,3 +475,15 @@ class WanVAEWrapper(nn.Module):
             assert pixel.shape[0] == 1, "Batch size must be 1 when using cache"
         enc = self._get_encoder()
         return torch.stack([enc.encode(u, keep_cache=keep_cache) for u in pixel], 0)
+
+    def encode_frames_to_latent(self, frames: torch.Tensor, keep_cache: bool = False) -> torch.Tensor:
+        """Video frames uint8 [B, T, H, W, 3] -> fp32 [B, 1 + (T - 1) // 4, 16, H/8, W/8]: bit for bit
+        encode_to_latent((frames.float() / 127.5 - 1).permute(0, 4, 1, 2, 3)), without the fp32 planes ever existing."""
+        if frames.dim() != 5 or frames.shape[4] != 3 or frames.dtype != torch.uint8:
+            raise RuntimeError(f"encode_frames_to_latent: expected uint8 frames [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
+        if not frames.is_cuda:
+            raise RuntimeError("encode_frames_to_latent: expected a device tensor (longlive_amd has no CPU path)")
+        if keep_cache:
+            assert frames.shape[0] == 1, "Batch size must be 1 when using cache"
+        enc = self._get_encoder()
+        return torch.stack([enc.encode(u, keep_cache=keep_cache) for u in frames], 0)
