@@ -54,7 +54,8 @@ enum ll_epilogue {
  * add entry points, so they keep 111; so does ll_conv_plan, and so do the VAE encoder's entry points (ll_conv_cl_down, ll_conv_cl_tdown,
  * ll_conv_down_plan, ll_pixels_to_cl, ll_vae_scale_tchw), and so do the attention entry points with quantised output
  * (ll_flash_attn_q_ok, ll_flash_attn_q, ll_flash_attn_q_plan, ll_flash_attn_mx_q), and so does the uint8 video intake
- * (ll_pixels_u8_to_cl): 111 covers them too. */
+ * (ll_pixels_u8_to_cl), and so do the frames-out entry points (ll_cl_to_frames_u8, ll_jpeg_sizes, ll_jpeg_encode_u8,
+ * ll_jpeg_coefficients_u8): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -517,6 +518,35 @@ int ll_vae_unscale_cl(const ll_bf16* z, const ll_bf16* mean, const ll_bf16* inv_
 /* Decoder output: channels-last bf16 [T,H,W,ldc] (first 3 channels) -> fp32 [T,3,H,W] clamped to [-1,1]
  * (wan/modules/vae.py decode's clamp_ + utils/wan_wrapper.py:112-116). */
 int ll_cl_to_tchw_clamp(const ll_bf16* x, float* out, int T, int H, int W, int ldc, ll_stream stream);
+
+/* -- frames out ("Frames out") -- */
+
+/* Decoder output as video frames: channels-last bf16 x [T,H,W,ldc] (first 3 channels, ldc >= 3) -> uint8 out [T,H,W,3] (rows and
+ * pixels contiguous, stride_t in BYTES >= H*W*3, any alignment).  Each byte, in fp32 with no FMA contraction:
+ *   trunc(255.0f * clamp(clamp((float)x, -1, 1) * 0.5f + 0.5f, 0, 1)),  NaN -> 0 (a signalling bit pattern -> 255, as below),
+ * i.e. ll_cl_to_tchw_clamp, then the pipelines' `(video * 0.5 + 0.5).clamp(0, 1)` (stream_video, inference, the side decoder), then
+ * the CLI's `(255.0 * video.permute(0, 1, 3, 4, 2)).to(torch.uint8)`, bit for bit, without the three fp32 passes.  Bytes of out
+ * outside the T frames of H*W*3 bytes are never written. */
+int ll_cl_to_frames_u8(const ll_bf16* x, uint8_t* out, long long stride_t, int T, int H, int W, int ldc, ll_stream stream);
+
+/* Baseline JPEG (JFIF, SOF0, 8 bits, 4:2:0, Annex K Huffman tables, Annex K quantisation tables scaled by the IJG rule for quality
+ * 1..100, restart interval = one row of 16 x 16 MCUs, RSTm cycling 0..7, edge replication into the padding), one complete file
+ * SOI ... EOI per frame.  Replaces the uncompressed write_avi_rgb24 fallback of the CLI's write_video; arithmetic in csrc/jpeg.hip's
+ * head comment, restated in tests/jpeg_ref.py.
+ *
+ * ll_jpeg_sizes (host only): *out_stride = the worst case of one frame = 613 header bytes + MCUs * 6 * 416 (208 bytes per block,
+ * doubled by FF 00 stuffing) + 2 per restart marker + 2 for EOI, rounded up to 16; *scratch_bytes = what ll_jpeg_encode_u8 needs
+ * for T frames.  H, W <= 65535; a frame whose worst case passes 2 GiB is refused. */
+int ll_jpeg_sizes(int T, int H, int W, long long* out_stride, long long* scratch_bytes);
+/* frames uint8 [T,H,W,3] RGB (stride_t in BYTES >= H*W*3) -> out + t * out_stride holds frame t's file, sizes[t] its length in bytes
+ * (device int32 [T]); bytes of out past sizes[t] are left alone.  No allocation, no synchronisation; scratch (16-byte aligned,
+ * scratch_bytes >= ll_jpeg_sizes') may hold anything: no stage accumulates in place.  Refused before any launch: null operands,
+ * quality outside 1..100, T, H, W < 1, H or W > 65535, short stride_t / out_stride / scratch_bytes. */
+int ll_jpeg_encode_u8(const uint8_t* frames, long long stride_t, int T, int H, int W, int quality, uint8_t* out, long long out_stride,
+                      int32_t* sizes, void* scratch, long long scratch_bytes, ll_stream stream);
+/* The first stage alone: colour conversion, 8 x 8 DCT and quantisation -> coef int16 [T, ceil(H/16), ceil(W/16), 6, 64], blocks
+ * Y00 Y01 Y10 Y11 Cb Cr of every MCU, each in zigzag order (what the tests pin the arithmetic with). */
+int ll_jpeg_coefficients_u8(const uint8_t* frames, long long stride_t, int T, int H, int W, int quality, int16_t* coef, ll_stream stream);
 
 /* -- encoder (Encoder3d + conv1, wan/modules/vae.py:265-366, 517-543): every stride-1 convolution runs on ll_conv_cl; the two
  * strided gathers below are further gather modes of the same implicit GEMM (same LDS staging, swizzle and epilogue). -- */

@@ -66,6 +66,10 @@ SIGNATURES = {
     "ll_softmax_rows": [_p, _p, _i, _i, _i, _f, _p],
     "ll_vae_unscale_cl": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ll_cl_to_tchw_clamp": [_p, _p, _i, _i, _i, _i, _p],
+    "ll_cl_to_frames_u8": [_p, _p, _ll, _i, _i, _i, _i, _p],
+    "ll_jpeg_sizes": [_i, _i, _i, C.POINTER(_ll), C.POINTER(_ll)],
+    "ll_jpeg_encode_u8": [_p, _ll, _i, _i, _i, _i, _p, _ll, _p, _p, _ll, _p],
+    "ll_jpeg_coefficients_u8": [_p, _ll, _i, _i, _i, _i, _p, _p],
     "ll_conv_cl_down": [_p] * 5 + [_i] * 7 + [_p],
     "ll_conv_cl_tdown": [_p] * 5 + [_i] * 7 + [_p],
     "ll_conv_down_plan": [_i] * 6 + [C.c_char_p, _i],

@@ -14,6 +14,8 @@ Extra key, because this repository cannot ship checkpoints: `synthetic: true` (o
 
 Extra keys, both modes: `input_video: <path>` continues a clip -- every prompt of the data file continues the same one -- and
 `input_frames: <int>` caps how many of its frames are used (the LAST 1 + 4k frames that fit).
+`video_codec: mjpeg` writes `<name>.avi` as Motion JPEG, encoded on the GPU at `jpeg_quality: 90` ("Frames
+out"); without the key the video is written as before.  An MJPEG .avi is also read back as `input_video` (through PIL).
 """
 from __future__ import annotations
 
@@ -199,6 +201,112 @@ def read_avi_rgb24(path: str) -> torch.Tensor:
     return torch.stack(frames, 0)
 
 
+AVI_LIMIT = (1 << 32) - 8                           # riff_len: the whole file, RIFF header included, stays within 4 GiB
+
+
+def _avi_mjpeg_layout(sizes: Sequence[int], hdrl_len: int):
+    """(movi_len, idx_len, riff_len) of an MJPEG AVI with these frame sizes: every frame is '00dc' + length + data padded to even."""
+    movi_len = 4 + sum(8 + n + (n & 1) for n in sizes)
+    idx_len = 16 * len(sizes)
+    return movi_len, idx_len, 4 + hdrl_len + 8 + movi_len + 8 + idx_len
+
+
+def write_avi_mjpeg(path: str, frames: Sequence[bytes], width: int, height: int, fps: int = 16) -> int:
+    """Motion-JPEG AVI: one 'vids' stream (fccHandler and biCompression 'MJPG') of '00dc' chunks, each one complete JPEG file padded to
+    even length, + idx1 with the true sizes.  Frames are written as they come; all lengths are known from the frames' sizes up front,
+    and a file that would pass 4 GiB is refused before anything is written.  Returns the file's size in bytes."""
+    sizes = [len(f) for f in frames]
+    T = len(sizes)
+    if T < 1:
+        raise ValueError("write_avi_mjpeg: no frames")
+    biggest = max(sizes)
+    avih = struct.pack("<IIIIIIIIII4I", 1000000 // fps, biggest * fps, 0, 0x10, T, 0, 1, biggest, width, height, 0, 0, 0, 0)
+    strh = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", b"MJPG", 0, 0, 0, 0, 1, fps, 0, T, biggest, 0xFFFFFFFF, 0, 0, 0, width, height)
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+
+    def chunk(tag, payload):
+        return tag + struct.pack("<I", len(payload)) + payload + (b"\x00" if len(payload) & 1 else b"")
+
+    def lst(tag, payload):
+        return b"LIST" + struct.pack("<I", len(payload) + 4) + tag + payload
+
+    hdrl = lst(b"hdrl", chunk(b"avih", avih) + lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
+    movi_len, idx_len, riff_len = _avi_mjpeg_layout(sizes, len(hdrl))
+    if riff_len > AVI_LIMIT:
+        fit = T
+        while fit > 0 and _avi_mjpeg_layout(sizes[:fit], len(hdrl))[2] > AVI_LIMIT:
+            fit -= 1
+        raise ValueError(f"write_avi_mjpeg: {T} frames make a {riff_len + 8}-byte file, past the 4 GiB an AVI can hold; "
+                         f"the first {fit} frames fit")
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", riff_len) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", movi_len) + b"movi")
+        for data in frames:
+            f.write(b"00dc" + struct.pack("<I", len(data)))
+            f.write(data)
+            if len(data) & 1:
+                f.write(b"\x00")
+        f.write(b"idx1" + struct.pack("<I", idx_len))
+        off = 4
+        for n in sizes:
+            f.write(b"00dc" + struct.pack("<III", 0x10, off, n))
+            off += 8 + n + (n & 1)
+    return riff_len + 8
+
+
+def avi_compression(path: str) -> bytes:
+    """biCompression of the first stream's `strf` chunk as four bytes (b"\\0\\0\\0\\0" = uncompressed RGB)."""
+    with open(path, "rb") as f:
+        head = f.read(4096)
+    if head[:4] != b"RIFF" or head[8:12] != b"AVI " or b"strf" not in head:
+        raise ValueError(f"{path!r} is not an AVI file")
+    p = head.index(b"strf") + 8
+    return head[p + 16:p + 20]
+
+
+def read_avi_mjpeg(path: str) -> torch.Tensor:
+    """uint8 [T, H, W, 3] RGB frames of a Motion-JPEG AVI (write_avi_mjpeg), each decoded by PIL."""
+    try:
+        from PIL import Image                       # noqa: WPS433 (optional dependency)
+    except ImportError:
+        raise RuntimeError(f"input_video: reading the MJPEG file {path!r} needs PIL (Pillow) to decode its frames; without it the "
+                           f"formats read are an uncompressed RGB24 .avi and a .pt holding a uint8 [T, H, W, 3] tensor") from None
+    import io
+    import numpy as np
+    raw = open(path, "rb").read()
+    assert raw[:4] == b"RIFF" and raw[8:12] == b"AVI "
+    frames, q = [], raw.index(b"movi") + 4
+    while raw[q:q + 4] == b"00dc":
+        n = struct.unpack("<I", raw[q + 4:q + 8])[0]
+        img = Image.open(io.BytesIO(raw[q + 8:q + 8 + n]))
+        frames.append(torch.from_numpy(np.array(img.convert("RGB"), dtype=np.uint8)))
+        q += 8 + n + (n & 1)
+    if not frames:
+        raise ValueError(f"input_video: {path!r} holds no '00dc' frame")
+    return torch.stack(frames, 0)
+
+
+VIDEO_CODECS = ("mjpeg",)
+
+
+def video_codec(value) -> Optional[str]:
+    """The yaml's `video_codec:` key: absent / none = write_video's path, `mjpeg` = Motion JPEG in an .avi from the GPU encoder."""
+    if value is None or str(value).strip().lower() == "none":
+        return None
+    v = str(value).strip().lower()
+    if v not in VIDEO_CODECS:
+        raise ValueError(f"video_codec: {value!r} is not one of {', '.join(VIDEO_CODECS)} (or absent)")
+    return v
+
+
+def jpeg_quality(value) -> int:
+    """The yaml's `jpeg_quality:` key (1..100, default 90)."""
+    if value is None:
+        return 90
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= 100:
+        raise ValueError(f"jpeg_quality: {value!r} must be an integer 1..100")
+    return int(value)
+
+
 def write_video(path: str, frames: torch.Tensor, fps: int = 16) -> str:
     """torchvision.io.write_video(path, uint8 [T,H,W,C], fps) (inference.py:243) when torchvision + PyAV exist; otherwise
     the same frames as an uncompressed .avi next to the requested name.  Returns the path written."""
@@ -229,11 +337,11 @@ def select_clip_frames(total: int, cap: Optional[int] = None) -> slice:
 
 
 def read_input_video(path: str) -> torch.Tensor:
-    """uint8 [T, H, W, 3] RGB frames of `path`: an .avi as write_avi_rgb24 writes it, a .pt holding such a tensor, anything else
-    through torchvision.io.read_video when torchvision + PyAV exist."""
+    """uint8 [T, H, W, 3] RGB frames of `path`: an .avi as write_avi_rgb24 or write_avi_mjpeg writes it (chosen by the `strf` chunk's
+    biCompression), a .pt holding such a tensor, anything else through torchvision.io.read_video when torchvision + PyAV exist."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".avi":
-        frames = read_avi_rgb24(path)
+        frames = read_avi_mjpeg(path) if avi_compression(path) == b"MJPG" else read_avi_rgb24(path)
     elif ext == ".pt":
         frames = torch.load(path, map_location="cpu", weights_only=True)      # a bare tensor: nothing is unpickled
     else:
@@ -389,7 +497,8 @@ def _dist_env():
 
 def run(mode: str, config, synthetic: bool = False, device: Optional[torch.device] = None) -> List[Dict]:
     """The body of inference.py (mode 'inference') / interactive_inference.py (mode 'interactive').  Returns one record per
-    written video: {"path", "idx", "frames", "seconds"}, and "input_frames" when the yaml's `input_video` gave a clip to continue."""
+    written video: {"path", "idx", "frames", "seconds"}, "input_frames" when the yaml's `input_video` gave a clip to continue, and
+    "codec" and "bytes" when `video_codec` chose one."""
     from .pipeline import CausalInferencePipeline, InteractiveCausalInferencePipeline
     local_rank, rank, world = _dist_env()
     if device is None:
@@ -398,6 +507,8 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     torch.manual_seed(replica_seed(int(config.seed), local_rank))                 # set_seed(config.seed + local_rank)
     synthetic = synthetic or bool(config.get("synthetic", False))
     shape = wan_config(config, synthetic)
+    codec = video_codec(config.get("video_codec"))             # names and ranges are refused before any model is built
+    quality = jpeg_quality(config.get("jpeg_quality"))
     clip = load_clip(config, shape.lat_h, shape.lat_w)         # read and checked before any model is built
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
     gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6, W4A6 or W4A4
@@ -422,6 +533,8 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         latent = vae.encode_frames_to_latent(clip.unsqueeze(0).to(device))
         more["initial_latent"] = latent.expand(config.num_samples, *latent.shape[1:])
         extra["input_frames"] = int(clip.shape[0])
+    if codec is not None:                           # the pipeline hands back uint8 frames: no fp32 planes, no torch conversion
+        more["frames"] = "uint8"
     records = []
     for i, idx in enumerate(rank_indices(len(dataset), rank, world)):
         item = dataset[idx]
@@ -440,12 +553,20 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
             first_prompt = item["prompts"]
         torch.cuda.synchronize(device)
         dt = time.perf_counter() - t0
-        frames = (255.0 * video.permute(0, 1, 3, 4, 2)).to(torch.uint8).cpu()       # b t c h w -> b t h w c
+        if codec is None:
+            frames = (255.0 * video.permute(0, 1, 3, 4, 2)).to(torch.uint8).cpu()       # b t c h w -> b t h w c
         vae.model.clear_cache()
         for seed_idx in range(config.num_samples):
             name = output_name(rank, idx, seed_idx, model_type, config.save_with_index, first_prompt, interactive)
-            path = write_video(os.path.join(config.output_folder, name), frames[seed_idx], fps=16)
-            records.append({"path": path, "idx": idx, "frames": int(frames.shape[1]), "seconds": dt, **extra})
+            if codec is None:
+                path = write_video(os.path.join(config.output_folder, name), frames[seed_idx], fps=16)
+                records.append({"path": path, "idx": idx, "frames": int(frames.shape[1]), "seconds": dt, **extra})
+                continue
+            from . import ops
+            files = ops.jpeg_bytes(*ops.jpeg_encode(video[seed_idx], quality))           # uint8 [T', H, W, 3] on the device
+            path = os.path.splitext(os.path.join(config.output_folder, name))[0] + ".avi"
+            size = write_avi_mjpeg(path, files, int(video.shape[3]), int(video.shape[2]), fps=16)
+            records.append({"path": path, "idx": idx, "frames": len(files), "seconds": dt, "codec": codec, "bytes": size, **extra})
         if config.inference_iter != -1 and i >= config.inference_iter:
             break
     return records

@@ -641,6 +641,42 @@ __global__ __launch_bounds__(256) void cl_to_tchw_clamp_kernel(const bf16* __res
   }
 }
 
+// Frames out: channels-last bf16 [T, H, W, ldc] (first 3 channels) -> uint8 [T, H, W, 3] (frame stride st in BYTES), each byte
+// trunc(255.0f * clamp(clamp(float(x), -1, 1) * 0.5f + 0.5f, 0, 1)) in fp32 with no contraction: cl_to_tchw_clamp_kernel's clamp
+// (NaN -> -1 -> byte 0), then the pipelines' `(v * 0.5 + 0.5).clamp(0, 1)` and the writer's `(255.0 * v).to(uint8)`.  The mirror of
+// pixels_u8_to_cl_kernel: a lane owns a run of 4 pixels = 12 output bytes, stored as three dwords where the address is dword
+// aligned and as bytes otherwise and on a frame's last, partial group.
+__global__ __launch_bounds__(256) void cl_to_frames_u8_kernel(const bf16* __restrict__ x, uint8_t* __restrict__ out, long long st,
+                                                              long long hw, long long groups, long long total, int ldc) {
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;      // group of 4 pixels
+  if (i >= total) return;
+  long long t = i / groups, p0 = (i - t * groups) * 4;
+  const int n = (int)(hw - p0 < 4 ? hw - p0 : 4);               // pixels of this group inside the frame
+  const bf16* s = x + (t * hw + p0) * ldc;
+  uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j >= n) break;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float v = (float)s[(long long)j * ldc + c];
+      v = fminf(fmaxf(v, -1.0f), 1.0f);
+      v = fminf(fmaxf(v * 0.5f + 0.5f, 0.0f), 1.0f);
+      const int b = 3 * j + c;
+      w[b >> 2] |= (uint32_t)(int)(255.0f * v) << (8 * (b & 3));
+    }
+  }
+  uint8_t* o = out + t * st + p0 * 3;
+  if (n == 4 && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+    uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+    o4[0] = w[0]; o4[1] = w[1]; o4[2] = w[2];
+  } else {
+#pragma unroll
+    for (int b = 0; b < 12; ++b)
+      if (b < 3 * n) o[b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+  }
+}
+
 // Encoder input: pixels [3, T, H, W] or [T, 3, H, W] (element strides sc, st; rows contiguous), fp32 or bf16 -> channels-last bf16
 // [T, H, W, CPAD], channels >= 3 zero; fp32 is rounded to bf16 once (the `pixel.to(bf16)` of the reference's callers).
 template <typename TI, int CPAD>
@@ -969,6 +1005,18 @@ extern "C" int ll_cl_to_tchw_clamp(const ll_bf16* x, float* out, int T, int H, i
   hipLaunchKernelGGL(cl_to_tchw_clamp_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)x, out, ppf, total, ldc);
   return ll_check_launch("ll_cl_to_tchw_clamp");
+}
+
+extern "C" int ll_cl_to_frames_u8(const ll_bf16* x, uint8_t* out, long long stride_t, int T, int H, int W, int ldc, ll_stream stream) {
+  LL_REQUIRE(x != nullptr && out != nullptr, "ll_cl_to_frames_u8: null operand");
+  LL_REQUIRE(ldc >= 3, "ll_cl_to_frames_u8: ldc=%d, needs >= 3 channels per pixel", ldc);
+  LL_REQUIRE(T > 0 && H > 0 && W > 0, "ll_cl_to_frames_u8: empty input %d x %d x %d", T, H, W);
+  const long long hw = (long long)H * W, groups = (hw + 3) / 4, total = groups * T;
+  LL_REQUIRE(stride_t >= 3 * hw, "ll_cl_to_frames_u8: stride_t=%lld bytes must span a %d x %d x 3 frame", stride_t, H, W);
+  LL_REQUIRE((total + 255) / 256 <= 0x7fffffffll, "ll_cl_to_frames_u8: %d x %d x %d is more than one launch covers", T, H, W);
+  hipLaunchKernelGGL(cl_to_frames_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, out,
+                     stride_t, hw, groups, total, ldc);
+  return ll_check_launch("ll_cl_to_frames_u8");
 }
 
 // ---- encoder: strided gathers (Resample 'downsample2d' / 'downsample3d', wan/modules/vae.py:87-96, 143-159) -------------------

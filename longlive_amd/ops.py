@@ -710,6 +710,79 @@ def cl_to_tchw_clamp(x):
     return out
 
 
+# ---- frames out: uint8 frames from the decoder, baseline JPEG ----------------------------------------------------------
+def _frames_u8(frames, what: str):
+    """uint8 [T, H, W, 3] on the device with contiguous frames (copied when they are not) and its frame stride in bytes."""
+    if not frames.is_cuda:
+        raise RuntimeError(f"{what}: expected a device tensor (longlive_amd has no CPU path)")
+    if frames.dtype != torch.uint8:
+        raise RuntimeError(f"{what}: expected uint8, got {frames.dtype}")
+    assert frames.dim() == 4 and frames.shape[3] == 3, f"{what}: {tuple(frames.shape)} is not [T, H, W, 3]"
+    T, H, W, _ = frames.shape
+    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W or (T > 1 and frames.stride(0) < 3 * H * W):
+        frames = frames.contiguous()
+    return frames, (frames.stride(0) if T > 1 else 3 * H * W)
+
+
+def cl_to_frames_u8(x, out=None):
+    """[T,H,W,C>=3] bf16 channels-last -> uint8 [T,H,W,3]: `(255.0 * (cl_to_tchw_clamp(x) * 0.5 + 0.5).clamp(0, 1)).to(uint8)` laid out
+    frame by frame, bit for bit, in one pass.  `out`: a uint8 [T,H,W,3] view whose frames are contiguous (any frame stride)."""
+    _chk(x, "x")
+    T, H, W, C = x.shape
+    if out is None:
+        out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=x.device)
+    if not out.is_cuda or out.dtype != torch.uint8:
+        raise RuntimeError("out: expected a uint8 device tensor")
+    assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
+        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
+    stride_t = out.stride(0) if T > 1 else 3 * H * W
+    assert stride_t >= 3 * H * W
+    _lib.check(_lib.load().ll_cl_to_frames_u8(x.data_ptr(), out.data_ptr(), stride_t, T, H, W, C, _stream()), "ll_cl_to_frames_u8")
+    return out
+
+
+def jpeg_sizes(T: int, H: int, W: int):
+    """(out_stride, scratch_bytes) of ll_jpeg_encode_u8 for T frames of H x W (host only)."""
+    import ctypes
+    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.check(_lib.load().ll_jpeg_sizes(T, H, W, ctypes.byref(a), ctypes.byref(b)), "ll_jpeg_sizes")
+    return int(a.value), int(b.value)
+
+
+def jpeg_encode(frames, quality: int = 90):
+    """uint8 frames [T, H, W, 3] RGB (or a view with contiguous frames) -> (buf uint8 [T, out_stride], sizes int32 [T]): frame t's
+    baseline JPEG file (4:2:0, one restart interval per MCU row) is buf[t, :sizes[t]].  Stream-ordered: nothing is read back."""
+    frames, stride_t = _frames_u8(frames, "frames")
+    T, H, W, _ = frames.shape
+    out_stride, scratch_bytes = jpeg_sizes(T, H, W)
+    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=frames.device)
+    sizes = torch.empty(T, dtype=torch.int32, device=frames.device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.load().ll_jpeg_encode_u8(frames.data_ptr(), stride_t, T, H, W, int(quality), buf.data_ptr(), out_stride,
+                                             sizes.data_ptr(), scratch.data_ptr(), scratch_bytes, _stream()), "ll_jpeg_encode_u8")
+    return buf, sizes
+
+
+def jpeg_bytes(buf, sizes) -> list:
+    """The files of jpeg_encode on the host: one copy of `sizes`, then one of the bytes in use."""
+    n = sizes.cpu().tolist()
+    if not n:
+        return []
+    width = max(n)
+    host = buf[:, :width].cpu().numpy()
+    return [host[t, :k].tobytes() for t, k in enumerate(n)]
+
+
+def jpeg_coefficients(frames, quality: int = 90):
+    """The encoder's first stage alone: int16 [T, ceil(H/16), ceil(W/16), 6, 64], blocks Y00 Y01 Y10 Y11 Cb Cr in zigzag order."""
+    frames, stride_t = _frames_u8(frames, "frames")
+    T, H, W, _ = frames.shape
+    coef = torch.empty(T, (H + 15) // 16, (W + 15) // 16, 6, 64, dtype=torch.int16, device=frames.device)
+    _lib.check(_lib.load().ll_jpeg_coefficients_u8(frames.data_ptr(), stride_t, T, H, W, int(quality), coef.data_ptr(), _stream()),
+               "ll_jpeg_coefficients_u8")
+    return coef
+
+
 # ---- VAE encoder: strided gathers, pixel intake, latent scaling ------------------------------------------------------
 def _conv_down(kind: int, x, packed, bias, geo, out):
     cin, cout, kpad, kt, kh = geo

@@ -6,7 +6,7 @@ from typing import List, Optional
 
 import torch
 
-from .causal_inference import CausalInferencePipeline, _Profiler, _timeline
+from .causal_inference import CausalInferencePipeline, _Profiler, _timeline, check_frames_mode
 
 
 class InteractiveCausalInferencePipeline(CausalInferencePipeline):
@@ -49,11 +49,13 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
     @torch.no_grad()
     def inference(self, noise: torch.Tensor, *, text_prompts_list: List[List[str]], switch_frame_indices: List[int],
                   return_latents: bool = False, low_memory: bool = False, profile: bool = False,
-                  initial_latent: Optional[torch.Tensor] = None):
+                  initial_latent: Optional[torch.Tensor] = None, frames: str = "float", jpeg_quality: int = 90):
         """Switch to prompt segment i+1 at the first block whose start frame >= switch_frame_indices[i] (:237).
         initial_latent [B, n, 16, h, w]: the clip to continue (CausalInferencePipeline.inference), prefilled under
         text_prompts_list[0].  Frame numbers -- the switch indices too -- count on the n + T timeline and only GENERATED blocks
-        switch: an index <= n switches at the first generated block, whose recache then re-encodes prefix frames under the new prompt."""
+        switch: an index <= n switches at the first generated block, whose recache then re-encodes prefix frames under the new prompt.
+        frames: the form of the video, as in CausalInferencePipeline.inference."""
+        check_frames_mode(frames, jpeg_quality)
         prefix = self._check_prefix(noise, initial_latent)
         n = 0 if prefix is None else prefix.shape[1]
         batch_size, num_output_frames = noise.shape[:2]
@@ -69,12 +71,12 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
         prof.start("init")
         self._setup(noise, n + num_output_frames)
         prof.stop("init")
-        side = self._prefill_profiled(prefix, cond_list[0], noise, prof)
+        side = self._prefill_profiled(prefix, cond_list[0], noise, prof, frames)
         prof.start("diffusion")
         seg, start, switch_blocks = 0, n, []
         next_switch = switch_frame_indices[0] if switch_frame_indices else None
         if prefix is None:
-            side = self._side_decoder(noise)
+            side = self._side_decoder(noise, frames)
         for blk in range(num_blocks):
             nf = self.num_frame_per_block
             prof.block_start()
@@ -94,12 +96,7 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
         self._join_context()
         prof.stop("diffusion")
         prof.start("vae")
-        video = None
-        if side is not None:
-            video = side.finish()
-        elif self.vae is not None:
-            video = self.vae.decode_to_pixel(output, use_cache=False)
-            video = (video * 0.5 + 0.5).clamp(0, 1)
+        video = self._finish_video(side, output, frames, jpeg_quality)
         prof.stop("vae")
         self.last_profile = prof.report(self.num_frame_per_block, switch_blocks=tuple(switch_blocks))
         if return_latents:

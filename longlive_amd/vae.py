@@ -287,9 +287,13 @@ class WanVAEDecoderHIP(_VaeHalfHIP):
         return head(y)                          # [T', H, W, 8] (3 channels + padding)
 
     @torch.no_grad()
-    def decode(self, z: torch.Tensor, keep_cache: bool = False) -> torch.Tensor:
+    def decode(self, z: torch.Tensor, keep_cache: bool = False, frames: str = "float") -> torch.Tensor:
         """z [T, 16, h, w] bf16 latent frames of one video -> fp32 [T', 3, 8h, 8w] in [-1, 1];
-        T' = 1 + 4 (T - 1) on a fresh cache, 4 T when continuing a stream (WanVAE_.decode / cached_decode, vae.py:545-593)."""
+        T' = 1 + 4 (T - 1) on a fresh cache, 4 T when continuing a stream (WanVAE_.decode / cached_decode, vae.py:545-593).
+        frames="uint8": video frames uint8 [T', 8h, 8w, 3] instead, `(255.0 * (v * 0.5 + 0.5).clamp(0, 1)).to(uint8)` of the float
+        result v bit for bit, written by one kernel per chunk (ops.cl_to_frames_u8)."""
+        if frames not in ("float", "uint8"):
+            raise ValueError(f"WanVAEDecoderHIP.decode: frames={frames!r} is not 'float' or 'uint8'")
         if not self._packed:
             self._pack()
         if not keep_cache:
@@ -301,7 +305,7 @@ class WanVAEDecoderHIP(_VaeHalfHIP):
         while i < T:
             n = 1 if self._first else min(self.chunk, T - i)
             y = self._decoder_step(x[i:i + n])
-            outs.append(ops.cl_to_tchw_clamp(y))
+            outs.append(ops.cl_to_tchw_clamp(y) if frames == "float" else ops.cl_to_frames_u8(y))
             self._first = False
             i += n
         if not keep_cache:
@@ -454,6 +458,16 @@ class WanVAEWrapper(nn.Module):
             assert latent.shape[0] == 1, "Batch size must be 1 when using cache"          # utils/wan_wrapper.py:99
         out = [self.model.decode(u, keep_cache=use_cache) for u in latent]
         return torch.stack(out, 0)
+
+    def decode_to_frames(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
+        """latent [B, T, 16, h, w] -> video frames uint8 [B, T', H, W, 3]: bit for bit
+        `(255.0 * (decode_to_pixel(latent, use_cache) * 0.5 + 0.5).clamp(0, 1).permute(0, 1, 3, 4, 2)).to(torch.uint8)`, without the
+        fp32 planes ever existing."""
+        if latent.dtype != bf16:
+            latent = latent.to(bf16)
+        if use_cache:
+            assert latent.shape[0] == 1, "Batch size must be 1 when using cache"
+        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames="uint8") for u in latent], 0)
 
     def _get_encoder(self) -> WanVAEEncoderHIP:
         if self.encoder is None:
