@@ -55,7 +55,8 @@ enum ll_epilogue {
  * ll_conv_down_plan, ll_pixels_to_cl, ll_vae_scale_tchw), and so do the attention entry points with quantised output
  * (ll_flash_attn_q_ok, ll_flash_attn_q, ll_flash_attn_q_plan, ll_flash_attn_mx_q), and so does the uint8 video intake
  * (ll_pixels_u8_to_cl), and so do the frames-out entry points (ll_cl_to_frames_u8, ll_jpeg_sizes, ll_jpeg_encode_u8,
- * ll_jpeg_coefficients_u8): 111 covers them too. */
+ * ll_jpeg_coefficients_u8), and so do the clip-intake entry points (ll_jpeg_decode_sizes, ll_jpeg_decode_coefficients,
+ * ll_jpeg_decode_pixels, ll_jpeg_decode_u8, ll_resize_u8): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -547,6 +548,44 @@ int ll_jpeg_encode_u8(const uint8_t* frames, long long stride_t, int T, int H, i
 /* The first stage alone: colour conversion, 8 x 8 DCT and quantisation -> coef int16 [T, ceil(H/16), ceil(W/16), 6, 64], blocks
  * Y00 Y01 Y10 Y11 Cb Cr of every MCU, each in zigzag order (what the tests pin the arithmetic with). */
 int ll_jpeg_coefficients_u8(const uint8_t* frames, long long stride_t, int T, int H, int W, int quality, int16_t* coef, ll_stream stream);
+
+/* Clip intake: a baseline JPEG decoder (SOF0, 8 bits; 1 component, or 3 as YCbCr with luma sampling hs x vs = 1x1, 2x1 or 2x2 and
+ * chroma 1x1; any tables; any restart interval) and an antialiased resize.  The host parses the files (longlive_amd/jpeg_files.py);
+ * every array below except the two size outputs is a DEVICE pointer.  Arithmetic in csrc/jpeg_dec.hip's head comment, restated in
+ * tests/jpeg_dec_ref.py.  MCU grid: rows = ceil(H / (8 vs)), cols = ceil(W / (8 hs)), bpm = hs * vs + 2 blocks per MCU (1 for grey).
+ *   data  uint8 [nbytes]      the frames' entropy-coded bytes, still stuffed
+ *   segs  int32 [nseg, 5]     per restart segment: byte offset, byte length, frame, first MCU, MCU count
+ *   huff  uint8 [T, 4, 272]   per frame (BITS[16], HUFFVAL[256]) of DC id 0, DC id 1, AC id 0, AC id 1
+ *   sel   uint8 [T, 4]        per frame and component (AC id << 4) | DC id
+ *   qt    uint16 [T, 3, 64]   per frame and component, natural order
+ *   coef  int16 [T, rows, cols, bpm, 64]   zigzag order, blocks in scan order (for 2x2 the layout of ll_jpeg_coefficients_u8)
+ *   status int32 [nseg]       0, or the JD_* code of csrc/jpeg_dec.h; a failed segment's remaining blocks are zero
+ * A segment row that points outside data, the T frames or a frame's MCUs is not decoded (status 7).  Nothing checks the rows
+ * against each other: rows that overlap, or that leave MCUs of a frame uncovered, leave those blocks of coef as they were.  The
+ * table is the host parser's (pack_jpegs), which covers every MCU of every frame exactly once.  No allocation, no
+ * synchronisation; coef, status and scratch may hold anything.  Refused before any launch: null operands, T, H, W < 1, H or W > 65535,
+ * other component counts or sampling, nbytes outside 0 .. 2^31 - 1, nseg < 1, misaligned tables (4 bytes) or coef (16 bytes in the
+ * entropy stage), short stride_t / scratch_bytes.
+ *
+ * ll_jpeg_decode_sizes (host only): *coef_bytes = the coefficient tensor, *scratch_bytes = the fp32 component planes. */
+int ll_jpeg_decode_sizes(int T, int H, int W, int ncomp, int hs, int vs, long long* coef_bytes, long long* scratch_bytes);
+int ll_jpeg_decode_coefficients(const uint8_t* data, long long nbytes, const int32_t* segs, int nseg, const uint8_t* huff,
+                                const uint8_t* sel, int T, int H, int W, int ncomp, int hs, int vs, int16_t* coef, int32_t* status,
+                                ll_stream stream);
+/* coef -> out uint8 [T,H,W,3] RGB (stride_t in BYTES >= H*W*3; bytes outside the T frames are never written; grey writes Y thrice). */
+int ll_jpeg_decode_pixels(const int16_t* coef, const uint16_t* qt, int T, int H, int W, int ncomp, int hs, int vs, uint8_t* out,
+                          long long stride_t, void* scratch, long long scratch_bytes, ll_stream stream);
+/* Both stages: three launches. */
+int ll_jpeg_decode_u8(const uint8_t* data, long long nbytes, const int32_t* segs, int nseg, const uint8_t* huff, const uint8_t* sel,
+                      const uint16_t* qt, int T, int H, int W, int ncomp, int hs, int vs, int16_t* coef, int32_t* status, uint8_t* out,
+                      long long stride_t, void* scratch, long long scratch_bytes, ll_stream stream);
+/* Separable antialiased triangle-filter resize of the crop window Hc x Wc at (y0, x0) of uint8 frames [T,Hs,Ws,3] into [T,Hd,Wd,3]
+ * (strides in BYTES).  Per axis the host passes, as device pointers, start int32 [out], count int32 [out] and weights fp32 [out, k]
+ * (k = ky or kx, rows padded with zeros; indices relative to the window).  fp32, vertical then horizontal, no rounding in between,
+ * then clamp(floor(v + 0.5), 0, 255).  The kernel clamps start and count into the window, so no table can move a read outside it. */
+int ll_resize_u8(const uint8_t* src, long long src_stride_t, int Hs, int Ws, int y0, int x0, int Hc, int Wc, uint8_t* dst,
+                 long long dst_stride_t, int Hd, int Wd, int T, const int32_t* ystart, const int32_t* ycount, const float* yweight, int ky,
+                 const int32_t* xstart, const int32_t* xcount, const float* xweight, int kx, ll_stream stream);
 
 /* -- encoder (Encoder3d + conv1, wan/modules/vae.py:265-366, 517-543): every stride-1 convolution runs on ll_conv_cl; the two
  * strided gathers below are further gather modes of the same implicit GEMM (same LDS staging, swizzle and epilogue). -- */

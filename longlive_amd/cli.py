@@ -16,6 +16,9 @@ Extra keys, both modes: `input_video: <path>` continues a clip -- every prompt o
 `input_frames: <int>` caps how many of its frames are used (the LAST 1 + 4k frames that fit).
 `video_codec: mjpeg` writes `<name>.avi` as Motion JPEG, encoded on the GPU at `jpeg_quality: 90` ("Frames
 out"); without the key the video is written as before.  An MJPEG .avi is also read back as `input_video` (through PIL).
+`input_decode: gpu` decodes such a file's frames on the GPU instead (ops.jpeg_decode: baseline JPEG as this project, libjpeg, Pillow
+or ffmpeg write it), and `input_fit: cover | stretch` resizes a clip of another size to the model's on the GPU (ops.resize_u8);
+without the two keys intake is as before ("Clip intake on the GPU").
 """
 from __future__ import annotations
 
@@ -285,6 +288,45 @@ def read_avi_mjpeg(path: str) -> torch.Tensor:
     return torch.stack(frames, 0)
 
 
+def read_avi_mjpeg_files(path: str) -> List[bytes]:
+    """The '00dc' chunks of a Motion-JPEG AVI, undecoded: one complete JPEG file per frame (what write_avi_mjpeg was given)."""
+    raw = open(path, "rb").read()
+    if raw[:4] != b"RIFF" or raw[8:12] != b"AVI " or b"movi" not in raw:
+        raise ValueError(f"input_video: {path!r} is not an AVI file")
+    files, q = [], raw.index(b"movi") + 4
+    while raw[q:q + 4] == b"00dc":
+        n = struct.unpack("<I", raw[q + 4:q + 8])[0]
+        files.append(raw[q + 8:q + 8 + n])
+        q += 8 + n + (n & 1)
+    if not files:
+        raise ValueError(f"input_video: {path!r} holds no '00dc' frame")
+    return files
+
+
+INPUT_DECODES = ("host", "gpu")
+INPUT_FITS = ("cover", "stretch")
+
+
+def input_decode(value) -> str:
+    """The yaml's `input_decode:` key: absent / host = MJPEG frames decoded by PIL, gpu = by ops.jpeg_decode."""
+    if value is None:
+        return "host"
+    v = str(value).strip().lower()
+    if isinstance(value, bool) or v not in INPUT_DECODES:
+        raise ValueError(f"input_decode: {value!r} is not one of {', '.join(INPUT_DECODES)} (or absent)")
+    return v
+
+
+def input_fit(value) -> Optional[str]:
+    """The yaml's `input_fit:` key: absent = a clip of another size is refused, cover / stretch = ops.resize_u8's `fit`."""
+    if value is None:
+        return None
+    v = str(value).strip().lower()
+    if isinstance(value, bool) or v not in INPUT_FITS:
+        raise ValueError(f"input_fit: {value!r} is not one of {', '.join(INPUT_FITS)} (or absent)")
+    return v
+
+
 VIDEO_CODECS = ("mjpeg",)
 
 
@@ -369,6 +411,31 @@ def load_clip(config, lat_h: int, lat_w: int) -> Optional[torch.Tensor]:
         raise ValueError(f"input_video: {path!r} is {frames.shape[2]}x{frames.shape[1]} (W x H), the configured size is "
                          f"{8 * lat_w}x{8 * lat_h}; clips are not resized")
     return frames[select_clip_frames(frames.shape[0], config.get("input_frames"))].contiguous()
+
+
+def load_clip_device(config, lat_h: int, lat_w: int, device):
+    """load_clip with the yaml's `input_decode` / `input_fit` keys: (uint8 [1 + 4k, H, W, 3] ON THE DEVICE, [W, H] of the source when
+    it was resized, else None).  `input_decode: gpu` takes an MJPEG .avi: select_clip_frames runs on the chunk count, so only the
+    chosen files are parsed, uploaded and decoded (ops.jpeg_decode).  `input_fit` resizes a clip of another size on the device
+    (ops.resize_u8); without it such a clip is refused as before."""
+    from . import ops
+    path = str(config.get("input_video"))
+    decode, fit = input_decode(config.get("input_decode")), input_fit(config.get("input_fit"))
+    if decode == "gpu":
+        if os.path.splitext(path)[1].lower() != ".avi" or avi_compression(path) != b"MJPG":
+            raise ValueError(f"input_decode: gpu reads a Motion-JPEG .avi, {path!r} is not one")
+        files = read_avi_mjpeg_files(path)
+        frames = ops.jpeg_decode(files[select_clip_frames(len(files), config.get("input_frames"))], device=device)
+    else:
+        frames = read_input_video(path)
+        frames = frames[select_clip_frames(frames.shape[0], config.get("input_frames"))].contiguous().to(device)
+    H, W = 8 * lat_h, 8 * lat_w
+    if tuple(frames.shape[1:3]) == (H, W):
+        return frames, None
+    if fit is None:
+        raise ValueError(f"input_video: {path!r} is {frames.shape[2]}x{frames.shape[1]} (W x H), the configured size is {W}x{H}; "
+                         f"set input_fit: cover | stretch to resize it")
+    return ops.resize_u8(frames, (H, W), fit=fit), [int(frames.shape[2]), int(frames.shape[1])]
 
 
 # ---- tokenizers --------------------------------------------------------------------------------------------------------
@@ -497,8 +564,8 @@ def _dist_env():
 
 def run(mode: str, config, synthetic: bool = False, device: Optional[torch.device] = None) -> List[Dict]:
     """The body of inference.py (mode 'inference') / interactive_inference.py (mode 'interactive').  Returns one record per
-    written video: {"path", "idx", "frames", "seconds"}, "input_frames" when the yaml's `input_video` gave a clip to continue, and
-    "codec" and "bytes" when `video_codec` chose one."""
+    written video: {"path", "idx", "frames", "seconds"}, "input_frames" when the yaml's `input_video` gave a clip to continue,
+    "input_size" ([W, H] of the clip) when `input_fit` resized it, and "codec" and "bytes" when `video_codec` chose one."""
     from .pipeline import CausalInferencePipeline, InteractiveCausalInferencePipeline
     local_rank, rank, world = _dist_env()
     if device is None:
@@ -509,7 +576,13 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     shape = wan_config(config, synthetic)
     codec = video_codec(config.get("video_codec"))             # names and ranges are refused before any model is built
     quality = jpeg_quality(config.get("jpeg_quality"))
-    clip = load_clip(config, shape.lat_h, shape.lat_w)         # read and checked before any model is built
+    on_device = config.get("input_decode") is not None or config.get("input_fit") is not None
+    input_decode(config.get("input_decode")), input_fit(config.get("input_fit"))
+    input_size = None
+    if on_device and config.get("input_video"):                # decoded / resized on the device, still before any model is built
+        clip, input_size = load_clip_device(config, shape.lat_h, shape.lat_w, device)
+    else:
+        clip = load_clip(config, shape.lat_h, shape.lat_w)     # read and checked before any model is built
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
     gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6, W4A6 or W4A4
     gen.model.set_attn_quant(attn_quant_mode(config.get("attn_quant", "none")))   # self-attention: bf16 or MXFP8
@@ -533,6 +606,8 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         latent = vae.encode_frames_to_latent(clip.unsqueeze(0).to(device))
         more["initial_latent"] = latent.expand(config.num_samples, *latent.shape[1:])
         extra["input_frames"] = int(clip.shape[0])
+        if input_size is not None:
+            extra["input_size"] = input_size
     if codec is not None:                           # the pipeline hands back uint8 frames: no fp32 planes, no torch conversion
         more["frames"] = "uint8"
     records = []

@@ -783,6 +783,165 @@ def jpeg_coefficients(frames, quality: int = 90):
     return coef
 
 
+# ---- clip intake: baseline JPEG decoder, antialiased resize ------------------------------------------------------------
+def jpeg_decode_sizes(T: int, H: int, W: int, components: int, hs: int, vs: int):
+    """(coef_bytes, scratch_bytes) of ll_jpeg_decode_u8 (host only)."""
+    import ctypes
+    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.check(_lib.load().ll_jpeg_decode_sizes(T, H, W, components, hs, vs, ctypes.byref(a), ctypes.byref(b)), "ll_jpeg_decode_sizes")
+    return int(a.value), int(b.value)
+
+
+def _jpeg_upload(files, device):
+    """pack_jpegs(files) and its arrays on the device, sent as ONE buffer: (packed, {name: device view})."""
+    import numpy as np
+    from . import jpeg_files
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("jpeg_decode: expected a device (longlive_amd has no CPU path)")
+    pk = jpeg_files.pack_jpegs(files)
+    parts = {"segs": pk.segs, "qt": pk.qt, "huff": pk.huff, "sel": pk.sel, "data": pk.data}
+    offs, n = {}, 0
+    for k, a in parts.items():
+        offs[k] = n
+        n += (a.nbytes + 15) // 16 * 16
+    blob = np.zeros(max(n, 16), dtype=np.uint8)
+    for k, a in parts.items():
+        blob[offs[k]:offs[k] + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    dev = torch.from_numpy(blob).to(device)
+    return pk, {k: dev[offs[k]:offs[k] + max(a.nbytes, 1)] for k, a in parts.items()}
+
+
+def _jpeg_status(status, pk):
+    bad = {}
+    for s, code in enumerate(status.cpu().tolist()):
+        if code:
+            bad.setdefault(int(pk.segs[s, 2]), code)
+    if bad:
+        raise ValueError("jpeg_decode: malformed entropy-coded data in frame" + ("s " if len(bad) > 1 else " ") +
+                         ", ".join(f"{t} (code {c})" for t, c in sorted(bad.items())))
+
+
+def _jpeg_coef_out(pk, device, coef):
+    rows, cols, bpm = pk.grid
+    shape = (pk.frames, rows, cols, bpm, 64)
+    if coef is None:
+        coef = torch.empty(shape, dtype=torch.int16, device=device)
+    assert coef.is_cuda and coef.dtype == torch.int16 and tuple(coef.shape) == shape and coef.is_contiguous(), \
+        f"coef: expected a contiguous int16 device tensor {shape}"
+    return coef
+
+
+def jpeg_decode_coefficients(files, device=None, out=None, check: bool = True):
+    """Baseline JPEG files (bytes, same size and sampling) -> int16 [T, rows, cols, bpm, 64] on the device: the entropy stage alone, in
+    zigzag order, blocks in scan order (for 4:2:0 the layout of jpeg_coefficients).  `check` reads the segments' status back once and
+    raises ValueError naming the frames whose data is malformed."""
+    pk, d = _jpeg_upload(files, device)
+    coef = _jpeg_coef_out(pk, d["data"].device, out)
+    status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=coef.device)
+    _lib.check(_lib.load().ll_jpeg_decode_coefficients(d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0],
+                                                       d["huff"].data_ptr(), d["sel"].data_ptr(), pk.frames, pk.height, pk.width,
+                                                       pk.components, pk.hs, pk.vs, coef.data_ptr(), status.data_ptr(), _stream()),
+               "ll_jpeg_decode_coefficients")
+    if check:
+        _jpeg_status(status, pk)
+    return coef
+
+
+def jpeg_decode(files, device=None, check: bool = True, out=None, scratch=None):
+    """Baseline JPEG files (bytes; grey, 4:4:4, 4:2:2 or 4:2:0, all of one size and sampling) -> uint8 [T, H, W, 3] RGB on the device.
+    One host-to-device copy of the packed bytes and tables, three launches.  `check` reads the segments' status back once and raises
+    ValueError naming the frames whose entropy data is malformed.  `out`: a uint8 [T, H, W, 3] view with contiguous frames (any
+    frame stride); `scratch`: (coef int16, planes uint8) to decode into, any content."""
+    pk, d = _jpeg_upload(files, device)
+    device = d["data"].device
+    T, H, W = pk.frames, pk.height, pk.width
+    coef_bytes, scratch_bytes = jpeg_decode_sizes(T, H, W, pk.components, pk.hs, pk.vs)
+    coef, planes = scratch if scratch is not None else (None, None)
+    coef = _jpeg_coef_out(pk, device, coef)
+    if planes is None:
+        planes = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+    assert planes.is_cuda and planes.dtype == torch.uint8 and planes.numel() >= scratch_bytes and planes.is_contiguous()
+    if out is None:
+        out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=device)
+    if not out.is_cuda or out.dtype != torch.uint8:
+        raise RuntimeError("out: expected a uint8 device tensor")
+    assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
+        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
+    stride_t = out.stride(0) if T > 1 else 3 * H * W
+    status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=device)
+    _lib.check(_lib.load().ll_jpeg_decode_u8(d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0],
+                                             d["huff"].data_ptr(), d["sel"].data_ptr(), d["qt"].data_ptr(), T, H, W, pk.components, pk.hs,
+                                             pk.vs, coef.data_ptr(), status.data_ptr(), out.data_ptr(), stride_t, planes.data_ptr(),
+                                             planes.numel(), _stream()), "ll_jpeg_decode_u8")
+    if check:
+        _jpeg_status(status, pk)
+    return out
+
+
+def resize_taps(n_in: int, n_out: int):
+    """Antialiased triangle filter of one axis as host arrays (start int32 [n_out], count int32 [n_out], weights fp32 [n_out, k]): with
+    scale = in / out, s = max(scale, 1), c = (o + 0.5) scale the taps are i in [max(int(c - s + 0.5), 0), min(int(c + s + 0.5), in))
+    with weights max(0, 1 - |(i + 0.5 - c) / s|), normalised in fp64, then rounded to fp32."""
+    import numpy as np
+    scale = n_in / n_out
+    s = max(scale, 1.0)
+    c = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum((c - s + 0.5).astype(np.int64), 0)
+    hi = np.minimum((c + s + 0.5).astype(np.int64), n_in)
+    k = int((hi - lo).max())
+    i = lo[:, None] + np.arange(k)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs((i + 0.5 - c[:, None]) / s)) * (i < hi[:, None])
+    w = w / w.sum(axis=1, keepdims=True)
+    return lo.astype(np.int32), (hi - lo).astype(np.int32), w.astype(np.float32)
+
+
+@functools.lru_cache(maxsize=16)
+def _resize_tables(n_in: int, n_out: int, dev_index: int):
+    start, count, w = resize_taps(n_in, n_out)
+    dev = torch.device("cuda", dev_index)
+    return torch.from_numpy(start).to(dev), torch.from_numpy(count).to(dev), torch.from_numpy(w).to(dev)
+
+
+RESIZE_FITS = ("cover", "stretch")
+
+
+def cover_window(Hs: int, Ws: int, Hd: int, Wd: int):
+    """(y0, x0, Hc, Wc): the centred integer crop window of an Hs x Ws frame that has the target's aspect."""
+    if Ws * Hd >= Wd * Hs:
+        Wc = min(Ws, max(1, int(math.floor(Hs * Wd / Hd + 0.5))))
+        return 0, (Ws - Wc) // 2, Hs, Wc
+    Hc = min(Hs, max(1, int(math.floor(Ws * Hd / Wd + 0.5))))
+    return (Hs - Hc) // 2, 0, Hc, Ws
+
+
+def resize_u8(frames, size, fit: str = "cover", out=None):
+    """uint8 frames [T, Hs, Ws, 3] -> [T, Hd, Wd, 3] (size = (Hd, Wd)) by a separable antialiased triangle filter, what
+    F.interpolate(mode="bilinear", antialias=True) computes, rounded once at the end.  fit "cover": a centred crop window of the
+    target's aspect (cover_window) is resized; "stretch": the whole frame.  Equal sizes return the input's bytes."""
+    if fit not in RESIZE_FITS:
+        raise ValueError(f"fit: {fit!r} is not one of {', '.join(RESIZE_FITS)}")
+    frames, stride_t = _frames_u8(frames, "frames")
+    T, Hs, Ws, _ = frames.shape
+    Hd, Wd = int(size[0]), int(size[1])
+    assert T >= 1 and Hd >= 1 and Wd >= 1
+    y0, x0, Hc, Wc = cover_window(Hs, Ws, Hd, Wd) if fit == "cover" else (0, 0, Hs, Ws)
+    if out is None:
+        out = torch.empty(T, Hd, Wd, 3, dtype=torch.uint8, device=frames.device)
+    if not out.is_cuda or out.dtype != torch.uint8:
+        raise RuntimeError("out: expected a uint8 device tensor")
+    assert out.shape == (T, Hd, Wd, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * Wd, \
+        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
+    idx = _dev_index(frames.device)
+    ys, yn, yw = _resize_tables(Hc, Hd, idx)
+    xs, xn, xw = _resize_tables(Wc, Wd, idx)
+    _lib.check(_lib.load().ll_resize_u8(frames.data_ptr(), stride_t, Hs, Ws, y0, x0, Hc, Wc, out.data_ptr(),
+                                        out.stride(0) if T > 1 else 3 * Hd * Wd, Hd, Wd, T, ys.data_ptr(), yn.data_ptr(), yw.data_ptr(),
+                                        yw.shape[1], xs.data_ptr(), xn.data_ptr(), xw.data_ptr(), xw.shape[1], _stream()), "ll_resize_u8")
+    return out
+
+
 # ---- VAE encoder: strided gathers, pixel intake, latent scaling ------------------------------------------------------
 def _conv_down(kind: int, x, packed, bias, geo, out):
     cin, cout, kpad, kt, kh = geo
