@@ -56,7 +56,8 @@ enum ll_epilogue {
  * (ll_flash_attn_q_ok, ll_flash_attn_q, ll_flash_attn_q_plan, ll_flash_attn_mx_q), and so does the uint8 video intake
  * (ll_pixels_u8_to_cl), and so do the frames-out entry points (ll_cl_to_frames_u8, ll_jpeg_sizes, ll_jpeg_encode_u8,
  * ll_jpeg_coefficients_u8), and so do the clip-intake entry points (ll_jpeg_decode_sizes, ll_jpeg_decode_coefficients,
- * ll_jpeg_decode_pixels, ll_jpeg_decode_u8, ll_resize_u8): 111 covers them too. */
+ * ll_jpeg_decode_pixels, ll_jpeg_decode_u8, ll_resize_u8), and so do the split entropy route's (ll_jpeg_decode_split_sizes,
+ * ll_jpeg_decode_coefficients_split, ll_jpeg_decode_u8_split): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -579,6 +580,26 @@ int ll_jpeg_decode_pixels(const int16_t* coef, const uint16_t* qt, int T, int H,
 int ll_jpeg_decode_u8(const uint8_t* data, long long nbytes, const int32_t* segs, int nseg, const uint8_t* huff, const uint8_t* sel,
                       const uint16_t* qt, int T, int H, int W, int ncomp, int hs, int vs, int16_t* coef, int32_t* status, uint8_t* out,
                       long long stride_t, void* scratch, long long scratch_bytes, ll_stream stream);
+/* The split route through the entropy stage: the subsequences of a segment decode side by side (csrc/jpeg_dec.h: resumable decoder
+ * and speculation policy; csrc/jpeg_dec.hip: passes).  coef and status are the serial entry points', bit for bit, for every input.
+ *   subs  int32 [nsub, 3]     per subsequence: segment, byte offset inside the segment, byte length; the rows of a segment follow
+ *                             one another and tile its bytes in order, segments in rising order (jpeg_files.split_segments); a
+ *                             segment without rows is decoded serially
+ *   rounds 1..64              resynchronisation rounds after pass 0, one launch each
+ *   info  int32 [nseg]        0 = serial by table, r >= 1 = settled in round r, -1 = fell back unsettled, -2 = fell back flagged
+ *                             (a bad row of subs, a block count that is not the segment's, any JD_* condition)
+ *   work                      ll_jpeg_decode_split_sizes(nseg, nsub) bytes, 16-byte aligned, any content
+ * Every row of subs is checked on the device before it is used.  rounds + 6 launches, no allocation, no synchronisation.  Refused
+ * before any launch: what the serial entry points refuse, null operands, nsub < 1, rounds outside 1..64, misaligned or short work. */
+int ll_jpeg_decode_split_sizes(int nseg, int nsub, long long* work_bytes);
+int ll_jpeg_decode_coefficients_split(const uint8_t* data, long long nbytes, const int32_t* segs, int nseg, const uint8_t* huff,
+                                      const uint8_t* sel, int T, int H, int W, int ncomp, int hs, int vs, int16_t* coef, int32_t* status,
+                                      const int32_t* subs, int nsub, int rounds, int32_t* info, void* work, long long work_bytes,
+                                      ll_stream stream);
+int ll_jpeg_decode_u8_split(const uint8_t* data, long long nbytes, const int32_t* segs, int nseg, const uint8_t* huff, const uint8_t* sel,
+                            const uint16_t* qt, int T, int H, int W, int ncomp, int hs, int vs, int16_t* coef, int32_t* status, uint8_t* out,
+                            long long stride_t, void* scratch, long long scratch_bytes, const int32_t* subs, int nsub, int rounds,
+                            int32_t* info, void* work, long long work_bytes, ll_stream stream);
 /* Separable antialiased triangle-filter resize of the crop window Hc x Wc at (y0, x0) of uint8 frames [T,Hs,Ws,3] into [T,Hd,Wd,3]
  * (strides in BYTES).  Per axis the host passes, as device pointers, start int32 [out], count int32 [out] and weights fp32 [out, k]
  * (k = ky or kx, rows padded with zeros; indices relative to the window).  fp32, vertical then horizontal, no rounding in between,

@@ -327,6 +327,27 @@ def input_fit(value) -> Optional[str]:
     return v
 
 
+INPUT_SPLIT_DEFAULT = "auto"    # what an absent `input_split:` means: None = off, or "auto" (DESIGN.md section 5c holds the measurement)
+
+
+def input_split(value):
+    """The yaml's `input_split:` key for `input_decode: gpu`: off = one lane per restart segment (None), auto = ops.jpeg_decode's
+    split="auto", an integer = that many bytes per subsequence (a multiple of 4, at least 8); absent = INPUT_SPLIT_DEFAULT."""
+    if value is None:
+        return INPUT_SPLIT_DEFAULT
+    if value is False:                                  # a bare `off` in yaml 1.1 is the boolean
+        return None
+    v = str(value).strip().lower()
+    if not isinstance(value, bool) and isinstance(value, (int, str)):
+        if v == "off":
+            return None
+        if v == "auto":
+            return "auto"
+        if v.isdigit() and int(v) >= 8 and int(v) % 4 == 0:
+            return int(v)
+    raise ValueError(f"input_split: {value!r} is not auto, off or a number of bytes (a multiple of 4, at least 8)")
+
+
 VIDEO_CODECS = ("mjpeg",)
 
 
@@ -425,7 +446,8 @@ def load_clip_device(config, lat_h: int, lat_w: int, device):
         if os.path.splitext(path)[1].lower() != ".avi" or avi_compression(path) != b"MJPG":
             raise ValueError(f"input_decode: gpu reads a Motion-JPEG .avi, {path!r} is not one")
         files = read_avi_mjpeg_files(path)
-        frames = ops.jpeg_decode(files[select_clip_frames(len(files), config.get("input_frames"))], device=device)
+        frames = ops.jpeg_decode(files[select_clip_frames(len(files), config.get("input_frames"))], device=device,
+                                 split=input_split(config.get("input_split")))
     else:
         frames = read_input_video(path)
         frames = frames[select_clip_frames(frames.shape[0], config.get("input_frames"))].contiguous().to(device)
@@ -577,7 +599,7 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     codec = video_codec(config.get("video_codec"))             # names and ranges are refused before any model is built
     quality = jpeg_quality(config.get("jpeg_quality"))
     on_device = config.get("input_decode") is not None or config.get("input_fit") is not None
-    input_decode(config.get("input_decode")), input_fit(config.get("input_fit"))
+    input_decode(config.get("input_decode")), input_fit(config.get("input_fit")), input_split(config.get("input_split"))
     input_size = None
     if on_device and config.get("input_video"):                # decoded / resized on the device, still before any model is built
         clip, input_size = load_clip_device(config, shape.lat_h, shape.lat_w, device)

@@ -193,6 +193,7 @@ static int g_gemm_lds_epi = 1;
 static int g_gemm_asm = 35;        // generated kernels where they cover the call (bits 0, 1), persistent form for multi-round launches (bit 5)
 static int g_gemm_group_m = 4;     // m-tiles per group in the workgroup -> tile walk (tile_of); <= 1: N fastest (round 1's order)
 void ll_set_conv_halo_internal(int v);
+int ll_set_jpeg_split_lanes_internal(int v);
 extern "C" int ll_set_tuning(const char* key, int value) {
   if (!strcmp(key, "gemm_variant")) { g_gemm_variant = value; return LL_OK; }
   if (!strcmp(key, "gemm_group_m")) { g_gemm_group_m = value; return LL_OK; }
@@ -210,6 +211,10 @@ extern "C" int ll_set_tuning(const char* key, int value) {
   if (!strcmp(key, "attn_asm_min_keys")) { g_attn.asm_min_keys = value; return LL_OK; }
   if (!strcmp(key, "attn_asm")) { g_attn.asm_on = value; return LL_OK; }
   if (!strcmp(key, "conv_halo")) { ll_set_conv_halo_internal(value); return LL_OK; }
+  if (!strcmp(key, "jpeg_split_lanes")) {          // lanes per wave of the JPEG subsequence kernels (jpeg_dec.hip)
+    if (ll_set_jpeg_split_lanes_internal(value)) { ll_set_error("ll_set_tuning: jpeg_split_lanes=%d (1, 64, or 0 = by subsequence size)", value); return LL_ERR_INVALID_ARG; }
+    return LL_OK;
+  }
   if (!strcmp(key, "gemm_asm_mfma16")) {
     if (value < -1 || value > 511) { ll_set_error("ll_set_tuning: gemm_asm_mfma16=%d (a mask of 9 bits, one per kernel; -1 = the default)", value); return LL_ERR_INVALID_ARG; }
     g_gemm_asm_mfma16 = value < 0 ? g_gemm_asm_mfma16_default : value;

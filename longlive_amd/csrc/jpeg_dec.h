@@ -216,3 +216,292 @@ JD_HD inline int jpeg_decode_segment(const uint8_t* data, long long length, cons
     for (; blk < nblk; ++blk) jd_zero_block(out + blk * 64);
   return err;
 }
+
+// ---- decoding inside a segment in parallel: subsequences ------------------------------------------------------------------------------
+// A segment is cut into subsequences at byte offsets (longlive_amd/jpeg_files.py: split_segments).  A baseline bit stream
+// self-synchronises: a decoder started at a wrong state falls into step with the true one after a short distance, so every
+// subsequence is scanned from a guess, then rescanned from its predecessor's exit until no exit changes (csrc/jpeg_dec.hip).
+//
+// State (JdState): a position and where the decoder stands in the MCU.
+//   * off, bit: raw byte offset from the segment's start in the STUFFED data and the bit inside that byte, 0 = the highest.  The
+//     position is canonical: `off` names a data byte that still holds an unread bit, or the first byte past the data, and never the
+//     00 that follows an FF.  Equal stream positions therefore give equal states, and states compare with ==.
+//   * bi: block index inside the MCU; k: the coefficient that comes next, 0 = the block's DC symbol.
+//   * JD_STATE_END: the scan consumed a bit past the segment's data (the 1-bits the reader pads with).  It is terminal.
+// An FF that no 00 follows (a marker, or the segment's last byte) ends the data there, as in jpeg_decode_segment.
+//
+// jd_sub_scan(entry, end) walks symbols (a Huffman code and its amplitude bits) from `entry` to the first symbol boundary at or past
+// the byte offset `end`, writes no coefficient and returns the exit state; *begun = the blocks that BEGIN in the subsequence (their DC
+// symbol starts before `end` and is read whole) | JD_SUB_DIRTY when it met one of the events below.
+//
+// Speculation policy: what the scan does where jpeg_decode_segment would stop with an error.  It is a function of (bytes, entry)
+// alone, and every step consumes at least one bit or ends the scan, so a scan takes at most (bits from entry to end) + 32 steps.
+//   no code in 16 bits, or a DC category above 11   the symbol's bits are put back, ONE bit is skipped, the state becomes (block 0, DC)
+//   a run (or ZRL) that would pass coefficient 63   the code is consumed, its amplitude is not; the block ends there
+//   run/size with size 0 that is not EOB or ZRL     taken as EOB
+//   an AC size above 10                             decoded as it stands (a size is at most 15 bits)
+//   a bit past the data is consumed                 the scan ends in JD_STATE_END; this is no event: the last subsequence of a valid
+//                                                   segment ends so when the padding 1-bits are read as the start of a further block
+// From a true state on valid data none of the first four can occur, so a subsequence whose final scan is dirty marks a segment that
+// the serial routine has to decode (it alone owns the JD_* code and the zero-fill).
+//
+// jd_sub_emit(entry, count) follows the same path from a final entry state: it skips what is left of the block a predecessor began,
+// then decodes `count` blocks (the scan's count), finishing the last one past the subsequence's end (a block is at most 208 bytes),
+// and stores each whole with jd_copy_block at block `first + j`, clamped into [0, nblk) before the store.  stage[0] holds the DC
+// DIFFERENCE: the running sum is a pass of its own.  Any event above, a consumed bit past the data included, ends it with a non-zero
+// JD_* code; the caller then hands the segment to jpeg_decode_segment.
+struct JdState {
+  int32_t off, pack;     // pack = bit | bi << 3 | k << 6
+};
+constexpr int32_t JD_STATE_END_OFF = 0x7fffffff;
+constexpr int32_t JD_SUB_DIRTY = 1 << 30;
+constexpr int JD_SUB_FIELDS = 3;      // segment, byte offset inside the segment, byte length
+constexpr int JD_SUB_MIN_BYTES = 7;   // a cut moved off a stuffing byte shortens the row after it by one: 8 - 1
+
+JD_HD inline bool jd_state_eq(const JdState& a, const JdState& b) { return a.off == b.off && a.pack == b.pack; }
+
+// Where BITS and HUFFVAL of the four tables lie: in the staged slice (jd_stage_tables) or in the packed tables of a frame.
+struct JdTabs {
+  const uint8_t* base;
+  int bits_stride, dc_off, dc_stride, ac_off, ac_stride;
+};
+JD_HD inline JdTabs jd_tabs_slice(const uint8_t* slice) { return JdTabs{slice, 16, 64, 16, 96, 256}; }
+JD_HD inline JdTabs jd_tabs_packed(const uint8_t* packed) {
+  return JdTabs{packed, JD_HUFF_TABLE, 16, JD_HUFF_TABLE, 16 + 2 * JD_HUFF_TABLE, JD_HUFF_TABLE};
+}
+
+// The reader of the subsequence routines: JdBits' look-ahead (eight independent byte loads at a time, a 64-bit accumulator) over
+// offsets, so that the position of the next unread bit can be told: every byte in the accumulator stands for one raw byte, or for
+// two when it is an FF (its stuffed 00 went with it).
+struct JdCur {
+  const uint8_t* seg;
+  int len, q;            // len: where the data ends; q: the next raw byte not yet in `raw`
+  uint64_t raw, acc;
+  int rn, cnt, pad;
+};
+
+JD_HD inline void jd_cur_load(JdCur& c) {
+  const int left = c.len - c.q;
+  const uint8_t* p = c.seg + c.q;
+  uint64_t w = 0;
+  if (left >= 8) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w |= (uint64_t)p[i] << (8 * i);
+    c.rn = 8;
+  } else {
+    for (int i = 0; i < left; ++i) w |= (uint64_t)p[i] << (8 * i);
+    c.rn = left;
+  }
+  c.raw = w;
+  c.q += c.rn;
+}
+
+JD_HD inline void jd_cur_fill(JdCur& c) {
+  while (c.cnt <= 56) {
+    uint32_t v = 0xFF;
+    if (c.rn == 0 && c.q < c.len) jd_cur_load(c);
+    if (c.rn > 0) {
+      v = (uint32_t)(c.raw & 0xFFu);
+      if (v == 0xFF) {
+        if (c.rn == 1 && c.q < c.len) {             // the byte after the FF is not loaded yet: load it behind the FF
+          const int at = c.q - 1;
+          c.q = at, c.rn = 0;
+          jd_cur_load(c);
+        }
+        if (c.rn > 1 && ((c.raw >> 8) & 0xFFu) == 0) {
+          c.raw >>= 16, c.rn -= 2;
+        } else {                                    // a marker, or an FF as the last byte: the data ends before it
+          c.len = c.q - c.rn, c.q = c.len, c.rn = 0;
+          c.pad += 8;
+        }
+      } else {
+        c.raw >>= 8, --c.rn;
+      }
+    } else {
+      c.pad += 8;
+    }
+    c.acc = (c.acc << 8) | v;
+    c.cnt += 8;
+  }
+}
+
+// the canonical position of the next unread bit; only asked while no padding bit has been consumed (cnt >= pad)
+JD_HD inline void jd_cur_position(const JdCur& c, int* off, int* bit) {
+  int o = c.q - c.rn;
+  const int nb = (c.cnt + 7) >> 3;
+  for (int j = c.pad >> 3; j < nb; ++j) o -= 1 + (int)(((c.acc >> (8 * j)) & 0xFFu) == 0xFFu);
+  *off = o;
+  *bit = (8 - (c.cnt & 7)) & 7;
+}
+
+// the next 16 bits, not consumed
+JD_HD inline int jd_cur_peek16(JdCur& c) {
+  if (c.cnt < 16) jd_cur_fill(c);
+  return (int)((c.acc >> (c.cnt - 16)) & 0xFFFFu);
+}
+
+// consumes n bits (0..16); false when one of them lies past the data
+JD_HD inline bool jd_cur_drop(JdCur& c, int n) {
+  if (c.cnt < n) jd_cur_fill(c);
+  c.cnt -= n;
+  return c.cnt >= c.pad;
+}
+
+// (symbol << 8) | code length of the code that heads the 16 bits v, or -1
+JD_HD inline int jd_lookup(int v, const uint8_t* bits, const uint8_t* vals, int mask) {
+  const uint32_t* bw = reinterpret_cast<const uint32_t*>(bits);
+  const uint32_t w[4] = {bw[0], bw[1], bw[2], bw[3]};
+  int first = 0, k = 0;
+#pragma unroll
+  for (int l = 0; l < 16; ++l) {
+    const int n = (int)((w[l >> 2] >> (8 * (l & 3))) & 0xFFu), code = v >> (15 - l);
+    if (code - first < n) return ((int)vals[(k + code - first) & mask] << 8) | (l + 1);
+    k += n;
+    first = (first + n) << 1;
+  }
+  return -1;
+}
+
+// The one walk that jd_sub_scan and jd_sub_emit share, so that both follow the same path by construction.
+template <bool EMIT>
+JD_HD inline int jd_sub_walk(const uint8_t* seg, int seglen, const JdTabs& tb, uint32_t sel, int bpm, int end, JdState in, JdState* exit,
+                             int32_t* begun, int count, long long first, long long nblk, int16_t* stage, int16_t* out) {
+  const int ny = bpm == 1 ? 1 : bpm - 2;
+  int bi = (in.pack >> 3) & 7, k = (in.pack >> 6) & 63, nbegun = 0, dirty = 0, stored = 0;
+  bool storing = k == 0;
+  if (bi >= bpm) bi = 0;
+  if (!EMIT) {
+    *begun = 0;
+    *exit = in;
+    if (in.off >= end) return JD_OK;                // the predecessor's last symbol passed this subsequence whole (JD_STATE_END too)
+  } else if (count <= 0) {
+    return JD_OK;
+  }
+  if (in.off < 0 || in.off > seglen) return JD_OVERRUN;      // no state of this segment: nothing is read
+  JdCur c{seg, seglen, in.off, 0ull, 0ull, 0, 0, 0};
+  if (!jd_cur_drop(c, in.pack & 7)) {
+    if (!EMIT) *exit = JdState{JD_STATE_END_OFF, 0};
+    return JD_OVERRUN;
+  }
+  for (;;) {
+    if (!EMIT) {                                    // a symbol boundary: at or past the end?
+      const int nb = (c.cnt + 7) >> 3;
+      if (c.q - c.rn - nb + (c.pad >> 3) >= end) {
+        int off, bit;
+        jd_cur_position(c, &off, &bit);
+        if (off >= end) {
+          *exit = JdState{off, bit | (bi << 3) | (k << 6)};
+          break;
+        }
+      }
+    } else if (k == 0 && storing && stored >= count) {
+      break;
+    }
+    const int comp = bi < ny ? 0 : bi - ny + 1;
+    const uint32_t s8 = (sel >> (8 * comp)) & 0xFFu;
+    const int td = (int)(s8 & 1u), ta = (int)((s8 >> 4) & 1u);
+    int code = 0;                                   // the JD_* event of this step, 0 = none
+    bool over = false, endblk = false, resync = false;
+    if (k == 0) {
+      const int sl = jd_lookup(jd_cur_peek16(c), tb.base + td * tb.bits_stride, tb.base + tb.dc_off + td * tb.dc_stride, 15);
+      const int s = sl >> 8;
+      if (sl < 0) {
+        if (c.cnt - c.pad < 16) over = true;
+        else code = JD_BAD_CODE, resync = true;
+      } else if (c.cnt - c.pad < (sl & 255)) {
+        over = true;
+      } else if (s > 11) {
+        code = JD_DC_CATEGORY, resync = true;
+      } else {
+        jd_cur_drop(c, sl & 255);
+        int diff = 0;
+        if (s > 0) {
+          const int v = jd_cur_peek16(c) >> (16 - s);
+          if (!jd_cur_drop(c, s)) over = true;
+          diff = jd_extend(v, s);
+        }
+        if (!over) {
+          ++nbegun;
+          if (EMIT && storing) {
+            jd_zero_block(stage);
+            stage[0] = (int16_t)diff;
+          }
+          k = 1;
+        }
+      }
+    } else {
+      const int sl = jd_lookup(jd_cur_peek16(c), tb.base + (2 + ta) * tb.bits_stride, tb.base + tb.ac_off + ta * tb.ac_stride, 255);
+      if (sl < 0) {
+        if (c.cnt - c.pad < 16) over = true;
+        else code = JD_BAD_CODE, resync = true;
+      } else if (!jd_cur_drop(c, sl & 255)) {
+        over = true;
+      } else {
+        const int rs = sl >> 8, r = rs >> 4, s = rs & 15;
+        if (s == 0) {
+          if (r == 0) endblk = true;                // EOB
+          else if (r != 15) code = JD_AC_SIZE, endblk = true;
+          else if (k + 16 > 64) code = JD_COEF_INDEX, endblk = true;
+          else k += 16;                             // ZRL
+        } else {
+          if (s > 10) code = JD_AC_SIZE;
+          if (k + r > 63) {
+            if (!code) code = JD_COEF_INDEX;
+            endblk = true;
+          } else {
+            const int v = jd_cur_peek16(c) >> (16 - s);
+            if (!jd_cur_drop(c, s)) over = true;
+            else {
+              k += r;
+              if (EMIT && storing) stage[k] = (int16_t)jd_extend(v, s);
+              ++k;
+            }
+          }
+        }
+        if (k >= 64) endblk = true;
+      }
+    }
+    if (over) {
+      if (!EMIT) *exit = JdState{JD_STATE_END_OFF, 0};
+      if (EMIT) return JD_OVERRUN;
+      break;
+    }
+    if (code) {
+      if (EMIT) return code;
+      dirty = JD_SUB_DIRTY;
+    }
+    if (resync) {
+      jd_cur_drop(c, 1);                            // at least 16 bits of data lie ahead: this cannot pass the end
+      bi = 0, k = 0;
+      storing = true;
+    } else if (endblk) {
+      if (EMIT) {
+        if (storing) {
+          long long b = first + stored;
+          b = b < 0 ? 0 : (b > nblk - 1 ? nblk - 1 : b);
+          jd_copy_block(out + b * 64, stage);
+          ++stored;
+        }
+        storing = true;
+      }
+      bi = bi + 1 == bpm ? 0 : bi + 1;
+      k = 0;
+    }
+  }
+  if (!EMIT) *begun = nbegun | dirty;
+  return JD_OK;
+}
+
+JD_HD inline JdState jd_sub_scan(const uint8_t* seg, int seglen, const JdTabs& tb, uint32_t sel, int bpm, int end, JdState in,
+                                 int32_t* begun) {
+  JdState exit;
+  jd_sub_walk<false>(seg, seglen, tb, sel, bpm, end, in, &exit, begun, 0, 0, 0, nullptr, nullptr);
+  return exit;
+}
+
+// out: the segment's first block; first: the index (inside the segment) of the first block that begins in this subsequence
+JD_HD inline int jd_sub_emit(const uint8_t* seg, int seglen, const JdTabs& tb, uint32_t sel, int bpm, JdState in, int count,
+                             long long first, long long nblk, int16_t* stage, int16_t* out) {
+  if (nblk < 1) return JD_OK;
+  return jd_sub_walk<true>(seg, seglen, tb, sel, bpm, 0, in, nullptr, nullptr, count, first, nblk, stage, out);
+}

@@ -238,6 +238,30 @@ class PackedJpegs:
         return mcu_grid(self.height, self.width, self.components, self.hs, self.vs)
 
 
+def split_segments(pk: PackedJpegs, sub_bytes: int) -> np.ndarray:
+    """The split table of csrc/jpeg_dec.hip's parallel entropy route: int32 [nsub, 3] = (segment, byte offset inside the segment,
+    byte length).  Every segment of at least 4 * sub_bytes is cut at the multiples of sub_bytes from its start (the last row takes
+    the remainder, so it is shorter than 2 * sub_bytes); a cut that lands on a stuffing 00 (the byte before it is FF) moves one byte
+    on, so no row starts on one.  Shorter segments get no rows: they decode serially.  sub_bytes: a multiple of 4, at least 8 (a
+    symbol with its amplitude is at most 26 bits, so every row holds a symbol boundary)."""
+    if isinstance(sub_bytes, bool) or not isinstance(sub_bytes, (int, np.integer)) or sub_bytes < 8 or sub_bytes % 4:
+        raise ValueError(f"split_segments: sub_bytes={sub_bytes!r} must be a multiple of 4, at least 8")
+    sub = int(sub_bytes)
+    lens = pk.segs[:, 1].astype(np.int64)
+    n = np.where(lens >= 4 * sub, lens // sub, 0)
+    total = int(n.sum())
+    if total == 0:
+        return np.zeros((0, 3), dtype=np.int32)
+    seg = np.repeat(np.arange(len(n), dtype=np.int64), n)
+    j = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+    at = pk.segs[seg, 0].astype(np.int64) + j * sub
+    off = j * sub + ((j > 0) & (pk.data[at] == 0) & (pk.data[np.maximum(at - 1, 0)] == 0xFF))
+    end = np.append(off[1:], 0)
+    last = j == n[seg] - 1
+    end[last] = lens[seg][last]
+    return np.stack([seg, off, end - off], 1).astype(np.int32)
+
+
 def pack_jpegs(files: Sequence[bytes]) -> PackedJpegs:
     if len(files) < 1:
         raise ValueError("pack_jpegs: no frames")

@@ -784,16 +784,53 @@ def jpeg_coefficients(frames, quality: int = 90):
 
 
 # ---- clip intake: baseline JPEG decoder, antialiased resize ------------------------------------------------------------
-def jpeg_decode_sizes(T: int, H: int, W: int, components: int, hs: int, vs: int):
-    """(coef_bytes, scratch_bytes) of ll_jpeg_decode_u8 (host only)."""
+# split="auto" (profiles/clip_intake.md): 1024 bytes per subsequence, so only segments of 4 KiB and more are
+# cut, and only in a clip of fewer than 1024 segments: the split route decodes every byte about three times (pass 0, the rescan, the
+# emit), which pays when a clip offers a few dozen lanes (81 no-DRI frames: 7.8 times faster) and loses when its restart intervals
+# already fill the device (2430 segments: the serial route is 1.8 to 3.7 times faster).  Between 81 and 2430 nothing is measured;
+# 1024 segments are four one-lane waves per CU.  12 rounds: the longest settle round measured at 256 bytes and more is 7.
+JPEG_SPLIT_AUTO = 1024
+JPEG_SPLIT_AUTO_SEGMENTS = 1024
+JPEG_SPLIT_ROUNDS = 12
+
+
+def jpeg_decode_sizes(T: int, H: int, W: int, components: int, hs: int, vs: int, split=None, rounds=None):
+    """(coef_bytes, scratch_bytes) of ll_jpeg_decode_u8 (host only); with split=(segments, subsequences), the shape of the split table,
+    also the work bytes of ll_jpeg_decode_u8_split: (coef_bytes, scratch_bytes, work_bytes).  `rounds` is checked, it changes no size."""
     import ctypes
     a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
     _lib.check(_lib.load().ll_jpeg_decode_sizes(T, H, W, components, hs, vs, ctypes.byref(a), ctypes.byref(b)), "ll_jpeg_decode_sizes")
-    return int(a.value), int(b.value)
+    if split is None:
+        return int(a.value), int(b.value)
+    _jpeg_rounds(rounds)
+    c = ctypes.c_longlong(0)
+    _lib.check(_lib.load().ll_jpeg_decode_split_sizes(int(split[0]), int(split[1]), ctypes.byref(c)), "ll_jpeg_decode_split_sizes")
+    return int(a.value), int(b.value), int(c.value)
 
 
-def _jpeg_upload(files, device):
-    """pack_jpegs(files) and its arrays on the device, sent as ONE buffer: (packed, {name: device view})."""
+def _jpeg_rounds(rounds) -> int:
+    if rounds is None:
+        return JPEG_SPLIT_ROUNDS
+    if isinstance(rounds, bool) or not isinstance(rounds, int) or not 1 <= rounds <= 64:
+        raise ValueError(f"rounds: {rounds!r} must be an integer 1..64")
+    return rounds
+
+
+def _jpeg_split_bytes(split):
+    """split=None -> None (the serial route), "auto" -> JPEG_SPLIT_AUTO, an int -> that many bytes per subsequence."""
+    if split is None:
+        return None
+    if isinstance(split, str) and split.strip().lower() == "auto":
+        return JPEG_SPLIT_AUTO
+    if isinstance(split, bool) or not isinstance(split, int) or split < 8 or split % 4:
+        raise ValueError(f"split: {split!r} must be None, 'auto' or a multiple of 4 bytes, at least 8")
+    return split
+
+
+def _jpeg_upload(files, device, split=None, auto=False):
+    """pack_jpegs(files) and its arrays on the device, sent as ONE buffer: (packed, {name: device view}); with `split` (bytes per
+    subsequence) the split table goes along as "subs" (absent when no segment is long enough to be cut, and under `auto` when the
+    clip has JPEG_SPLIT_AUTO_SEGMENTS segments or more)."""
     import numpy as np
     from . import jpeg_files
     if device is None:
@@ -802,6 +839,10 @@ def _jpeg_upload(files, device):
         raise RuntimeError("jpeg_decode: expected a device (longlive_amd has no CPU path)")
     pk = jpeg_files.pack_jpegs(files)
     parts = {"segs": pk.segs, "qt": pk.qt, "huff": pk.huff, "sel": pk.sel, "data": pk.data}
+    if split is not None and not (auto and pk.segs.shape[0] >= JPEG_SPLIT_AUTO_SEGMENTS):
+        subs = jpeg_files.split_segments(pk, split)
+        if subs.shape[0]:
+            parts["subs"] = subs
     offs, n = {}, 0
     for k, a in parts.items():
         offs[k] = n
@@ -833,32 +874,85 @@ def _jpeg_coef_out(pk, device, coef):
     return coef
 
 
-def jpeg_decode_coefficients(files, device=None, out=None, check: bool = True):
+def _jpeg_split_args(pk, d, device, rounds, info, work):
+    """(status, info, the split entry points' trailing arguments or None when the clip has no subsequence).  Without an `info` of the
+    caller's, status and info are the two rows of one tensor, so that `check` reads both back in one copy."""
+    nseg = pk.segs.shape[0]
+    if info is None:
+        both = torch.zeros(2, nseg, dtype=torch.int32, device=device)
+        status, info = both[0], both[1]
+    else:
+        assert info.is_cuda and info.dtype == torch.int32 and info.shape == (nseg,) and info.is_contiguous(), \
+            f"info: expected a contiguous int32 device tensor [{nseg}]"
+        status = torch.empty(nseg, dtype=torch.int32, device=device)
+    if "subs" not in d:                                 # every segment is too short to cut: the serial route, info 0 throughout
+        info.zero_()
+        return status, info, None
+    nsub = d["subs"].numel() // 12
+    work_bytes = jpeg_decode_sizes(pk.frames, pk.height, pk.width, pk.components, pk.hs, pk.vs, split=(nseg, nsub), rounds=rounds)[2]
+    if work is None:
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=device)
+    assert work.is_cuda and work.dtype == torch.uint8 and work.numel() >= work_bytes and work.is_contiguous()
+    return status, info, (d["subs"].data_ptr(), nsub, rounds, info.data_ptr(), work.data_ptr(), work.numel())
+
+
+def _jpeg_checked(status, info, pk):
+    """One read-back of status and info where they share a tensor."""
+    if status._base is not None and status._base is info._base:
+        host = status._base.cpu()
+        _jpeg_status(host[0], pk)
+    else:
+        _jpeg_status(status, pk)
+
+
+def jpeg_decode_coefficients(files, device=None, out=None, check: bool = True, split=None, rounds=None, return_info: bool = False,
+                             info=None, work=None):
     """Baseline JPEG files (bytes, same size and sampling) -> int16 [T, rows, cols, bpm, 64] on the device: the entropy stage alone, in
     zigzag order, blocks in scan order (for 4:2:0 the layout of jpeg_coefficients).  `check` reads the segments' status back once and
-    raises ValueError naming the frames whose data is malformed."""
-    pk, d = _jpeg_upload(files, device)
+    raises ValueError naming the frames whose data is malformed.  split / rounds / return_info / info / work: as in jpeg_decode."""
+    sub = _jpeg_split_bytes(split)
+    pk, d = _jpeg_upload(files, device, sub, auto=isinstance(split, str))
     coef = _jpeg_coef_out(pk, d["data"].device, out)
-    status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=coef.device)
-    _lib.check(_lib.load().ll_jpeg_decode_coefficients(d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0],
-                                                       d["huff"].data_ptr(), d["sel"].data_ptr(), pk.frames, pk.height, pk.width,
-                                                       pk.components, pk.hs, pk.vs, coef.data_ptr(), status.data_ptr(), _stream()),
-               "ll_jpeg_decode_coefficients")
+    head = (d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0], d["huff"].data_ptr(), d["sel"].data_ptr(),
+            pk.frames, pk.height, pk.width, pk.components, pk.hs, pk.vs, coef.data_ptr())
+    if sub is None:
+        if return_info or info is not None or work is not None:
+            raise ValueError("return_info, info and work belong to the split route: pass split=")
+        status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=coef.device)
+        _lib.check(_lib.load().ll_jpeg_decode_coefficients(*head, status.data_ptr(), _stream()), "ll_jpeg_decode_coefficients")
+        if check:
+            _jpeg_status(status, pk)
+        return coef
+    status, info, tail = _jpeg_split_args(pk, d, coef.device, _jpeg_rounds(rounds), info, work)
+    if tail is None:
+        _lib.check(_lib.load().ll_jpeg_decode_coefficients(*head, status.data_ptr(), _stream()), "ll_jpeg_decode_coefficients")
+    else:
+        _lib.check(_lib.load().ll_jpeg_decode_coefficients_split(*head, status.data_ptr(), *tail, _stream()),
+                   "ll_jpeg_decode_coefficients_split")
     if check:
-        _jpeg_status(status, pk)
-    return coef
+        _jpeg_checked(status, info, pk)
+    return (coef, info) if return_info else coef
 
 
-def jpeg_decode(files, device=None, check: bool = True, out=None, scratch=None):
+def jpeg_decode(files, device=None, check: bool = True, out=None, scratch=None, split=None, rounds=None, return_info: bool = False,
+                info=None):
     """Baseline JPEG files (bytes; grey, 4:4:4, 4:2:2 or 4:2:0, all of one size and sampling) -> uint8 [T, H, W, 3] RGB on the device.
     One host-to-device copy of the packed bytes and tables, three launches.  `check` reads the segments' status back once and raises
     ValueError naming the frames whose entropy data is malformed.  `out`: a uint8 [T, H, W, 3] view with contiguous frames (any
-    frame stride); `scratch`: (coef int16, planes uint8) to decode into, any content."""
-    pk, d = _jpeg_upload(files, device)
+    frame stride); `scratch`: (coef int16, planes uint8) to decode into, any content.
+
+    split: None = one lane per restart segment, as ever; an int = the entropy stage decodes subsequences of that many bytes side by
+    side (csrc/jpeg_dec.hip's split route: the same coefficients and status, bit for bit; rounds + 6 launches in its place);
+    "auto" = JPEG_SPLIT_AUTO bytes where the clip has fewer than JPEG_SPLIT_AUTO_SEGMENTS segments, else the serial route.  rounds (default JPEG_SPLIT_ROUNDS): resynchronisation rounds; a segment that needs more is
+    decoded serially.  The split table rides in the same one copy, `check` still reads back once (status and info together), and
+    return_info=True returns (frames, info): per segment 0 = serial by table, r >= 1 = settled in round r, -1 / -2 = fell back
+    unsettled / flagged.  `info`: an int32 [segments] tensor to write it to; `scratch` may carry the work buffer as a third entry."""
+    sub = _jpeg_split_bytes(split)
+    pk, d = _jpeg_upload(files, device, sub, auto=isinstance(split, str))
     device = d["data"].device
     T, H, W = pk.frames, pk.height, pk.width
     coef_bytes, scratch_bytes = jpeg_decode_sizes(T, H, W, pk.components, pk.hs, pk.vs)
-    coef, planes = scratch if scratch is not None else (None, None)
+    coef, planes, work = (tuple(scratch) + (None,))[:3] if scratch is not None else (None, None, None)
     coef = _jpeg_coef_out(pk, device, coef)
     if planes is None:
         planes = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
@@ -870,14 +964,25 @@ def jpeg_decode(files, device=None, check: bool = True, out=None, scratch=None):
     assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
         f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
     stride_t = out.stride(0) if T > 1 else 3 * H * W
-    status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=device)
-    _lib.check(_lib.load().ll_jpeg_decode_u8(d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0],
-                                             d["huff"].data_ptr(), d["sel"].data_ptr(), d["qt"].data_ptr(), T, H, W, pk.components, pk.hs,
-                                             pk.vs, coef.data_ptr(), status.data_ptr(), out.data_ptr(), stride_t, planes.data_ptr(),
-                                             planes.numel(), _stream()), "ll_jpeg_decode_u8")
+    head = (d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0], d["huff"].data_ptr(), d["sel"].data_ptr(),
+            d["qt"].data_ptr(), T, H, W, pk.components, pk.hs, pk.vs, coef.data_ptr())
+    mid = (out.data_ptr(), stride_t, planes.data_ptr(), planes.numel())
+    if sub is None:
+        if return_info or info is not None or work is not None:
+            raise ValueError("return_info, info and a work buffer belong to the split route: pass split=")
+        status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=device)
+        _lib.check(_lib.load().ll_jpeg_decode_u8(*head, status.data_ptr(), *mid, _stream()), "ll_jpeg_decode_u8")
+        if check:
+            _jpeg_status(status, pk)
+        return out
+    status, info, tail = _jpeg_split_args(pk, d, device, _jpeg_rounds(rounds), info, work)
+    if tail is None:
+        _lib.check(_lib.load().ll_jpeg_decode_u8(*head, status.data_ptr(), *mid, _stream()), "ll_jpeg_decode_u8")
+    else:
+        _lib.check(_lib.load().ll_jpeg_decode_u8_split(*head, status.data_ptr(), *mid, *tail, _stream()), "ll_jpeg_decode_u8_split")
     if check:
-        _jpeg_status(status, pk)
-    return out
+        _jpeg_checked(status, info, pk)
+    return (out, info) if return_info else out
 
 
 def resize_taps(n_in: int, n_out: int):

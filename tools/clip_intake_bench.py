@@ -2,7 +2,10 @@
 """Clip intake on the GPU, measured: decode time per frame of ops.jpeg_decode for a clip of this project's own files (one restart
 interval per MCU row: 30 lanes per 480 x 832 frame) and for Pillow-made files of the same frames without restart markers (one lane per
 frame), the entropy launch and the two pixel launches separately (device events around ll_jpeg_decode_coefficients and
-ll_jpeg_decode_pixels), the resize of 1080p frames to 480p, and Pillow's host decode of the same files on the same machine.
+ll_jpeg_decode_pixels), the resize of 1080p frames to 480p, and Pillow's host decode of the same files on the same machine.  The
+entropy stage is also measured as an A/B ("entropy_ab"): the serial route against the split route (subsequences of a segment side by
+side) at 128 / 256 / 512 / 1024 bytes and at 64 and 1 lanes per wave, alternating in one loop, with the share of segments per `info`
+value and the highest settle round.
 
     python tools/clip_intake_bench.py [--frames 81] [--reps 5] [--out profiles/clip_intake.json]
 
@@ -94,6 +97,86 @@ def decode_figures(files, reps: int, device) -> dict:
             "jpeg_decode_call_ms_per_frame": call_ms / T}, out
 
 
+SPLIT_SIZES = (128, 256, 512, 1024)
+SPLIT_LANES = (64, 1)
+
+
+def event_ms(fn) -> float:
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def split_figures(files, reps: int, rounds: int, device) -> dict:
+    """The entropy stage alone, A/B in one loop on one device: per repetition the serial route (the parent's, one lane per restart
+    segment), then the split route at every subsequence size and lane count per wave, each timed by device events; medians over the
+    repetitions.  Per size also the share of segments per `info` value and the highest settle round."""
+    T = len(files)
+    pk, d = ops._jpeg_upload(files, device)
+    geo = (T, pk.height, pk.width, pk.components, pk.hs, pk.vs)
+    nseg = pk.segs.shape[0]
+    coef_bytes = ops.jpeg_decode_sizes(*geo)[0]
+    ref = torch.empty(coef_bytes // 2, dtype=torch.int16, device=device)
+    coef = torch.empty_like(ref)
+    status = torch.empty(nseg, dtype=torch.int32, device=device)
+    info = torch.empty(nseg, dtype=torch.int32, device=device)
+    lib, s = _lib.load(), ops._stream()
+    head = (d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), nseg, d["huff"].data_ptr(), d["sel"].data_ptr(), *geo)
+
+    def serial():
+        _lib.check(lib.ll_jpeg_decode_coefficients(*head, ref.data_ptr(), status.data_ptr(), s), "ll_jpeg_decode_coefficients")
+
+    tables, empty = {}, []
+    for sub in SPLIT_SIZES:
+        rows = jpeg_files.split_segments(pk, sub)
+        if rows.shape[0] == 0:                             # no segment reaches 4 * sub bytes: the call is the serial route's
+            empty.append(sub)
+        else:
+            work_bytes = ops.jpeg_decode_sizes(*geo, split=(nseg, rows.shape[0]), rounds=rounds)[2]
+            tables[sub] = (torch.from_numpy(rows).to(device), rows.shape[0], torch.empty(work_bytes, dtype=torch.uint8, device=device))
+
+    def split(sub, lanes):
+        subs, nsub, work = tables[sub]
+        _lib.check(lib.ll_set_tuning(b"jpeg_split_lanes", lanes), "ll_set_tuning")
+        _lib.check(lib.ll_jpeg_decode_coefficients_split(*head, coef.data_ptr(), status.data_ptr(), subs.data_ptr(), nsub, rounds,
+                                                         info.data_ptr(), work.data_ptr(), work.numel(), s),
+                   "ll_jpeg_decode_coefficients_split")
+
+    res = {"frames": T, "segments": nseg, "rounds": rounds, "bytes_per_frame": sum(len(f) for f in files) // T,
+           "longest_segment_bytes": int(pk.segs[:, 1].max()), "sizes_without_rows": empty, "split": {}}
+    serial()
+    torch.cuda.synchronize()
+    for sub in tables:
+        shares = None
+        for lanes in SPLIT_LANES:
+            coef.fill_(0x7FFF)
+            split(sub, lanes)
+            torch.cuda.synchronize()
+            assert torch.equal(coef, ref) and int(status.abs().max()) == 0, (sub, lanes)
+            host = info.cpu()
+            shares = {"serial_by_table": float((host == 0).float().mean()), "settled": float((host >= 1).float().mean()),
+                      "unsettled": float((host == -1).float().mean()), "flagged": float((host == -2).float().mean()),
+                      "highest_settle_round": int(host.max())}
+        res["split"][str(sub)] = {"subsequences": tables[sub][1], **shares}
+    times = {"serial": []}
+    for _ in range(reps):
+        times["serial"].append(event_ms(serial))
+        for sub in tables:
+            for lanes in SPLIT_LANES:
+                times.setdefault((sub, lanes), []).append(event_ms(lambda: split(sub, lanes)))
+    _lib.check(lib.ll_set_tuning(b"jpeg_split_lanes", 0), "ll_set_tuning")
+    res["serial_entropy_ms_per_frame"] = statistics.median(times["serial"]) / T
+    for sub in tables:
+        for lanes in SPLIT_LANES:
+            ms = statistics.median(times[(sub, lanes)]) / T
+            res["split"][str(sub)][f"entropy_ms_per_frame_lanes{lanes}"] = ms
+            res["split"][str(sub)][f"serial_over_split_lanes{lanes}"] = res["serial_entropy_ms_per_frame"] / ms
+    return res
+
+
 def pil_decode_ms(files) -> float:
     from PIL import Image
     import numpy as np
@@ -108,6 +191,7 @@ def main(argv=None) -> int:
     ap.add_argument("--frames", type=int, default=81)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--rounds", type=str, default=str(ops.JPEG_SPLIT_ROUNDS), help="rounds of the split route's A/B, comma-separated")
     ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -120,6 +204,8 @@ def main(argv=None) -> int:
     tel = Telemetry(0)
     tel.start()
     res["own_files"], dec = decode_figures(own, args.reps, device)
+    rounds = [int(r) for r in args.rounds.split(",")]
+    res["entropy_ab"] = {"own_files": {str(r): split_figures(own, args.reps, r, device) for r in rounds}}
     try:
         from PIL import Image
         import numpy as np
@@ -130,6 +216,7 @@ def main(argv=None) -> int:
             Image.fromarray(host[t]).save(b, "JPEG", quality=args.quality, subsampling=2)
             pil.append(b.getvalue())
         res["pillow_files"], dec_pil = decode_figures(pil, args.reps, device)
+        res["entropy_ab"]["pillow_files"] = {str(r): split_figures(pil, args.reps, r, device) for r in rounds}
         res["pillow_host_decode_ms_per_frame"] = {"own_files": pil_decode_ms(own), "pillow_files": pil_decode_ms(pil)}
         ref = torch.from_numpy(np.stack([np.array(Image.open(io.BytesIO(f)).convert("RGB")) for f in pil[:4]]))
         res["pillow_files"]["max_abs_difference_from_pillows_decoder"] = int((dec_pil[:4].cpu().int() - ref.int()).abs().max())
