@@ -36,76 +36,91 @@ VAE_STD = [2.8184, 1.4541, 2.3275, 2.6558, 1.2196, 1.7708, 2.6052, 2.0743, 3.268
            1.1253, 2.8251, 1.9160]
 
 
-class _Conv:
-    """One convolution: packed weights + (for temporal kernels) its input buffer [2 + T, H, W, Cin], whose first two frames
-    are the stream's previous two input frames -- the reference's feat_cache (vae.py:29-34, 207-216) -- kept in the layout
-    the kernel reads, so the history costs one 2-frame copy per call and no concatenation."""
+class _Staged:
+    """A convolution's input where its kernel reads it: `buf` [hist + T, H, W, Cin] -- the stream's previous `hist` input frames, then
+    the T new ones -- and `new` = buf[hist:], where a producer writes them.  Made by the convolution (input / stage), held by the
+    caller, handed back to the convolution's call."""
+    __slots__ = ("buf", "new")
 
-    def __init__(self, w: torch.Tensor, b: torch.Tensor):
+    def __init__(self, buf: torch.Tensor, hist: int):
+        self.buf, self.new = buf, buf[hist:]
+
+
+class _Conv:
+    """One convolution: packed weights + (for temporal kernels, hist = 2) a view of the last two input frames it has read -- the
+    reference's feat_cache (vae.py:29-34, 207-216) -- kept in the layout the kernel reads, so the history costs one 2-frame copy
+    per call and no concatenation.  The view keeps the buffer it lies in alive until the next call."""
+
+    def __init__(self, w: torch.Tensor, b: torch.Tensor, fuse_rms: bool = True):
         self.w, self.b, self.geo = ops.pack_conv_weight(w, b)
-        self.temporal = self.geo[3] > 1
-        self._hist: Optional[torch.Tensor] = None       # view of the last two input frames seen so far
-        self._buf: Optional[torch.Tensor] = None
+        self.hist = 2 if self.geo[3] > 1 else 0
+        self.fuse_rms = fuse_rms
+        self._hist: Optional[torch.Tensor] = None
 
     def reset(self):
         self._hist = None
-        self._buf = None
 
-    def input(self, T: int, H: int, W: int, device) -> torch.Tensor:
-        """Where the producer should write this convolution's T input frames."""
-        cin = self.geo[0]
-        if not self.temporal:
-            return torch.empty(T, H, W, cin, dtype=bf16, device=device)
-        buf = torch.empty(2 + T, H, W, cin, dtype=bf16, device=device)
-        if self._hist is None:
-            buf[:2].zero_()
-        else:
-            buf[:2].copy_(self._hist)
-        self._buf = buf
-        return buf[2:]
+    def input(self, T: int, H: int, W: int, device) -> _Staged:
+        """Room for T input frames behind the history (zeros at the start of a stream)."""
+        buf = torch.empty(self.hist + T, H, W, self.geo[0], dtype=bf16, device=device)
+        if self.hist:
+            if self._hist is None:
+                buf[:self.hist].zero_()
+            else:
+                buf[:self.hist].copy_(self._hist)
+        return _Staged(buf, self.hist)
 
-    def __call__(self, x: torch.Tensor, upsample: bool = False, res: Optional[torch.Tensor] = None, rms=None,
+    def stage(self, x: torch.Tensor) -> _Staged:
+        """An input that already exists as a tensor: copied behind the history -- or, with no history to put in front of it, read
+        where it lies."""
+        if not self.hist:
+            return _Staged(x, 0)
+        s = self.input(x.shape[0], x.shape[1], x.shape[2], x.device)
+        s.new.copy_(x)
+        return s
+
+    def __call__(self, s: _Staged, upsample: bool = False, res: Optional[torch.Tensor] = None, rms=None,
                  want_raw: bool = True) -> torch.Tensor:
-        """rms = (gamma, out_rms): the convolution's epilogue also writes rms_silu(result) into out_rms (the next convolution's input
-        buffer) -- one launch instead of two where ops.conv_cl_rms_ok says so, else the two launches; want_raw = False: the
-        un-normalised result is not needed (None is returned when the fused kernel ran)."""
-        if not self.temporal:
-            buf = x
+        """rms = (gamma, staged): rms_silu(result) is written into staged.new (the next convolution's input) as well -- by this
+        convolution's epilogue, one launch instead of two, where fusing is on and ops.conv_cl_rms_ok says so, else by the two launches;
+        want_raw = False: the un-normalised result is not needed (None is returned when the fused kernel ran)."""
+        H, W = s.new.shape[1:3]
+        if rms is not None and self.fuse_rms and ops.conv_cl_rms_ok(self.geo, H, W, upsample):
+            y = ops.conv_cl_rms(s.buf, self.w, self.b, self.geo, rms[0], rms[1].new, upsample=upsample, res=res, want_raw=want_raw)
         else:
-            if self._buf is None or x.data_ptr() != self._buf[2:].data_ptr():
-                self.input(x.shape[0], x.shape[1], x.shape[2], x.device).copy_(x)     # producer did not write in place
-            buf, self._buf = self._buf, None
-        if rms is not None and ops.conv_cl_rms_ok(self.geo, x.shape[1], x.shape[2], upsample):
-            y = ops.conv_cl_rms(buf, self.w, self.b, self.geo, rms[0], rms[1], upsample=upsample, res=res, want_raw=want_raw)
-        else:
-            y = ops.conv_cl(buf, self.w, self.b, self.geo, upsample=upsample, res=res)
+            y = ops.conv_cl(s.buf, self.w, self.b, self.geo, upsample=upsample, res=res)
             if rms is not None:
-                ops.rms_silu_cl(y, rms[0], out=rms[1])
-        if self.temporal:
-            self._hist = buf[-2:]
+                ops.rms_silu_cl(y, rms[0], out=rms[1].new)
+        if self.hist:
+            self._hist = s.buf[-self.hist:]
         return y
 
 
-class _TDownConv:
-    """The time_conv of Resample 'downsample3d' (vae.py:95-96): packed weights + its input buffer [1 + T, H, W, C] whose first frame is
-    the stream's previous input frame -- feat_cache[idx][:, :, -1:] (vae.py:151-158) -- so the spatial down-convolution writes its
-    result straight behind the history.  `last` is None until the first chunk has been seen (whose time_conv is skipped, vae.py:146-148)."""
+class _TDownConv(_Conv):
+    """The time_conv of Resample 'downsample3d' (vae.py:95-96): ONE history frame -- feat_cache[idx][:, :, -1:] (vae.py:151-158) -- in
+    front of its input, so the spatial down-convolution writes its result straight behind it.  The stream's first chunk does not
+    run it (vae.py:146-148): `skip` takes that chunk instead, and until then there is no input to ask for."""
 
     def __init__(self, w: torch.Tensor, b: torch.Tensor):
-        self.w, self.b, self.geo = ops.pack_conv_weight(w, b)
-        self.last: Optional[torch.Tensor] = None
+        super().__init__(w, b)
+        self.hist = 1
 
-    def reset(self):
-        self.last = None
+    @property
+    def started(self) -> bool:
+        return self._hist is not None
 
-    def input(self, T: int, H: int, W: int, device) -> torch.Tensor:
-        buf = torch.empty(1 + T, H, W, self.geo[0], dtype=bf16, device=device)
-        buf[:1].copy_(self.last)
-        return buf
+    def skip(self, y: torch.Tensor) -> torch.Tensor:
+        self._hist = y[-1:]                         # feat_cache[idx] = x.clone(); time_conv skipped (vae.py:146-148)
+        return y
 
-    def __call__(self, buf: torch.Tensor) -> torch.Tensor:
-        y = ops.conv_cl_tdown(buf, self.w, self.b, self.geo)
-        self.last = buf[-1:]
+    def input(self, T: int, H: int, W: int, device) -> _Staged:
+        if self._hist is None:
+            raise RuntimeError("time_conv: its input was asked for before the stream's first chunk (which skips it) was seen")
+        return super().input(T, H, W, device)
+
+    def __call__(self, s: _Staged) -> torch.Tensor:
+        y = ops.conv_cl_tdown(s.buf, self.w, self.b, self.geo)
+        self._hist = s.buf[-1:]
         return y
 
 
@@ -116,8 +131,9 @@ class _VaeHalfHIP(nn.Module):
     _foreign: tuple = ()               # key prefixes of the other half of a WanVAE_ state dict: ignored by a strict load
     _head: tuple = ("", "")            # names of the head's RMS_norm gamma and convolution
 
-    def _init_half(self, cfg: Optional[VaeConfig], layout, shapes, device):
-        self.fuse_rms = os.environ.get("LL_VAE_FUSE", "1") != "0"      # kernel A/B only: 0 = RMS_norm + SiLU as their own launches
+    def _init_half(self, cfg: Optional[VaeConfig], layout, shapes, device, fuse_rms: Optional[bool]):
+        # kernel A/B only: LL_VAE_FUSE=0 (fuse_rms=False) = RMS_norm + SiLU as their own launches
+        self.fuse_rms = os.environ.get("LL_VAE_FUSE", "1") != "0" if fuse_rms is None else bool(fuse_rms)
         self.cfg = cfg or VaeConfig()
         self.dims, self.layers = layout(self.cfg)
         self._names: Dict[str, str] = {}
@@ -177,7 +193,7 @@ class _VaeHalfHIP(nn.Module):
         self._packed = True
 
     def _make_conv(self, name: str, w: torch.Tensor, b: torch.Tensor):
-        return _Conv(w, b)
+        return _Conv(w, b, self.fuse_rms)
 
     # -- streaming state -------------------------------------------------------------------------------------------
     def clear_cache(self):
@@ -187,25 +203,35 @@ class _VaeHalfHIP(nn.Module):
         self._first = True
 
     # -- blocks ----------------------------------------------------------------------------------------------------
-    def _res_block(self, x, name, pre: bool = False, nxt=None):           # ResidualBlock.forward (vae.py:202-220)
-        """pre: the producer of x already wrote rms_silu(x) into this block's first convolution's input buffer.  nxt = (gamma, conv) of
-        the RMS_norm + SiLU + convolution that consume this block's output next: written by conv2's epilogue (one launch where
-        ops.conv_cl_rms_ok, else conv + rms_silu) -- the un-normalised output is returned as well (the next block's shortcut)."""
+    def _normed(self, x, gamma, conv: _Conv, staged: Optional[_Staged]) -> _Staged:
+        """rms_silu(x) as conv's input: the one x's producer handed over, held to x's frames, else written here by its own launch."""
         T, H, W, _ = x.shape
-        c1, c2 = self._convs[name + ".residual.2"], self._convs[name + ".residual.6"]
-        h = self._convs[name + ".shortcut"](x) if (name + ".shortcut") in self._convs else x
-        if pre:
-            y = c1._buf[2:] if c1.temporal else c1._buf
-        else:
-            y = ops.rms_silu_cl(x, self._gamma[name + ".residual.0.gamma"], out=c1.input(T, H, W, x.device))
-        y2 = c2.input(T, H, W, x.device)
-        if self.fuse_rms:
-            c1(y, rms=(self._gamma[name + ".residual.3.gamma"], y2), want_raw=False)  # conv -> RMS_norm -> SiLU in one launch where covered
-        else:
-            ops.rms_silu_cl(c1(y), self._gamma[name + ".residual.3.gamma"], out=y2)
+        if staged is None:
+            staged = conv.input(T, H, W, x.device)
+            ops.rms_silu_cl(x, gamma, out=staged.new)
+        elif tuple(staged.buf.shape) != (conv.hist + T, H, W, conv.geo[0]):
+            raise RuntimeError(f"staged input {tuple(staged.buf.shape)} does not belong to {tuple(x.shape)} read by a convolution of "
+                               f"{conv.geo[0]} channels with {conv.hist} history frames")
+        return staged
+
+    def _conv_handoff(self, conv: _Conv, s: _Staged, nxt, upsample: bool = False, res=None):
+        """conv(s) -> (raw, staged): nxt = (gamma, conv) of the RMS_norm + SiLU + convolution that read the result next gets
+        rms_silu(raw) staged as its input by this launch (or the two, _Conv.__call__), raw being kept for the shortcut; None without nxt."""
         if nxt is None:
-            return c2(y2, res=h)
-        return c2(y2, res=h, rms=(nxt[0], nxt[1].input(T, H, W, x.device)), want_raw=True)
+            return conv(s, upsample=upsample, res=res), None
+        T, H, W, _ = s.new.shape
+        out = nxt[1].input(T, H << upsample, W << upsample, s.new.device)
+        return conv(s, upsample=upsample, res=res, rms=(nxt[0], out)), out
+
+    def _res_block(self, x, name, staged: Optional[_Staged] = None, nxt=None):   # ResidualBlock.forward (vae.py:202-220)
+        """staged: rms_silu(x) as the producer of x wrote it into this block's first convolution's input; nxt: see _conv_handoff."""
+        c1, c2 = self._convs[name + ".residual.2"], self._convs[name + ".residual.6"]
+        sc = self._convs.get(name + ".shortcut")
+        h = sc(sc.stage(x)) if sc is not None else x
+        s1 = self._normed(x, self._gamma[name + ".residual.0.gamma"], c1, staged)
+        s2 = c2.input(x.shape[0], x.shape[1], x.shape[2], x.device)
+        c1(s1, rms=(self._gamma[name + ".residual.3.gamma"], s2), want_raw=False)
+        return self._conv_handoff(c2, s2, nxt, res=h)
 
     def _attn_block(self, x, name):                                      # AttentionBlock.forward (vae.py:240-262)
         a = self._attn[name]
@@ -232,7 +258,8 @@ class _VaeHalfHIP(nn.Module):
 
     def _consumer(self, i: int):
         """(gamma, conv) of the RMS_norm + SiLU + convolution that read layer i's output next -- a residual block's first pair, or the
-        head's -- when the producer can write the normalised tensor itself; None: an attention block or a resample comes next."""
+        head's -- when the producer can write the normalised tensor itself; None: an attention block or a resample comes next.
+        Offered to temporal convolutions only: in both layouts of the default VaeConfig that is every one of them."""
         if not self.fuse_rms:
             return None
         if i + 1 == len(self.layers):
@@ -242,7 +269,20 @@ class _VaeHalfHIP(nn.Module):
             c = (self._gamma[nl[1] + ".residual.0.gamma"], self._convs[nl[1] + ".residual.2"])
         else:
             return None
-        return c if c[1].temporal else None           # (the consumer's input buffer is remembered only by temporal convolutions)
+        return c if c[1].hist == 2 else None
+
+    def _walk(self, x, staged: Optional[_Staged] = None):
+        """The layers behind the front end (which may hand over rms_silu(x) staged for the first block), then the head: RMS_norm +
+        SiLU + head convolution.  Decoder3d.forward (vae.py:423-472) and Encoder3d.forward (vae.py:318-366) alike."""
+        for i, L in enumerate(self.layers):
+            if L[0] == "res":
+                x, staged = self._res_block(x, L[1], staged, self._consumer(i))
+            elif L[0] == "attn":
+                x, staged = self._attn_block(x, L[1]), None
+            else:
+                x, staged = self._resample(x, L[1], L[0], self._consumer(i))
+        head = self._convs[self._head[1]]
+        return head(self._normed(x, self._gamma[self._head[0]], head, staged))
 
 
 class WanVAEDecoderHIP(_VaeHalfHIP):
@@ -252,39 +292,19 @@ class WanVAEDecoderHIP(_VaeHalfHIP):
     _foreign = ("encoder.", "conv1.")
     _head = ("decoder.head.0.gamma", "decoder.head.2")
 
-    def __init__(self, cfg: Optional[VaeConfig] = None, device="cuda", chunk: int = 2):
+    def __init__(self, cfg: Optional[VaeConfig] = None, device="cuda", chunk: int = 2, fuse_rms: Optional[bool] = None):
         super().__init__()
-        self._init_half(cfg, vae_decoder_layout, vae_decoder_param_shapes, device)
+        self._init_half(cfg, vae_decoder_layout, vae_decoder_param_shapes, device, fuse_rms)
         self.chunk = max(1, int(chunk))
 
-    def _resample(self, x, name, mode, nxt=None):                                  # Resample.forward (vae.py:101-143)
+    def _resample(self, x, name, mode, nxt):                             # Resample.forward (vae.py:101-143)
         if mode == "up3d" and not self._first:
             T, H, W, C = x.shape
-            y = self._convs[name + ".time_conv"](x)                      # [T,H,W,2C]: two output frames per input frame
+            tc = self._convs[name + ".time_conv"]
+            y = tc(tc.stage(x))                                          # [T,H,W,2C]: two output frames per input frame
             x = y.view(T, H, W, 2, C).permute(0, 3, 1, 2, 4).reshape(2 * T, H, W, C).contiguous()   # vae.py:131-134 interleave
         conv = self._convs[name + ".resample.1"]
-        if nxt is None:
-            return conv(x, upsample=True)
-        return conv(x, upsample=True, rms=(nxt[0], nxt[1].input(x.shape[0], 2 * x.shape[1], 2 * x.shape[2], x.device)), want_raw=True)
-
-    def _decoder_step(self, x):                                          # Decoder3d.forward (vae.py:423-472)
-        x = self._convs["decoder.conv1"](x)
-        pre = False
-        for i, L in enumerate(self.layers):
-            nxt = self._consumer(i)
-            if L[0] == "res":
-                x = self._res_block(x, L[1], pre, nxt)
-            elif L[0] == "attn":
-                x, nxt = self._attn_block(x, L[1]), None
-            else:
-                x = self._resample(x, L[1], L[0], nxt)
-            pre = nxt is not None
-        head = self._convs["decoder.head.2"]
-        if pre:
-            y = head._buf[2:] if head.temporal else head._buf
-        else:
-            y = ops.rms_silu_cl(x, self._gamma["decoder.head.0.gamma"], out=head.input(x.shape[0], x.shape[1], x.shape[2], x.device))
-        return head(y)                          # [T', H, W, 8] (3 channels + padding)
+        return self._conv_handoff(conv, conv.stage(x), nxt, upsample=True)
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, keep_cache: bool = False, frames: str = "float") -> torch.Tensor:
@@ -299,12 +319,13 @@ class WanVAEDecoderHIP(_VaeHalfHIP):
         if not keep_cache:
             self.clear_cache()
         x = ops.vae_unscale_cl(z.contiguous(), self._mean, self._inv_std)
-        x = self._convs["conv2"](x)
+        conv2, conv1 = self._convs["conv2"], self._convs["decoder.conv1"]
+        x = conv2(conv2.stage(x))
         outs: List[torch.Tensor] = []
         i, T = 0, x.shape[0]
         while i < T:
             n = 1 if self._first else min(self.chunk, T - i)
-            y = self._decoder_step(x[i:i + n])
+            y = self._walk(conv1(conv1.stage(x[i:i + n])))               # [T', H, W, 8] (3 channels + padding)
             outs.append(ops.cl_to_tchw_clamp(y) if frames == "float" else ops.cl_to_frames_u8(y))
             self._first = False
             i += n
@@ -324,9 +345,10 @@ class WanVAEEncoderHIP(_VaeHalfHIP):
     _head = ("encoder.head.0.gamma", "encoder.head.2")
     CPAD = 32       # input channels of encoder.conv1 after zero padding: 32 = halo-tile kernel with the fused RMS_norm, 8 = generic decode
 
-    def __init__(self, cfg: Optional[VaeConfig] = None, device="cuda", chunk: int = 4, cpad: Optional[int] = None):
+    def __init__(self, cfg: Optional[VaeConfig] = None, device="cuda", chunk: int = 4, cpad: Optional[int] = None,
+                 fuse_rms: Optional[bool] = None):
         super().__init__()
-        self._init_half(cfg, vae_encoder_layout, vae_encoder_param_shapes, device)
+        self._init_half(cfg, vae_encoder_layout, vae_encoder_param_shapes, device, fuse_rms)
         chunk = int(chunk)
         if chunk < 4 or chunk % 4:
             raise ValueError(f"WanVAEEncoderHIP: chunk={chunk} must be a positive multiple of 4 (vae.py:520-535 feeds 4 frames per step)")
@@ -337,55 +359,34 @@ class WanVAEEncoderHIP(_VaeHalfHIP):
         if name == "encoder.conv1":                 # 3 -> cpad input channels, zero weights (ll_pixels_to_cl writes zero channels)
             wp = torch.zeros(w.shape[0], self.cpad, *w.shape[2:], dtype=w.dtype, device=w.device)
             wp[:, :w.shape[1]] = w
-            return _Conv(wp, b)
-        if name == "conv1":                         # mu, log_var = conv1(out).chunk(2, dim=1) (vae.py:536): mu's rows only
-            return _Conv(w[:self.cfg.z_dim], b[:self.cfg.z_dim])
-        if name.endswith(".time_conv"):
+            w = wp
+        elif name == "conv1":                       # mu, log_var = conv1(out).chunk(2, dim=1) (vae.py:536): mu's rows only
+            w, b = w[:self.cfg.z_dim], b[:self.cfg.z_dim]
+        elif name.endswith(".time_conv"):
             return _TDownConv(w, b)
-        return _Conv(w, b)
+        return super()._make_conv(name, w, b)
 
-    def _downsample(self, x, name, mode):           # Resample.forward, downsample modes (vae.py:138-160)
+    def _resample(self, x, name, mode, nxt):        # Resample.forward, downsample modes (vae.py:138-160)
+        """Hands nothing over, whatever reads it next: the strided kernels have no RMS_norm epilogue."""
         conv = self._convs[name + ".resample.1"]
         tc = self._convs[name + ".time_conv"] if mode == "down3d" else None
-        T, H, W, _ = x.shape
-        if tc is None or tc.last is None:
+        if tc is None or not tc.started:
             y = ops.conv_cl_down(x, conv.w, conv.b, conv.geo)
-            if tc is not None:
-                tc.last = y[-1:]                    # feat_cache[idx] = x.clone(); time_conv skipped (vae.py:146-148)
-            return y
-        buf = tc.input(T, H // 2, W // 2, x.device)
-        ops.conv_cl_down(x, conv.w, conv.b, conv.geo, out=buf[1:])
-        return tc(buf)
+            return (y if tc is None else tc.skip(y)), None
+        s = tc.input(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.device)
+        ops.conv_cl_down(x, conv.w, conv.b, conv.geo, out=s.new)
+        return tc(s), None
 
-    def _encoder_step(self, px, channel_dim: int):   # Encoder3d.forward (vae.py:318-366) + conv1's mu rows
-        c1 = self._convs["encoder.conv1"]
+    def _encoder_step(self, px, channel_dim: int):   # the pixel front end, Encoder3d.forward (vae.py:318-366), conv1's mu rows
+        c1, mu = self._convs["encoder.conv1"], self._convs["conv1"]
         if px.dtype == torch.uint8:                 # video frames [T, H, W, 3]: normalised, rounded and laid out by one kernel
-            T, H, W = px.shape[:3]
-            x = ops.pixels_u8_to_cl(px, self.cpad, out=c1.input(T, H, W, px.device))
+            s = c1.input(px.shape[0], px.shape[1], px.shape[2], px.device)
+            ops.pixels_u8_to_cl(px, self.cpad, out=s.new)
         else:
-            T, H, W = px.shape[1 - channel_dim], px.shape[2], px.shape[3]
-            x = ops.pixels_to_cl(px, channel_dim, self.cpad, out=c1.input(T, H, W, px.device))
-        nxt = self._consumer(-1)
-        if nxt is None:
-            x = c1(x)
-        else:
-            x = c1(x, rms=(nxt[0], nxt[1].input(T, H, W, px.device)), want_raw=True)
-        pre = nxt is not None
-        for i, L in enumerate(self.layers):
-            nxt = self._consumer(i)
-            if L[0] == "res":
-                x = self._res_block(x, L[1], pre, nxt)
-            elif L[0] == "attn":
-                x, nxt = self._attn_block(x, L[1]), None
-            else:
-                x, nxt = self._downsample(x, L[1], L[0]), None
-            pre = nxt is not None
-        head = self._convs["encoder.head.2"]
-        if pre:
-            y = head._buf[2:]
-        else:
-            y = ops.rms_silu_cl(x, self._gamma["encoder.head.0.gamma"], out=head.input(x.shape[0], x.shape[1], x.shape[2], x.device))
-        return self._convs["conv1"](head(y))        # [T', h, w, z_dim]
+            s = c1.input(px.shape[1 - channel_dim], px.shape[2], px.shape[3], px.device)
+            ops.pixels_to_cl(px, channel_dim, self.cpad, out=s.new)
+        x, staged = self._conv_handoff(c1, s, self._consumer(-1))
+        return mu(mu.stage(self._walk(x, staged)))  # [T', h, w, z_dim]
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, keep_cache: bool = False, channel_dim: int = 0) -> torch.Tensor:
@@ -451,23 +452,21 @@ class WanVAEWrapper(nn.Module):
                 self.encoder.load_state_dict(enc, strict=False)
         return self.model.load_state_dict(sd, strict=strict)
 
-    def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
+    def _decode(self, latent: torch.Tensor, use_cache: bool, frames: str) -> torch.Tensor:
         if latent.dtype != bf16:
             latent = latent.to(bf16)
         if use_cache:      # ONE streaming feature cache: a second sample would continue the first one's stream
             assert latent.shape[0] == 1, "Batch size must be 1 when using cache"          # utils/wan_wrapper.py:99
-        out = [self.model.decode(u, keep_cache=use_cache) for u in latent]
-        return torch.stack(out, 0)
+        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames=frames) for u in latent], 0)
+
+    def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
+        return self._decode(latent, use_cache, "float")
 
     def decode_to_frames(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
         """latent [B, T, 16, h, w] -> video frames uint8 [B, T', H, W, 3]: bit for bit
         `(255.0 * (decode_to_pixel(latent, use_cache) * 0.5 + 0.5).clamp(0, 1).permute(0, 1, 3, 4, 2)).to(torch.uint8)`, without the
         fp32 planes ever existing."""
-        if latent.dtype != bf16:
-            latent = latent.to(bf16)
-        if use_cache:
-            assert latent.shape[0] == 1, "Batch size must be 1 when using cache"
-        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames="uint8") for u in latent], 0)
+        return self._decode(latent, use_cache, "uint8")
 
     def _get_encoder(self) -> WanVAEEncoderHIP:
         if self.encoder is None:
@@ -479,25 +478,24 @@ class WanVAEWrapper(nn.Module):
             self.encoder = enc
         return self.encoder
 
+    def _encode(self, what: str, x: torch.Tensor, keep_cache: bool, wrong: Optional[str]) -> torch.Tensor:
+        if wrong is not None:
+            raise RuntimeError(f"{what}: expected {wrong}")
+        if not x.is_cuda:
+            raise RuntimeError(f"{what}: expected a device tensor (longlive_amd has no CPU path)")
+        if keep_cache:
+            assert x.shape[0] == 1, "Batch size must be 1 when using cache"
+        enc = self._get_encoder()
+        return torch.stack([enc.encode(u, keep_cache=keep_cache) for u in x], 0)
+
     def encode_to_latent(self, pixel: torch.Tensor, keep_cache: bool = False) -> torch.Tensor:
         """utils/wan_wrapper.py:80-94.  keep_cache (not in the reference): continue the stream of the previous call (B = 1)."""
-        if pixel.dim() != 5 or pixel.shape[1] != 3:
-            raise RuntimeError(f"encode_to_latent: expected pixel [B, 3, T, H, W], got {tuple(pixel.shape)}")
-        if not pixel.is_cuda:
-            raise RuntimeError("encode_to_latent: expected a device tensor (longlive_amd has no CPU path)")
-        if keep_cache:
-            assert pixel.shape[0] == 1, "Batch size must be 1 when using cache"
-        enc = self._get_encoder()
-        return torch.stack([enc.encode(u, keep_cache=keep_cache) for u in pixel], 0)
+        ok = pixel.dim() == 5 and pixel.shape[1] == 3
+        return self._encode("encode_to_latent", pixel, keep_cache, None if ok else f"pixel [B, 3, T, H, W], got {tuple(pixel.shape)}")
 
     def encode_frames_to_latent(self, frames: torch.Tensor, keep_cache: bool = False) -> torch.Tensor:
         """Video frames uint8 [B, T, H, W, 3] -> fp32 [B, 1 + (T - 1) // 4, 16, H/8, W/8]: bit for bit
         encode_to_latent((frames.float() / 127.5 - 1).permute(0, 4, 1, 2, 3)), without the fp32 planes ever existing."""
-        if frames.dim() != 5 or frames.shape[4] != 3 or frames.dtype != torch.uint8:
-            raise RuntimeError(f"encode_frames_to_latent: expected uint8 frames [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
-        if not frames.is_cuda:
-            raise RuntimeError("encode_frames_to_latent: expected a device tensor (longlive_amd has no CPU path)")
-        if keep_cache:
-            assert frames.shape[0] == 1, "Batch size must be 1 when using cache"
-        enc = self._get_encoder()
-        return torch.stack([enc.encode(u, keep_cache=keep_cache) for u in frames], 0)
+        ok = frames.dim() == 5 and frames.shape[4] == 3 and frames.dtype == torch.uint8
+        return self._encode("encode_frames_to_latent", frames, keep_cache,
+                            None if ok else f"uint8 frames [B, T, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
