@@ -57,7 +57,8 @@ enum ll_epilogue {
  * (ll_pixels_u8_to_cl), and so do the frames-out entry points (ll_cl_to_frames_u8, ll_jpeg_sizes, ll_jpeg_encode_u8,
  * ll_jpeg_coefficients_u8), and so do the clip-intake entry points (ll_jpeg_decode_sizes, ll_jpeg_decode_coefficients,
  * ll_jpeg_decode_pixels, ll_jpeg_decode_u8, ll_resize_u8), and so do the split entropy route's (ll_jpeg_decode_split_sizes,
- * ll_jpeg_decode_coefficients_split, ll_jpeg_decode_u8_split): 111 covers them too. */
+ * ll_jpeg_decode_coefficients_split, ll_jpeg_decode_u8_split), and so do the planar YUV entry points (ll_frames_u8_to_yuv420,
+ * ll_cl_to_yuv420, ll_yuv_to_frames_u8): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -607,6 +608,28 @@ int ll_jpeg_decode_u8_split(const uint8_t* data, long long nbytes, const int32_t
 int ll_resize_u8(const uint8_t* src, long long src_stride_t, int Hs, int Ws, int y0, int x0, int Hc, int Wc, uint8_t* dst,
                  long long dst_stride_t, int Hd, int Wd, int T, const int32_t* ystart, const int32_t* ycount, const float* yweight, int ky,
                  const int32_t* xstart, const int32_t* xcount, const float* xweight, int kx, ll_stream stream);
+
+/* -- planar YUV ("Planar YUV and Y4M"): BT.601 in 2^16 fixed point, limited range (full_range = 0: Y 16..235,
+ * chroma 16..240) or full range (0..255); the integer arithmetic is csrc/yuv.h's, restated in tests/yuv_ref.py.  An I420 frame is
+ * contiguous: the Y plane H*W, then Cb and Cr of Hc*Wc each, Hc = ceil(H/2), Wc = ceil(W/2), chroma sited at the centre of its 2 x 2
+ * pixels (Y4M C420jpeg), a missing last row or column replicated; frame strides are in BYTES, any alignment.  Stream-ordered, no
+ * allocation; every byte of the frames is written whole and nothing outside them.  Refused before any launch: null operands, T, H,
+ * W < 1, H or W > 65535, short strides, more than one launch covers. -- */
+
+/* frames uint8 [T,H,W,3] RGB (stride_t >= H*W*3) -> out: T I420 frames out_stride >= H*W + 2*Hc*Wc apart. */
+int ll_frames_u8_to_yuv420(const uint8_t* frames, long long stride_t, int T, int H, int W, int full_range, uint8_t* out,
+                           long long out_stride, ll_stream stream);
+/* The decoder head's channels-last bf16 x [T,H,W,ldc] (first 3 channels, ldc >= 3) -> the same I420 frames: the bytes of
+ * ll_cl_to_frames_u8 feed ll_frames_u8_to_yuv420's arithmetic in registers, bit for bit the two calls in a row. */
+int ll_cl_to_yuv420(const ll_bf16* x, int T, int H, int W, int ldc, int full_range, uint8_t* out, long long out_stride, ll_stream stream);
+/* Planes -> frames uint8 out [T,H,W,3] RGB (out_stride_t >= H*W*3).  layout: 0 = 4:2:0 chroma at the centre (C420jpeg, C420),
+ * 1 = 4:2:0 centred vertically and co-sited horizontally (C420mpeg2), 2 = 4:2:0 co-sited on both axes (C420paldv), 3 = 4:2:2 co-sited
+ * (C422), 4 = 4:4:4 (C444), 5 = luma only (Cmono: cb and cr may be NULL).  y [T] planes of H*W stride_y apart; cb, cr [T] planes of
+ * the layout's chroma size (ceil(H/2) or H rows of ceil(W/2) or W) stride_c apart; the three pointers are separate, so the packed
+ * payloads of a Y4M stream and loose planes both work.  Chroma is interpolated to luma resolution with weights in quarters per axis
+ * (3, 1 around a centred sample; 4, 0 and 2, 2 between co-sited ones), the far sample clamped to the plane. */
+int ll_yuv_to_frames_u8(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, long long stride_y, long long stride_c, int T, int H,
+                        int W, int layout, int full_range, uint8_t* out, long long out_stride_t, ll_stream stream);
 
 /* -- encoder (Encoder3d + conv1, wan/modules/vae.py:265-366, 517-543): every stride-1 convolution runs on ll_conv_cl; the two
  * strided gathers below are further gather modes of the same implicit GEMM (same LDS staging, swizzle and epilogue). -- */

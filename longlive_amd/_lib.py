@@ -78,6 +78,9 @@ SIGNATURES = {
     "ll_jpeg_decode_coefficients_split": [_p, _ll, _p, _i, _p, _p] + [_i] * 6 + [_p, _p] + [_p, _i, _i, _p, _p, _ll, _p],
     "ll_jpeg_decode_u8_split": [_p, _ll, _p, _i, _p, _p, _p] + [_i] * 6 + [_p, _p, _p, _ll, _p, _ll] + [_p, _i, _i, _p, _p, _ll, _p],
     "ll_resize_u8": [_p, _ll] + [_i] * 6 + [_p, _ll, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p],
+    "ll_frames_u8_to_yuv420": [_p, _ll, _i, _i, _i, _i, _p, _ll, _p],
+    "ll_cl_to_yuv420": [_p, _i, _i, _i, _i, _i, _p, _ll, _p],
+    "ll_yuv_to_frames_u8": [_p, _p, _p, _ll, _ll, _i, _i, _i, _i, _i, _p, _ll, _p],
     "ll_conv_cl_down": [_p] * 5 + [_i] * 7 + [_p],
     "ll_conv_cl_tdown": [_p] * 5 + [_i] * 7 + [_p],
     "ll_conv_down_plan": [_i] * 6 + [C.c_char_p, _i],

@@ -16,6 +16,10 @@ Extra keys, both modes: `input_video: <path>` continues a clip -- every prompt o
 `input_frames: <int>` caps how many of its frames are used (the LAST 1 + 4k frames that fit).
 `video_codec: mjpeg` writes `<name>.avi` as Motion JPEG, encoded on the GPU at `jpeg_quality: 90` ("Frames
 out"); without the key the video is written as before.  An MJPEG .avi is also read back as `input_video` (through PIL).
+`video_codec: y4m` writes `<name>.y4m` instead: I420 frames from the decoder's last kernel (`yuv_range: limited | full`) in a
+YUV4MPEG2 stream, which any ffmpeg encodes (`ffmpeg -i out.y4m out.mp4`); `input_video: clip.y4m` (or a FIFO that
+`ffmpeg -i any.mp4 -f yuv4mpegpipe` writes into) is converted on the device, `input_rate: match` picks its frames by the header's
+rate, `input_range: full` names the range of a header without one ("Planar YUV and Y4M").
 `input_decode: gpu` decodes such a file's frames on the GPU instead (ops.jpeg_decode: baseline JPEG as this project, libjpeg, Pillow
 or ffmpeg write it), and `input_fit: cover | stretch` resizes a clip of another size to the model's on the GPU (ops.resize_u8);
 without the two keys intake is as before ("Clip intake on the GPU").
@@ -348,11 +352,50 @@ def input_split(value):
     raise ValueError(f"input_split: {value!r} is not auto, off or a number of bytes (a multiple of 4, at least 8)")
 
 
-VIDEO_CODECS = ("mjpeg",)
+VIDEO_CODECS = ("mjpeg", "y4m")
+
+
+def _one_of(key: str, value, choices, default):
+    """A yaml key that names one of `choices` (absent = default), refused by name otherwise."""
+    if value is None:
+        return default
+    v = str(value).strip().lower()
+    if isinstance(value, bool) or v not in choices:
+        raise ValueError(f"{key}: {value!r} is not one of {', '.join(choices)}")
+    return v
+
+
+def yuv_range(value) -> str:
+    """The yaml's `yuv_range:` key for `video_codec: y4m`: limited (default) | full."""
+    return _one_of("yuv_range", value, ("limited", "full"), "limited")
+
+
+def input_range(value) -> Optional[str]:
+    """The yaml's `input_range:` key: the range of a .y4m `input_video` whose header has no XCOLORRANGE tag (absent = limited)."""
+    return _one_of("input_range", value, ("limited", "full"), None)
+
+
+def input_rate(value) -> str:
+    """The yaml's `input_rate:` key for a .y4m `input_video`: keep (default) = its last frames as they are (select_clip_frames),
+    match = frames picked at the header's rate so that the clip plays at 16 frames/s (y4m.select_frames_at_rate)."""
+    return _one_of("input_rate", value, ("keep", "match"), "keep")
+
+
+def is_y4m_input(path) -> bool:
+    """A `.y4m` file, or a FIFO (what `ffmpeg -f yuv4mpegpipe` writes into)."""
+    import stat
+    path = str(path)
+    if os.path.splitext(path)[1].lower() == ".y4m":
+        return True
+    try:
+        return stat.S_ISFIFO(os.stat(path).st_mode)
+    except OSError:
+        return False
 
 
 def video_codec(value) -> Optional[str]:
-    """The yaml's `video_codec:` key: absent / none = write_video's path, `mjpeg` = Motion JPEG in an .avi from the GPU encoder."""
+    """The yaml's `video_codec:` key: absent / none = write_video's path, `mjpeg` = Motion JPEG in an .avi from the GPU encoder,
+    `y4m` = I420 frames from the decoder's last kernel in a YUV4MPEG2 stream (`ffmpeg -i out.y4m out.mp4` makes an mp4 of it)."""
     if value is None or str(value).strip().lower() == "none":
         return None
     v = str(value).strip().lower()
@@ -427,6 +470,9 @@ def load_clip(config, lat_h: int, lat_w: int) -> Optional[torch.Tensor]:
     path = config.get("input_video")
     if not path:
         return None
+    if is_y4m_input(path):
+        raise ValueError(f"input_video: {path!r} is a YUV4MPEG2 stream: it is not read on the host but converted on the device "
+                         f"(load_clip_y4m, the route run() takes for a .y4m file or a FIFO)")
     frames = read_input_video(str(path))
     if tuple(frames.shape[1:3]) != (8 * lat_h, 8 * lat_w):
         raise ValueError(f"input_video: {path!r} is {frames.shape[2]}x{frames.shape[1]} (W x H), the configured size is "
@@ -458,6 +504,48 @@ def load_clip_device(config, lat_h: int, lat_w: int, device):
         raise ValueError(f"input_video: {path!r} is {frames.shape[2]}x{frames.shape[1]} (W x H), the configured size is {W}x{H}; "
                          f"set input_fit: cover | stretch to resize it")
     return ops.resize_u8(frames, (H, W), fit=fit), [int(frames.shape[2]), int(frames.shape[1])]
+
+
+def load_clip_y4m(config, lat_h: int, lat_w: int, device):
+    """The clip of a YUV4MPEG2 `input_video` (a .y4m file or a FIFO), converted on the device: (uint8 [1 + 4k, H, W, 3] ON THE DEVICE,
+    [W, H] of the source when it was resized, else None, [num, den] of the header's rate when `input_rate: match` selected by it, else
+    None).  The stream is read once, front to back, and only a ring of the frames the selection can touch is held; the selected
+    payloads go up in one copy, their planes through ops.yuv_to_frames_u8 (any of the six layouts, `input_range` when the header
+    names no range), then through ops.resize_u8 when `input_fit` is set and the size differs."""
+    from . import ops, y4m
+    path, cap = str(config.get("input_video")), config.get("input_frames")
+    fit, how = input_fit(config.get("input_fit")), input_rate(config.get("input_rate"))
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
+        raise ValueError(f"input_frames: {cap!r} must be an integer >= 1")
+    with y4m.Y4MReader(path, input_range=input_range(config.get("input_range"))) as reader:
+        rate = reader.rate() if how == "match" else None          # F0:0 is refused before a frame is read
+        keep = None if cap is None else 1 + 4 * ((cap - 1) // 4)
+        ring = reader.read_last(keep if rate is None or keep is None else y4m.frames_spanned(keep, rate, 16))
+        total = reader.frames_read
+        Hs, Ws, layout, rng = reader.height, reader.width, reader.layout, reader.range
+    if rate is None:
+        picked = list(range(total))[select_clip_frames(total, cap)]
+    else:
+        picked = y4m.select_frames_at_rate(total, rate, 16, cap)
+    first = total - len(ring)
+    host = torch.frombuffer(bytearray(b"".join(ring[i - first] for i in picked)), dtype=torch.uint8).view(len(picked), -1)
+    buf = host.to(device)                                          # the one copy up
+    hc, wc = ops.yuv_chroma_shape(layout, Hs, Ws)
+    ybytes, cbytes = Hs * Ws, hc * wc
+    y = buf[:, :ybytes].unflatten(1, (Hs, Ws))
+    cb = cr = None
+    if layout != "mono":
+        cb = buf[:, ybytes:ybytes + cbytes].unflatten(1, (hc, wc))
+        cr = buf[:, ybytes + cbytes:].unflatten(1, (hc, wc))
+    frames = ops.yuv_to_frames_u8(y, cb, cr, layout=layout, range=rng)
+    matched = None if rate is None else [rate.numerator, rate.denominator]
+    H, W = 8 * lat_h, 8 * lat_w
+    if (Hs, Ws) == (H, W):
+        return frames, None, matched
+    if fit is None:
+        raise ValueError(f"input_video: {path!r} is {Ws}x{Hs} (W x H), the configured size is {W}x{H}; "
+                         f"set input_fit: cover | stretch to resize it")
+    return ops.resize_u8(frames, (H, W), fit=fit), [Ws, Hs], matched
 
 
 # ---- tokenizers --------------------------------------------------------------------------------------------------------
@@ -587,7 +675,8 @@ def _dist_env():
 def run(mode: str, config, synthetic: bool = False, device: Optional[torch.device] = None) -> List[Dict]:
     """The body of inference.py (mode 'inference') / interactive_inference.py (mode 'interactive').  Returns one record per
     written video: {"path", "idx", "frames", "seconds"}, "input_frames" when the yaml's `input_video` gave a clip to continue,
-    "input_size" ([W, H] of the clip) when `input_fit` resized it, and "codec" and "bytes" when `video_codec` chose one."""
+    "input_size" ([W, H] of the clip) when `input_fit` resized it, "input_rate" ([num, den] of a .y4m clip's header) when
+    `input_rate: match` selected by it, "codec" and "bytes" when `video_codec` chose one, and "range" for `video_codec: y4m`."""
     from .pipeline import CausalInferencePipeline, InteractiveCausalInferencePipeline
     local_rank, rank, world = _dist_env()
     if device is None:
@@ -598,10 +687,14 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     shape = wan_config(config, synthetic)
     codec = video_codec(config.get("video_codec"))             # names and ranges are refused before any model is built
     quality = jpeg_quality(config.get("jpeg_quality"))
+    out_range = yuv_range(config.get("yuv_range"))
+    input_range(config.get("input_range")), input_rate(config.get("input_rate"))
     on_device = config.get("input_decode") is not None or config.get("input_fit") is not None
     input_decode(config.get("input_decode")), input_fit(config.get("input_fit")), input_split(config.get("input_split"))
-    input_size = None
-    if on_device and config.get("input_video"):                # decoded / resized on the device, still before any model is built
+    input_size = matched_rate = None
+    if config.get("input_video") and is_y4m_input(config.get("input_video")):      # planes up in one copy, converted on the device
+        clip, input_size, matched_rate = load_clip_y4m(config, shape.lat_h, shape.lat_w, device)
+    elif on_device and config.get("input_video"):                # decoded / resized on the device, still before any model is built
         clip, input_size = load_clip_device(config, shape.lat_h, shape.lat_w, device)
     else:
         clip = load_clip(config, shape.lat_h, shape.lat_w)     # read and checked before any model is built
@@ -630,7 +723,11 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         extra["input_frames"] = int(clip.shape[0])
         if input_size is not None:
             extra["input_size"] = input_size
-    if codec is not None:                           # the pipeline hands back uint8 frames: no fp32 planes, no torch conversion
+        if matched_rate is not None:
+            extra["input_rate"] = matched_rate
+    if codec == "y4m":                              # the decoder's last kernel writes I420: the bytes of the file's payloads
+        more["frames"], more["yuv_range"] = "yuv420", out_range
+    elif codec is not None:                         # the pipeline hands back uint8 frames: no fp32 planes, no torch conversion
         more["frames"] = "uint8"
     records = []
     for i, idx in enumerate(rank_indices(len(dataset), rank, world)):
@@ -658,6 +755,14 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
             if codec is None:
                 path = write_video(os.path.join(config.output_folder, name), frames[seed_idx], fps=16)
                 records.append({"path": path, "idx": idx, "frames": int(frames.shape[1]), "seconds": dt, **extra})
+                continue
+            if codec == "y4m":
+                from . import y4m
+                host = video[seed_idx].cpu().numpy()                                     # I420 [T', bytes]: written frame by frame
+                path = os.path.splitext(os.path.join(config.output_folder, name))[0] + ".y4m"
+                size = y4m.write_y4m(path, iter(host), 8 * wcfg.lat_w, 8 * wcfg.lat_h, fps=16, range=out_range)
+                records.append({"path": path, "idx": idx, "frames": int(host.shape[0]), "seconds": dt, "codec": codec, "bytes": size,
+                                "range": out_range, **extra})
                 continue
             from . import ops
             files = ops.jpeg_bytes(*ops.jpeg_encode(video[seed_idx], quality))           # uint8 [T', H, W, 3] on the device

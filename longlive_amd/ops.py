@@ -783,6 +783,120 @@ def jpeg_coefficients(frames, quality: int = 90):
     return coef
 
 
+# ---- planar YUV: I420 frames out, planes of six layouts in ("Planar YUV and Y4M") -----------------
+YUV_RANGES = ("limited", "full")
+YUV_LAYOUTS = ("420jpeg", "420mpeg2", "420paldv", "422", "444", "mono")     # the index is ll_yuv_to_frames_u8's `layout`
+
+
+def _yuv_full(range) -> int:
+    if range not in YUV_RANGES:
+        raise ValueError(f"range: {range!r} is not one of {', '.join(YUV_RANGES)}")
+    return int(range == "full")
+
+
+def yuv420_bytes(H: int, W: int) -> int:
+    """Bytes of one I420 frame: the Y plane, then Cb and Cr of ceil(H/2) x ceil(W/2)."""
+    return int(H) * int(W) + 2 * ((int(H) + 1) // 2) * ((int(W) + 1) // 2)
+
+
+def yuv_chroma_shape(layout: str, H: int, W: int):
+    """(Hc, Wc) of a layout's chroma planes; (0, 0) for mono."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f"layout: {layout!r} is not one of {', '.join(YUV_LAYOUTS)}")
+    if layout == "mono":
+        return 0, 0
+    return (H if layout in ("422", "444") else (H + 1) // 2), (W if layout == "444" else (W + 1) // 2)
+
+
+def _yuv420_out(out, T: int, H: int, W: int, device):
+    n = yuv420_bytes(H, W)
+    if out is None:
+        out = torch.empty(T, n, dtype=torch.uint8, device=device)
+    if not out.is_cuda or out.dtype != torch.uint8:
+        raise RuntimeError("out: expected a uint8 device tensor")
+    assert out.shape == (T, n) and out.stride(1) == 1, f"out: {tuple(out.shape)} strides {out.stride()} is not [T, {n}] with contiguous frames"
+    stride = out.stride(0) if T > 1 else n
+    assert stride >= n
+    return out, stride
+
+
+def frames_u8_to_yuv420(frames, range: str = "limited", out=None):
+    """uint8 frames [T, H, W, 3] RGB -> uint8 [T, yuv420_bytes(H, W)]: I420 frames (BT.601, chroma at the centre of its 2 x 2 pixels,
+    `range` limited or full), the integer arithmetic of csrc/yuv.h.  `out`: a uint8 [T, yuv420_bytes] view with contiguous frames."""
+    full = _yuv_full(range)
+    frames, stride_t = _frames_u8(frames, "frames")
+    T, H, W, _ = frames.shape
+    out, ost = _yuv420_out(out, T, H, W, frames.device)
+    _lib.check(_lib.load().ll_frames_u8_to_yuv420(frames.data_ptr(), stride_t, T, H, W, full, out.data_ptr(), ost, _stream()),
+               "ll_frames_u8_to_yuv420")
+    return out
+
+
+def cl_to_yuv420(x, range: str = "limited", out=None):
+    """[T,H,W,C>=3] bf16 channels-last -> uint8 [T, yuv420_bytes(H, W)]: frames_u8_to_yuv420(cl_to_frames_u8(x)) bit for bit, in one
+    pass without the RGB bytes touching memory."""
+    full = _yuv_full(range)
+    _chk(x, "x")
+    T, H, W, C = x.shape
+    out, ost = _yuv420_out(out, T, H, W, x.device)
+    _lib.check(_lib.load().ll_cl_to_yuv420(x.data_ptr(), T, H, W, C, full, out.data_ptr(), ost, _stream()), "ll_cl_to_yuv420")
+    return out
+
+
+def yuv420_planes(buf, H: int, W: int):
+    """Views (y [..., H, W], cb [..., Hc, Wc], cr [..., Hc, Wc]) of I420 frames buf [..., yuv420_bytes(H, W)]."""
+    hc, wc = (H + 1) // 2, (W + 1) // 2
+    assert buf.shape[-1] == yuv420_bytes(H, W), f"buf: {tuple(buf.shape)} does not hold {H} x {W} I420 frames"
+    return (buf[..., :H * W].unflatten(-1, (H, W)), buf[..., H * W:H * W + hc * wc].unflatten(-1, (hc, wc)),
+            buf[..., H * W + hc * wc:].unflatten(-1, (hc, wc)))
+
+
+def _yuv_plane(p, name: str, T: int, h: int, w: int):
+    """A [T, h, w] uint8 device plane stack with contiguous planes (copied when they are not) and its plane stride in bytes."""
+    if not p.is_cuda:
+        raise RuntimeError(f"{name}: expected a device tensor (longlive_amd has no CPU path)")
+    if p.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: expected uint8, got {p.dtype}")
+    assert tuple(p.shape) == (T, h, w), f"{name}: {tuple(p.shape)} is not [{T}, {h}, {w}]"
+    if p.stride(2) != 1 or p.stride(1) != w or (T > 1 and p.stride(0) < h * w):
+        p = p.contiguous()
+    return p, (p.stride(0) if T > 1 else h * w)
+
+
+def yuv_to_frames_u8(y, cb=None, cr=None, layout: str = "420jpeg", range: str = "limited", out=None):
+    """Planes y [T, H, W], cb / cr [T, Hc, Wc] (yuv_chroma_shape; None for mono) -> uint8 frames [T, H, W, 3] RGB: BT.601, chroma
+    interpolated to luma resolution as the layout sites it (csrc/yuv.h).  The planes may be views of packed payloads (any plane
+    stride); cb and cr must share one.  `out`: a uint8 [T, H, W, 3] view with contiguous frames."""
+    full = _yuv_full(range)
+    if y.dim() != 3:
+        raise RuntimeError(f"y: {tuple(y.shape)} is not [T, H, W]")
+    T, H, W = y.shape
+    hc, wc = yuv_chroma_shape(layout, H, W)
+    y, sty = _yuv_plane(y, "y", T, H, W)
+    stc = 0
+    if layout == "mono":
+        cb = cr = None
+    else:
+        if cb is None or cr is None:
+            raise RuntimeError(f"cb, cr: layout {layout} needs both chroma planes")
+        cb, stc = _yuv_plane(cb, "cb", T, hc, wc)
+        cr, stc_r = _yuv_plane(cr, "cr", T, hc, wc)
+        if stc_r != stc:
+            cb, cr = cb.contiguous(), cr.contiguous()
+            stc = hc * wc
+    if out is None:
+        out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=y.device)
+    if not out.is_cuda or out.dtype != torch.uint8:
+        raise RuntimeError("out: expected a uint8 device tensor")
+    assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
+        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
+    ost = out.stride(0) if T > 1 else 3 * H * W
+    assert ost >= 3 * H * W
+    _lib.check(_lib.load().ll_yuv_to_frames_u8(y.data_ptr(), _ptr(cb), _ptr(cr), sty, stc, T, H, W, YUV_LAYOUTS.index(layout), full,
+                                               out.data_ptr(), ost, _stream()), "ll_yuv_to_frames_u8")
+    return out
+
+
 # ---- clip intake: baseline JPEG decoder, antialiased resize ------------------------------------------------------------
 # split="auto" (profiles/clip_intake.md, DESIGN.md section 5c): 1024 bytes per subsequence, so only segments of 4 KiB and more are
 # cut, and only in a clip of fewer than 1024 segments: the split route decodes every byte about three times (pass 0, the rescan, the

@@ -139,9 +139,9 @@ class CausalInferencePipeline(nn.Module):
                        crossattn_cache=self.crossattn_cache, current_start=start_frame * self.frame_seq_length,
                        **self._kv_only_kw())
 
-    def _side_decoder(self, noise: torch.Tensor, frames: str = "float"):
+    def _side_decoder(self, noise: torch.Tensor, frames: str = "float", yuv_range: str = "limited"):
         if self.overlap_decode and self.vae is not None and noise.is_cuda and noise.shape[0] == 1:
-            return _SideDecoder(self.vae, frames)
+            return _SideDecoder(self.vae, frames, yuv_range)
         return None
 
     def _use_overlap(self, t: torch.Tensor) -> bool:
@@ -215,14 +215,14 @@ class CausalInferencePipeline(nn.Module):
             yield start, block
         self._join_context()
 
-    def _prefill_profiled(self, prefix, cond, noise, prof, frames: str = "float"):
+    def _prefill_profiled(self, prefix, cond, noise, prof, frames: str = "float", yuv_range: str = "limited"):
         """inference()'s prefill: the "prefill" phase of last_profile, the prefix blocks also handed to the side decoder (returned;
         None without a prefix: nothing is created, queued or timed).  `_prefill` ends with the main stream joined to the aux
         stream, so the phase's closing event sees the passes and the time is their own, profiled or not."""
         if prefix is None:
             return None
         prof.start("prefill")
-        side = self._side_decoder(noise, frames)
+        side = self._side_decoder(noise, frames, yuv_range)
         for _, block in self._prefill(prefix, cond):
             if side is not None:
                 side.push(block)
@@ -261,7 +261,7 @@ class CausalInferencePipeline(nn.Module):
     @torch.no_grad()
     def stream_video(self, noise: torch.Tensor, text_prompts, output: Optional[torch.Tensor] = None,
                      overlap_decode: bool = False, initial_latent: Optional[torch.Tensor] = None, frames: str = "float",
-                     jpeg_quality: int = 90):
+                     jpeg_quality: int = 90, yuv_range: str = "limited"):
         """Live form of `inference`: yields (start_frame, pixels[B, T', 3, H, W] in [0, 1]) after every block, decoding
         each block with the VAE's streaming cache (WanVAE_.cached_decode, wan/modules/vae.py:571-593) -- the first block
         gives 1 + 4 (F - 1) frames, later ones 4 F.  The concatenation equals `inference(...)`'s video bit for bit.
@@ -276,8 +276,11 @@ class CausalInferencePipeline(nn.Module):
         frames: "float" is the above.  "uint8" yields video frames uint8 [B, T', H, W, 3], bit for bit
         `(255.0 * pixels.permute(0, 1, 3, 4, 2)).to(torch.uint8)`, written by the decoder's last kernel ("Frames
         out").  "jpeg" yields [[bytes per frame] per batch item]: those frames as baseline JPEG files at `jpeg_quality`
-        (ops.jpeg_encode, encoded on the stream that decoded them; the bytes are fetched when the block is yielded)."""
-        check_frames_mode(frames, jpeg_quality)
+        (ops.jpeg_encode, encoded on the stream that decoded them; the bytes are fetched when the block is yielded).  "yuv420" yields
+        those frames as I420, uint8 [B, T', ops.yuv420_bytes(H, W)] in `yuv_range` (limited | full), bit for bit
+        ops.frames_u8_to_yuv420 of the "uint8" frames, written by the decoder's last kernel ("Planar YUV and
+        Y4M")."""
+        check_frames_mode(frames, jpeg_quality, yuv_range)
         if self.vae is None:
             raise RuntimeError("stream_video needs a VAE (pass vae= to the pipeline)")
         self.vae.model.clear_cache()
@@ -286,7 +289,7 @@ class CausalInferencePipeline(nn.Module):
         try:
             for start, latents in self.stream(noise, text_prompts, output=output, initial_latent=initial_latent):
                 if not (overlap_decode and latents.is_cuda):
-                    yield start, _delivered(_decode_frames(self.vae, latents, True, frames, jpeg_quality), frames)
+                    yield start, _delivered(_decode_frames(self.vae, latents, True, frames, jpeg_quality, yuv_range), frames)
                     continue
                 main = torch.cuda.current_stream(latents.device)
                 if side is None:
@@ -294,7 +297,7 @@ class CausalInferencePipeline(nn.Module):
                 side.wait_stream(main)                   # the block's denoised latents are final (the context pass only reads them)
                 latents.record_stream(side)
                 with torch.cuda.stream(side):            # decodes are ordered among themselves by the side stream (streaming cache)
-                    video = _decode_frames(self.vae, latents, True, frames, jpeg_quality)
+                    video = _decode_frames(self.vae, latents, True, frames, jpeg_quality, yuv_range)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 if pending is not None:
@@ -318,13 +321,14 @@ class CausalInferencePipeline(nn.Module):
     @torch.no_grad()
     def inference(self, noise: torch.Tensor, text_prompts: List[str], return_latents: bool = False,
                   profile: bool = False, low_memory: bool = False, initial_latent: Optional[torch.Tensor] = None,
-                  frames: str = "float", jpeg_quality: int = 90):
+                  frames: str = "float", jpeg_quality: int = 90, yuv_range: str = "limited"):
         """noise [B, T, 16, H/8, W/8] -> video [B, T', 3, H, W] in [0,1] (None without a VAE) and, with
         return_latents, the denoised latents [B, T, 16, H/8, W/8].
-        frames: "uint8" returns the video as frames uint8 [B, T', H, W, 3], "jpeg" as [[bytes per frame] per batch item] (stream_video).
+        frames: "uint8" returns the video as frames uint8 [B, T', H, W, 3], "jpeg" as [[bytes per frame] per batch item],
+        "yuv420" as I420 frames uint8 [B, T', ops.yuv420_bytes(H, W)] in `yuv_range` (stream_video).
         initial_latent [B, n, 16, H/8, W/8]: the clip to continue.  `noise` then holds only the T NEW frames; the latents and the
         video cover all n + T frames (1 + 4 (n + T - 1) pixel frames), `[:, :n]` being the prefix itself."""
-        check_frames_mode(frames, jpeg_quality)
+        check_frames_mode(frames, jpeg_quality, yuv_range)
         prefix = self._check_prefix(noise, initial_latent)
         n = 0 if prefix is None else prefix.shape[1]
         batch_size, num_new_frames = noise.shape[:2]
@@ -338,11 +342,11 @@ class CausalInferencePipeline(nn.Module):
         prof.start("init")
         self._setup(noise, n + num_new_frames)
         prof.stop("init")
-        side = self._prefill_profiled(prefix, cond, noise, prof, frames)
+        side = self._prefill_profiled(prefix, cond, noise, prof, frames, yuv_range)
         prof.start("diffusion")
         start = n
         if prefix is None:
-            side = self._side_decoder(noise, frames)
+            side = self._side_decoder(noise, frames, yuv_range)
         for _ in range(num_blocks):
             nf = self.num_frame_per_block
             prof.block_start()
@@ -356,14 +360,14 @@ class CausalInferencePipeline(nn.Module):
         self._join_context()
         prof.stop("diffusion")
         prof.start("vae")
-        video = self._finish_video(side, output, frames, jpeg_quality)
+        video = self._finish_video(side, output, frames, jpeg_quality, yuv_range)
         prof.stop("vae")
         self.last_profile = prof.report(self.num_frame_per_block, switch_blocks=())
         if return_latents:
             return video, output
         return video
 
-    def _finish_video(self, side, output, frames: str, jpeg_quality: int):
+    def _finish_video(self, side, output, frames: str, jpeg_quality: int, yuv_range: str = "limited"):
         """inference()'s last step: the side decoder's pieces, or the one-shot decode of the finished latents, in the form `frames`
         names (None without a VAE)."""
         if side is not None:
@@ -373,7 +377,7 @@ class CausalInferencePipeline(nn.Module):
             return video
         if self.vae is None:
             return None
-        return _delivered(_decode_frames(self.vae, output, False, frames, jpeg_quality), frames)
+        return _delivered(_decode_frames(self.vae, output, False, frames, jpeg_quality, yuv_range), frames)
 
     # ---- cache allocation (causal_inference.py:255-293) ----------------------------------------------------------
     def _initialize_kv_cache(self, batch_size, dtype, device, kv_cache_size_override: Optional[int] = None):
@@ -421,15 +425,19 @@ def _mk(args, name, default):
     return getattr(mk, name, default)
 
 
-FRAME_MODES = ("float", "uint8", "jpeg")
+FRAME_MODES = ("float", "uint8", "jpeg", "yuv420")
+YUV_RANGES = ("limited", "full")
 
 
-def check_frames_mode(frames, jpeg_quality=90) -> None:
-    """The `frames=` keyword of stream_video / inference, refused before any launch."""
+def check_frames_mode(frames, jpeg_quality=90, yuv_range="limited") -> None:
+    """The `frames=` keyword of stream_video / inference, refused before any launch.  `jpeg_quality` is read by "jpeg" alone,
+    `yuv_range` by "yuv420" alone."""
     if frames not in FRAME_MODES:
         raise ValueError(f"frames: {frames!r} is not one of {', '.join(FRAME_MODES)}")
     if frames == "jpeg" and (isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int) or not 1 <= jpeg_quality <= 100):
         raise ValueError(f"jpeg_quality: {jpeg_quality!r} must be an integer 1..100")
+    if frames == "yuv420" and yuv_range not in YUV_RANGES:
+        raise ValueError(f"yuv_range: {yuv_range!r} is not one of {', '.join(YUV_RANGES)}")
 
 
 def _jpeg_pairs(video_u8: torch.Tensor, quality: int):
@@ -438,12 +446,14 @@ def _jpeg_pairs(video_u8: torch.Tensor, quality: int):
     return [ops.jpeg_encode(v, quality) for v in video_u8]
 
 
-def _decode_frames(vae, latents, use_cache: bool, frames: str, jpeg_quality: int):
-    """One decode in the form `frames` names, queued on the current stream: pixels in [0, 1], uint8 frames, or the (buf, sizes)
-    pairs of their JPEG files."""
+def _decode_frames(vae, latents, use_cache: bool, frames: str, jpeg_quality: int, yuv_range: str = "limited"):
+    """One decode in the form `frames` names, queued on the current stream: pixels in [0, 1], uint8 frames, the (buf, sizes)
+    pairs of their JPEG files, or I420 frames."""
     if frames == "float":
         video = vae.decode_to_pixel(latents, use_cache=use_cache)
         return (video * 0.5 + 0.5).clamp(0, 1)
+    if frames == "yuv420":
+        return vae.decode_to_frames(latents, use_cache=use_cache, frames="yuv420", yuv_range=yuv_range)
     video = vae.decode_to_frames(latents, use_cache=use_cache)
     return video if frames == "uint8" else _jpeg_pairs(video, jpeg_quality)
 
@@ -465,11 +475,13 @@ class _SideDecoder:
     """inference() with overlap_decode: every finished block goes through the VAE's streaming decode on a second HIP stream while
     the next block is generated; the pieces concatenated equal the one-shot decode of the finished latents bit for bit
     (tests/test_vae_gpu.py).  Batch 1 only (the streaming cache holds one stream).  frames "uint8" / "jpeg": the pieces are uint8
-    frames [1, T', H, W, 3] (inference() encodes the finished video)."""
+    frames [1, T', H, W, 3] (inference() encodes the finished video).  frames "yuv420": the pieces are I420 frames [1, T', bytes]
+    already; either way they concatenate along dim 1."""
 
-    def __init__(self, vae, frames: str = "float"):
+    def __init__(self, vae, frames: str = "float", yuv_range: str = "limited"):
         self.vae, self.pieces, self.side = vae, [], None
-        self.frames = "float" if frames == "float" else "uint8"
+        self.frames = frames if frames in ("float", "yuv420") else "uint8"
+        self.yuv_range = yuv_range
         vae.model.clear_cache()
 
     def push(self, latents: torch.Tensor):
@@ -479,7 +491,7 @@ class _SideDecoder:
         self.side.wait_stream(main)
         latents.record_stream(self.side)
         with torch.cuda.stream(self.side):
-            self.pieces.append(_decode_frames(self.vae, latents, True, self.frames, 0))
+            self.pieces.append(_decode_frames(self.vae, latents, True, self.frames, 0, self.yuv_range))
 
     def finish(self) -> Optional[torch.Tensor]:
         if self.side is None:                       # no block was pushed

@@ -49,13 +49,14 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
     @torch.no_grad()
     def inference(self, noise: torch.Tensor, *, text_prompts_list: List[List[str]], switch_frame_indices: List[int],
                   return_latents: bool = False, low_memory: bool = False, profile: bool = False,
-                  initial_latent: Optional[torch.Tensor] = None, frames: str = "float", jpeg_quality: int = 90):
+                  initial_latent: Optional[torch.Tensor] = None, frames: str = "float", jpeg_quality: int = 90,
+                  yuv_range: str = "limited"):
         """Switch to prompt segment i+1 at the first block whose start frame >= switch_frame_indices[i] (:237).
         initial_latent [B, n, 16, h, w]: the clip to continue (CausalInferencePipeline.inference), prefilled under
         text_prompts_list[0].  Frame numbers -- the switch indices too -- count on the n + T timeline and only GENERATED blocks
         switch: an index <= n switches at the first generated block, whose recache then re-encodes prefix frames under the new prompt.
         frames: the form of the video, as in CausalInferencePipeline.inference."""
-        check_frames_mode(frames, jpeg_quality)
+        check_frames_mode(frames, jpeg_quality, yuv_range)
         prefix = self._check_prefix(noise, initial_latent)
         n = 0 if prefix is None else prefix.shape[1]
         batch_size, num_output_frames = noise.shape[:2]
@@ -71,12 +72,12 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
         prof.start("init")
         self._setup(noise, n + num_output_frames)
         prof.stop("init")
-        side = self._prefill_profiled(prefix, cond_list[0], noise, prof, frames)
+        side = self._prefill_profiled(prefix, cond_list[0], noise, prof, frames, yuv_range)
         prof.start("diffusion")
         seg, start, switch_blocks = 0, n, []
         next_switch = switch_frame_indices[0] if switch_frame_indices else None
         if prefix is None:
-            side = self._side_decoder(noise, frames)
+            side = self._side_decoder(noise, frames, yuv_range)
         for blk in range(num_blocks):
             nf = self.num_frame_per_block
             prof.block_start()
@@ -96,7 +97,7 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
         self._join_context()
         prof.stop("diffusion")
         prof.start("vae")
-        video = self._finish_video(side, output, frames, jpeg_quality)
+        video = self._finish_video(side, output, frames, jpeg_quality, yuv_range)
         prof.stop("vae")
         self.last_profile = prof.report(self.num_frame_per_block, switch_blocks=tuple(switch_blocks))
         if return_latents:

@@ -307,13 +307,17 @@ class WanVAEDecoderHIP(_VaeHalfHIP):
         return self._conv_handoff(conv, conv.stage(x), nxt, upsample=True)
 
     @torch.no_grad()
-    def decode(self, z: torch.Tensor, keep_cache: bool = False, frames: str = "float") -> torch.Tensor:
+    def decode(self, z: torch.Tensor, keep_cache: bool = False, frames: str = "float", yuv_range: str = "limited") -> torch.Tensor:
         """z [T, 16, h, w] bf16 latent frames of one video -> fp32 [T', 3, 8h, 8w] in [-1, 1];
         T' = 1 + 4 (T - 1) on a fresh cache, 4 T when continuing a stream (WanVAE_.decode / cached_decode, vae.py:545-593).
         frames="uint8": video frames uint8 [T', 8h, 8w, 3] instead, `(255.0 * (v * 0.5 + 0.5).clamp(0, 1)).to(uint8)` of the float
-        result v bit for bit, written by one kernel per chunk (ops.cl_to_frames_u8)."""
-        if frames not in ("float", "uint8"):
-            raise ValueError(f"WanVAEDecoderHIP.decode: frames={frames!r} is not 'float' or 'uint8'")
+        result v bit for bit, written by one kernel per chunk (ops.cl_to_frames_u8).
+        frames="yuv420": those frames as I420 uint8 [T', ops.yuv420_bytes(8h, 8w)] in `yuv_range` (limited | full), bit for bit
+        ops.frames_u8_to_yuv420 of the uint8 result, written by one kernel per chunk (ops.cl_to_yuv420)."""
+        if frames not in ("float", "uint8", "yuv420"):
+            raise ValueError(f"WanVAEDecoderHIP.decode: frames={frames!r} is not 'float', 'uint8' or 'yuv420'")
+        if frames == "yuv420" and yuv_range not in ops.YUV_RANGES:
+            raise ValueError(f"WanVAEDecoderHIP.decode: yuv_range={yuv_range!r} is not 'limited' or 'full'")
         if not self._packed:
             self._pack()
         if not keep_cache:
@@ -326,7 +330,10 @@ class WanVAEDecoderHIP(_VaeHalfHIP):
         while i < T:
             n = 1 if self._first else min(self.chunk, T - i)
             y = self._walk(conv1(conv1.stage(x[i:i + n])))               # [T', H, W, 8] (3 channels + padding)
-            outs.append(ops.cl_to_tchw_clamp(y) if frames == "float" else ops.cl_to_frames_u8(y))
+            if frames == "yuv420":
+                outs.append(ops.cl_to_yuv420(y, yuv_range))
+            else:
+                outs.append(ops.cl_to_tchw_clamp(y) if frames == "float" else ops.cl_to_frames_u8(y))
             self._first = False
             i += n
         if not keep_cache:
@@ -452,21 +459,25 @@ class WanVAEWrapper(nn.Module):
                 self.encoder.load_state_dict(enc, strict=False)
         return self.model.load_state_dict(sd, strict=strict)
 
-    def _decode(self, latent: torch.Tensor, use_cache: bool, frames: str) -> torch.Tensor:
+    def _decode(self, latent: torch.Tensor, use_cache: bool, frames: str, yuv_range: str = "limited") -> torch.Tensor:
         if latent.dtype != bf16:
             latent = latent.to(bf16)
         if use_cache:      # ONE streaming feature cache: a second sample would continue the first one's stream
             assert latent.shape[0] == 1, "Batch size must be 1 when using cache"          # utils/wan_wrapper.py:99
-        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames=frames) for u in latent], 0)
+        more = {"yuv_range": yuv_range} if frames == "yuv420" else {}
+        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames=frames, **more) for u in latent], 0)
 
     def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
         return self._decode(latent, use_cache, "float")
 
-    def decode_to_frames(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
+    def decode_to_frames(self, latent: torch.Tensor, use_cache: bool = False, frames: str = "uint8",
+                         yuv_range: str = "limited") -> torch.Tensor:
         """latent [B, T, 16, h, w] -> video frames uint8 [B, T', H, W, 3]: bit for bit
         `(255.0 * (decode_to_pixel(latent, use_cache) * 0.5 + 0.5).clamp(0, 1).permute(0, 1, 3, 4, 2)).to(torch.uint8)`, without the
-        fp32 planes ever existing."""
-        return self._decode(latent, use_cache, "uint8")
+        fp32 planes ever existing.  frames="yuv420": those frames as I420, uint8 [B, T', ops.yuv420_bytes(H, W)] in `yuv_range`."""
+        if frames not in ("uint8", "yuv420"):
+            raise ValueError(f"decode_to_frames: frames={frames!r} is not 'uint8' or 'yuv420'")
+        return self._decode(latent, use_cache, frames, yuv_range)
 
     def _get_encoder(self) -> WanVAEEncoderHIP:
         if self.encoder is None:
