@@ -27,6 +27,7 @@ without the two keys intake is as before ("Clip intake on 
 from __future__ import annotations
 
 import argparse
+import functools
 import json
 import os
 import struct
@@ -34,10 +35,11 @@ import sys
 import time
 import zlib
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 
+from .ops import YUV_RANGES
 from .replicas import replica_seed, shard_prompts
 
 
@@ -151,6 +153,14 @@ def model_type_of(config, lora_enabled: bool) -> str:
 
 
 # ---- video files -------------------------------------------------------------------------------------------------------
+def _riff_chunk(tag: bytes, payload: bytes) -> bytes:
+    return tag + struct.pack("<I", len(payload)) + payload + (b"\x00" if len(payload) & 1 else b"")
+
+
+def _riff_list(tag: bytes, payload: bytes) -> bytes:
+    return b"LIST" + struct.pack("<I", len(payload) + 4) + tag + payload
+
+
 def write_avi_rgb24(path: str, frames: torch.Tensor, fps: int = 16) -> None:
     """Uncompressed AVI (RIFF, one 'vids' stream of bottom-up BGR24 DIBs + idx1).  frames uint8 [T, H, W, 3] RGB.
     Streamed to disk one frame at a time: all sizes are known up front, so a 3840-frame clip never exists twice in memory."""
@@ -161,15 +171,8 @@ def write_avi_rgb24(path: str, frames: torch.Tensor, fps: int = 16) -> None:
     avih = struct.pack("<IIIIIIIIII4I", 1000000 // fps, fsz * fps, 0, 0x10, T, 0, 1, fsz, W, H, 0, 0, 0, 0)
     strh = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", b"DIB ", 0, 0, 0, 0, 1, fps, 0, T, fsz, 0xFFFFFFFF, 0, 0, 0, W, H)
     strf = struct.pack("<IiiHHIIiiII", 40, W, H, 1, 24, 0, fsz, 0, 0, 0, 0)
-
-    def chunk(tag, payload):
-        return tag + struct.pack("<I", len(payload)) + payload + (b"\x00" if len(payload) & 1 else b"")
-
-    def lst(tag, payload):
-        return b"LIST" + struct.pack("<I", len(payload) + 4) + tag + payload
-
-    strl = lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf))
-    hdrl = lst(b"hdrl", chunk(b"avih", avih) + strl)
+    strl = _riff_list(b"strl", _riff_chunk(b"strh", strh) + _riff_chunk(b"strf", strf))
+    hdrl = _riff_list(b"hdrl", _riff_chunk(b"avih", avih) + strl)
     movi_len = 4 + T * (8 + fsz)                                    # 'movi' + T x ('00db' size data); fsz is even
     idx_len = 16 * T
     riff_len = 4 + len(hdrl) + 8 + movi_len + 8 + idx_len
@@ -230,14 +233,8 @@ def write_avi_mjpeg(path: str, frames: Sequence[bytes], width: int, height: int,
     avih = struct.pack("<IIIIIIIIII4I", 1000000 // fps, biggest * fps, 0, 0x10, T, 0, 1, biggest, width, height, 0, 0, 0, 0)
     strh = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", b"MJPG", 0, 0, 0, 0, 1, fps, 0, T, biggest, 0xFFFFFFFF, 0, 0, 0, width, height)
     strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
-
-    def chunk(tag, payload):
-        return tag + struct.pack("<I", len(payload)) + payload + (b"\x00" if len(payload) & 1 else b"")
-
-    def lst(tag, payload):
-        return b"LIST" + struct.pack("<I", len(payload) + 4) + tag + payload
-
-    hdrl = lst(b"hdrl", chunk(b"avih", avih) + lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
+    strl = _riff_list(b"strl", _riff_chunk(b"strh", strh) + _riff_chunk(b"strf", strf))
+    hdrl = _riff_list(b"hdrl", _riff_chunk(b"avih", avih) + strl)
     movi_len, idx_len, riff_len = _avi_mjpeg_layout(sizes, len(hdrl))
     if riff_len > AVI_LIMIT:
         fit = T
@@ -307,28 +304,28 @@ def read_avi_mjpeg_files(path: str) -> List[bytes]:
     return files
 
 
+def _one_of(key: str, value, choices, default, absent: str = ""):
+    """A yaml key that names one of `choices` (absent = default), refused by name otherwise."""
+    if value is None:
+        return default
+    v = str(value).strip().lower()
+    if isinstance(value, bool) or v not in choices:
+        raise ValueError(f"{key}: {value!r} is not one of {', '.join(choices)}{absent}")
+    return v
+
+
 INPUT_DECODES = ("host", "gpu")
 INPUT_FITS = ("cover", "stretch")
 
 
 def input_decode(value) -> str:
     """The yaml's `input_decode:` key: absent / host = MJPEG frames decoded by PIL, gpu = by ops.jpeg_decode."""
-    if value is None:
-        return "host"
-    v = str(value).strip().lower()
-    if isinstance(value, bool) or v not in INPUT_DECODES:
-        raise ValueError(f"input_decode: {value!r} is not one of {', '.join(INPUT_DECODES)} (or absent)")
-    return v
+    return _one_of("input_decode", value, INPUT_DECODES, "host", " (or absent)")
 
 
 def input_fit(value) -> Optional[str]:
     """The yaml's `input_fit:` key: absent = a clip of another size is refused, cover / stretch = ops.resize_u8's `fit`."""
-    if value is None:
-        return None
-    v = str(value).strip().lower()
-    if isinstance(value, bool) or v not in INPUT_FITS:
-        raise ValueError(f"input_fit: {value!r} is not one of {', '.join(INPUT_FITS)} (or absent)")
-    return v
+    return _one_of("input_fit", value, INPUT_FITS, None, " (or absent)")
 
 
 INPUT_SPLIT_DEFAULT = "auto"    # what an absent `input_split:` means: None = off, or "auto" (DESIGN.md section 5c holds the measurement)
@@ -352,27 +349,14 @@ def input_split(value):
     raise ValueError(f"input_split: {value!r} is not auto, off or a number of bytes (a multiple of 4, at least 8)")
 
 
-VIDEO_CODECS = ("mjpeg", "y4m")
-
-
-def _one_of(key: str, value, choices, default):
-    """A yaml key that names one of `choices` (absent = default), refused by name otherwise."""
-    if value is None:
-        return default
-    v = str(value).strip().lower()
-    if isinstance(value, bool) or v not in choices:
-        raise ValueError(f"{key}: {value!r} is not one of {', '.join(choices)}")
-    return v
-
-
 def yuv_range(value) -> str:
     """The yaml's `yuv_range:` key for `video_codec: y4m`: limited (default) | full."""
-    return _one_of("yuv_range", value, ("limited", "full"), "limited")
+    return _one_of("yuv_range", value, YUV_RANGES, "limited")
 
 
 def input_range(value) -> Optional[str]:
     """The yaml's `input_range:` key: the range of a .y4m `input_video` whose header has no XCOLORRANGE tag (absent = limited)."""
-    return _one_of("input_range", value, ("limited", "full"), None)
+    return _one_of("input_range", value, YUV_RANGES, None)
 
 
 def input_rate(value) -> str:
@@ -393,24 +377,21 @@ def is_y4m_input(path) -> bool:
         return False
 
 
+VIDEO_CODECS = ("mjpeg", "y4m")
+
+
 def video_codec(value) -> Optional[str]:
     """The yaml's `video_codec:` key: absent / none = write_video's path, `mjpeg` = Motion JPEG in an .avi from the GPU encoder,
     `y4m` = I420 frames from the decoder's last kernel in a YUV4MPEG2 stream (`ffmpeg -i out.y4m out.mp4` makes an mp4 of it)."""
-    if value is None or str(value).strip().lower() == "none":
+    if str(value).strip().lower() == "none":                    # the word, or the absent key
         return None
-    v = str(value).strip().lower()
-    if v not in VIDEO_CODECS:
-        raise ValueError(f"video_codec: {value!r} is not one of {', '.join(VIDEO_CODECS)} (or absent)")
-    return v
+    return _one_of("video_codec", value, VIDEO_CODECS, None, " (or absent)")
 
 
 def jpeg_quality(value) -> int:
     """The yaml's `jpeg_quality:` key (1..100, default 90)."""
-    if value is None:
-        return 90
-    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= 100:
-        raise ValueError(f"jpeg_quality: {value!r} must be an integer 1..100")
-    return int(value)
+    from .pipeline.frames_out import check_jpeg_quality
+    return 90 if value is None else check_jpeg_quality(value)
 
 
 def write_video(path: str, frames: torch.Tensor, fps: int = 16) -> str:
@@ -428,16 +409,41 @@ def write_video(path: str, frames: torch.Tensor, fps: int = 16) -> str:
     return path
 
 
+# One writer per `video_codec`: (run()'s .mp4 name, one sample's frames in the form the pipeline was asked for) -> (the path written,
+# its frame count, the record's codec keys).  Absent key: uint8 [T', H, W, 3] on the host; mjpeg: the same on the device; y4m: I420.
+def _write_default(path: str, frames: torch.Tensor):
+    return write_video(path, frames, fps=16), int(frames.shape[0]), {}
+
+
+def _write_mjpeg(path: str, frames: torch.Tensor, quality: int):
+    from . import ops
+    files = ops.jpeg_bytes(*ops.jpeg_encode(frames, quality))
+    path = os.path.splitext(path)[0] + ".avi"
+    size = write_avi_mjpeg(path, files, int(frames.shape[2]), int(frames.shape[1]), fps=16)
+    return path, len(files), {"codec": "mjpeg", "bytes": size}
+
+
+def _write_y4m(path: str, frames: torch.Tensor, width: int, height: int, out_range: str):
+    from . import y4m
+    host = frames.cpu().numpy()                                     # I420 [T', bytes]: written frame by frame
+    path = os.path.splitext(path)[0] + ".y4m"
+    size = y4m.write_y4m(path, iter(host), width, height, fps=16, range=out_range)
+    return path, int(host.shape[0]), {"codec": "y4m", "bytes": size, "range": out_range}
+
+
+def input_frames(cap) -> Optional[int]:
+    """The yaml's `input_frames:` key: at most so many frames of the clip are used (absent = all of them)."""
+    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
+        raise ValueError(f"input_frames: {cap!r} must be an integer >= 1")
+    return cap
+
+
 def select_clip_frames(total: int, cap: Optional[int] = None) -> slice:
     """Which frames of a `total`-frame clip are continued: the last 1 + 4k with the largest k that fits the clip and the cap (the
     VAE encoder takes 1 frame, then 4 per latent).  The END of the clip is what gets continued, so frames are dropped at the front."""
     if isinstance(total, bool) or int(total) < 1:
         raise ValueError(f"input_video: the clip holds {total} frames, at least 1 is needed")
-    room = int(total)
-    if cap is not None:
-        if isinstance(cap, bool) or int(cap) < 1:
-            raise ValueError(f"input_frames: {cap!r} must be an integer >= 1")
-        room = min(room, int(cap))
+    room = int(total) if input_frames(cap) is None else min(int(total), cap)
     used = 1 + 4 * ((room - 1) // 4)
     return slice(int(total) - used, int(total))
 
@@ -480,6 +486,20 @@ def load_clip(config, lat_h: int, lat_w: int) -> Optional[torch.Tensor]:
     return frames[select_clip_frames(frames.shape[0], config.get("input_frames"))].contiguous()
 
 
+def _fitted(frames: torch.Tensor, path: str, lat_h: int, lat_w: int, fit: Optional[str]):
+    """Device frames [T, Hs, Ws, 3] at the configured size: (as they are, None) when it is theirs, (ops.resize_u8 of them, [Ws, Hs])
+    when `input_fit` says how; refused otherwise."""
+    from . import ops
+    H, W = 8 * lat_h, 8 * lat_w
+    Hs, Ws = int(frames.shape[1]), int(frames.shape[2])
+    if (Hs, Ws) == (H, W):
+        return frames, None
+    if fit is None:
+        raise ValueError(f"input_video: {path!r} is {Ws}x{Hs} (W x H), the configured size is {W}x{H}; "
+                         f"set input_fit: cover | stretch to resize it")
+    return ops.resize_u8(frames, (H, W), fit=fit), [Ws, Hs]
+
+
 def load_clip_device(config, lat_h: int, lat_w: int, device):
     """load_clip with the yaml's `input_decode` / `input_fit` keys: (uint8 [1 + 4k, H, W, 3] ON THE DEVICE, [W, H] of the source when
     it was resized, else None).  `input_decode: gpu` takes an MJPEG .avi: select_clip_frames runs on the chunk count, so only the
@@ -497,13 +517,7 @@ def load_clip_device(config, lat_h: int, lat_w: int, device):
     else:
         frames = read_input_video(path)
         frames = frames[select_clip_frames(frames.shape[0], config.get("input_frames"))].contiguous().to(device)
-    H, W = 8 * lat_h, 8 * lat_w
-    if tuple(frames.shape[1:3]) == (H, W):
-        return frames, None
-    if fit is None:
-        raise ValueError(f"input_video: {path!r} is {frames.shape[2]}x{frames.shape[1]} (W x H), the configured size is {W}x{H}; "
-                         f"set input_fit: cover | stretch to resize it")
-    return ops.resize_u8(frames, (H, W), fit=fit), [int(frames.shape[2]), int(frames.shape[1])]
+    return _fitted(frames, path, lat_h, lat_w, fit)
 
 
 def load_clip_y4m(config, lat_h: int, lat_w: int, device):
@@ -513,10 +527,8 @@ def load_clip_y4m(config, lat_h: int, lat_w: int, device):
     payloads go up in one copy, their planes through ops.yuv_to_frames_u8 (any of the six layouts, `input_range` when the header
     names no range), then through ops.resize_u8 when `input_fit` is set and the size differs."""
     from . import ops, y4m
-    path, cap = str(config.get("input_video")), config.get("input_frames")
+    path, cap = str(config.get("input_video")), input_frames(config.get("input_frames"))
     fit, how = input_fit(config.get("input_fit")), input_rate(config.get("input_rate"))
-    if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
-        raise ValueError(f"input_frames: {cap!r} must be an integer >= 1")
     with y4m.Y4MReader(path, input_range=input_range(config.get("input_range"))) as reader:
         rate = reader.rate() if how == "match" else None          # F0:0 is refused before a frame is read
         keep = None if cap is None else 1 + 4 * ((cap - 1) // 4)
@@ -539,13 +551,25 @@ def load_clip_y4m(config, lat_h: int, lat_w: int, device):
         cr = buf[:, ybytes + cbytes:].unflatten(1, (hc, wc))
     frames = ops.yuv_to_frames_u8(y, cb, cr, layout=layout, range=rng)
     matched = None if rate is None else [rate.numerator, rate.denominator]
-    H, W = 8 * lat_h, 8 * lat_w
-    if (Hs, Ws) == (H, W):
-        return frames, None, matched
-    if fit is None:
-        raise ValueError(f"input_video: {path!r} is {Ws}x{Hs} (W x H), the configured size is {W}x{H}; "
-                         f"set input_fit: cover | stretch to resize it")
-    return ops.resize_u8(frames, (H, W), fit=fit), [Ws, Hs], matched
+    return (*_fitted(frames, path, lat_h, lat_w, fit), matched)
+
+
+class Clip(NamedTuple):
+    """What `input_video` gave, in the terms of the three routes' docstrings (frames: on the host from load_clip, else on the device)."""
+    frames: Optional[torch.Tensor]
+    input_size: Optional[List[int]] = None
+    matched_rate: Optional[List[int]] = None
+
+
+def input_clip(config, lat_h: int, lat_w: int, device) -> Clip:
+    """The clip to continue, by the route the yaml picks: a .y4m file or a FIFO is converted on the device, `input_decode` /
+    `input_fit` decode / resize on the device, anything else is read on the host as before."""
+    path = config.get("input_video")
+    if path and is_y4m_input(path):                              # planes up in one copy, converted on the device
+        return Clip(*load_clip_y4m(config, lat_h, lat_w, device))
+    if path and (config.get("input_decode") is not None or config.get("input_fit") is not None):
+        return Clip(*load_clip_device(config, lat_h, lat_w, device))
+    return Clip(load_clip(config, lat_h, lat_w))
 
 
 # ---- tokenizers --------------------------------------------------------------------------------------------------------
@@ -648,9 +672,7 @@ QUANT_MODES = ("none", "int8", "mxfp8", "fp8_rowwise", "mxfp6", "mxfp4_a6", "mxf
 def quant_mode(value) -> Optional[str]:
     """The yaml's `quant:` key (none | int8 | mxfp8 | fp8_rowwise | mxfp6 | mxfp4_a6 | mxfp4_a4, default none) as
     CausalWanModelHIP.set_quant's argument."""
-    v = "none" if value is None else str(value).strip().lower()
-    if v not in QUANT_MODES:
-        raise ValueError(f"quant: {value!r} is not one of {', '.join(QUANT_MODES)}")
+    v = _one_of("quant", value, QUANT_MODES, "none")
     return None if v == "none" else v
 
 
@@ -659,9 +681,7 @@ ATTN_QUANT_MODES = ("none", "mxfp8")
 
 def attn_quant_mode(value) -> Optional[str]:
     """The yaml's `attn_quant:` key (none | mxfp8, default none) as CausalWanModelHIP.set_attn_quant's argument."""
-    v = "none" if value is None else str(value).strip().lower()
-    if v not in ATTN_QUANT_MODES:
-        raise ValueError(f"attn_quant: {value!r} is not one of {', '.join(ATTN_QUANT_MODES)}")
+    v = _one_of("attn_quant", value, ATTN_QUANT_MODES, "none")
     return None if v == "none" else v
 
 
@@ -689,15 +709,10 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     quality = jpeg_quality(config.get("jpeg_quality"))
     out_range = yuv_range(config.get("yuv_range"))
     input_range(config.get("input_range")), input_rate(config.get("input_rate"))
-    on_device = config.get("input_decode") is not None or config.get("input_fit") is not None
     input_decode(config.get("input_decode")), input_fit(config.get("input_fit")), input_split(config.get("input_split"))
-    input_size = matched_rate = None
-    if config.get("input_video") and is_y4m_input(config.get("input_video")):      # planes up in one copy, converted on the device
-        clip, input_size, matched_rate = load_clip_y4m(config, shape.lat_h, shape.lat_w, device)
-    elif on_device and config.get("input_video"):                # decoded / resized on the device, still before any model is built
-        clip, input_size = load_clip_device(config, shape.lat_h, shape.lat_w, device)
-    else:
-        clip = load_clip(config, shape.lat_h, shape.lat_w)     # read and checked before any model is built
+    clip = input_clip(config, shape.lat_h, shape.lat_w, device)    # read (decoded, resized) and checked before any model is built
+    write = {None: _write_default, "mjpeg": functools.partial(_write_mjpeg, quality=quality),
+             "y4m": functools.partial(_write_y4m, width=8 * shape.lat_w, height=8 * shape.lat_h, out_range=out_range)}[codec]
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
     gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6, W4A6 or W4A4
     gen.model.set_attn_quant(attn_quant_mode(config.get("attn_quant", "none")))   # self-attention: bf16 or MXFP8
@@ -717,14 +732,14 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     os.makedirs(config.output_folder, exist_ok=True)
     model_type = model_type_of(config, lora_enabled)
     extra, more = {}, {}
-    if clip is not None:                            # every prompt continues the same clip: encoded once
-        latent = vae.encode_frames_to_latent(clip.unsqueeze(0).to(device))
+    if clip.frames is not None:                     # every prompt continues the same clip: encoded once
+        latent = vae.encode_frames_to_latent(clip.frames.unsqueeze(0).to(device))
         more["initial_latent"] = latent.expand(config.num_samples, *latent.shape[1:])
-        extra["input_frames"] = int(clip.shape[0])
-        if input_size is not None:
-            extra["input_size"] = input_size
-        if matched_rate is not None:
-            extra["input_rate"] = matched_rate
+        extra["input_frames"] = int(clip.frames.shape[0])
+        if clip.input_size is not None:
+            extra["input_size"] = clip.input_size
+        if clip.matched_rate is not None:
+            extra["input_rate"] = clip.matched_rate
     if codec == "y4m":                              # the decoder's last kernel writes I420: the bytes of the file's payloads
         more["frames"], more["yuv_range"] = "yuv420", out_range
     elif codec is not None:                         # the pipeline hands back uint8 frames: no fp32 planes, no torch conversion
@@ -748,27 +763,12 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         torch.cuda.synchronize(device)
         dt = time.perf_counter() - t0
         if codec is None:
-            frames = (255.0 * video.permute(0, 1, 3, 4, 2)).to(torch.uint8).cpu()       # b t c h w -> b t h w c
+            video = (255.0 * video.permute(0, 1, 3, 4, 2)).to(torch.uint8).cpu()        # b t c h w -> b t h w c
         vae.model.clear_cache()
         for seed_idx in range(config.num_samples):
             name = output_name(rank, idx, seed_idx, model_type, config.save_with_index, first_prompt, interactive)
-            if codec is None:
-                path = write_video(os.path.join(config.output_folder, name), frames[seed_idx], fps=16)
-                records.append({"path": path, "idx": idx, "frames": int(frames.shape[1]), "seconds": dt, **extra})
-                continue
-            if codec == "y4m":
-                from . import y4m
-                host = video[seed_idx].cpu().numpy()                                     # I420 [T', bytes]: written frame by frame
-                path = os.path.splitext(os.path.join(config.output_folder, name))[0] + ".y4m"
-                size = y4m.write_y4m(path, iter(host), 8 * wcfg.lat_w, 8 * wcfg.lat_h, fps=16, range=out_range)
-                records.append({"path": path, "idx": idx, "frames": int(host.shape[0]), "seconds": dt, "codec": codec, "bytes": size,
-                                "range": out_range, **extra})
-                continue
-            from . import ops
-            files = ops.jpeg_bytes(*ops.jpeg_encode(video[seed_idx], quality))           # uint8 [T', H, W, 3] on the device
-            path = os.path.splitext(os.path.join(config.output_folder, name))[0] + ".avi"
-            size = write_avi_mjpeg(path, files, int(video.shape[3]), int(video.shape[2]), fps=16)
-            records.append({"path": path, "idx": idx, "frames": len(files), "seconds": dt, "codec": codec, "bytes": size, **extra})
+            path, count, coded = write(os.path.join(config.output_folder, name), video[seed_idx])
+            records.append({"path": path, "idx": idx, "frames": count, "seconds": dt, **coded, **extra})
         if config.inference_iter != -1 and i >= config.inference_iter:
             break
     return records

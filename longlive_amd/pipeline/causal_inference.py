@@ -8,6 +8,7 @@ optional profiler.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
@@ -15,6 +16,7 @@ import torch.nn as nn
 
 from ..scheduler import tag_uniform
 from ..wan_wrapper import WanDiffusionWrapper
+from .frames_out import FRAME_MODES, FramesOut      # noqa: F401  (FRAME_MODES: importable from here as before)
 
 
 class CausalInferencePipeline(nn.Module):
@@ -139,9 +141,9 @@ class CausalInferencePipeline(nn.Module):
                        crossattn_cache=self.crossattn_cache, current_start=start_frame * self.frame_seq_length,
                        **self._kv_only_kw())
 
-    def _side_decoder(self, noise: torch.Tensor, frames: str = "float", yuv_range: str = "limited"):
-        if self.overlap_decode and self.vae is not None and noise.is_cuda and noise.shape[0] == 1:
-            return _SideDecoder(self.vae, frames, yuv_range)
+    def _side_decoder(self, noise: torch.Tensor, out: Optional[FramesOut]):
+        if out is not None and self.overlap_decode and self.vae is not None and noise.is_cuda and noise.shape[0] == 1:
+            return _SideDecoder(self.vae, out)
         return None
 
     def _use_overlap(self, t: torch.Tensor) -> bool:
@@ -202,31 +204,46 @@ class CausalInferencePipeline(nn.Module):
             start += f
         return out
 
-    def _prefill(self, prefix: torch.Tensor, cond):
-        """Yield (start, block) for every prefix block after its clean-context pass -- the one thing a generated block leaves in
-        the caches -- has been queued.  Passes in a row on the aux stream are ordered by that stream.  The main stream JOINS the aux
-        stream behind the last one: the first pass of a run also fills the cross-attention K/V of every layer but the last, and it
-        does so AFTER recording that layer's event (the event marks the last access to the self-attention cache), so the per-layer
-        events alone would let the first denoising forward read text K/V that are still being written.  Generated blocks never meet
-        this: their cross-attention caches were filled by a denoising forward on the main stream."""
-        for start, f in self._prefix_blocks(prefix.shape[1]):
-            block = prefix[:, start:start + f]
-            self._clean_context_pass(block, cond, start)
-            yield start, block
-        self._join_context()
-
-    def _prefill_profiled(self, prefix, cond, noise, prof, frames: str = "float", yuv_range: str = "limited"):
-        """inference()'s prefill: the "prefill" phase of last_profile, the prefix blocks also handed to the side decoder (returned;
-        None without a prefix: nothing is created, queued or timed).  `_prefill` ends with the main stream joined to the aux
-        stream, so the phase's closing event sees the passes and the time is their own, profiled or not."""
-        if prefix is None:
-            return None
-        prof.start("prefill")
-        side = self._side_decoder(noise, frames, yuv_range)
-        for _, block in self._prefill(prefix, cond):
+    def _walk(self, noise, prefix, output, cond, prof: "_Profiler", side_out: Optional[FramesOut] = None, before_block=None):
+        """The one autoregressive walk (`stream`, both `inference`s): yields (start, latents [B, F, 16, h, w]) for every prefix block,
+        once its clean-context pass -- the one thing a generated block leaves in the caches -- is queued, then for every generated block
+        (written into `output` when given) once its own is.  Returns the side decoder (`side_out`: the form it decodes every block in).
+        cond: the conditioning, until `before_block(blk, start, output)`, run before generated block `blk` is queued, returns another.
+        Prefix passes in a row are ordered by the aux stream.  The main stream JOINS it behind the last one: the first pass of a run
+        also fills the cross-attention K/V of every layer but the last, AFTER recording that layer's event (which marks the last access
+        to the self-attention cache), so the events alone would let the first denoising forward read text K/V that are still being
+        written (generated blocks' were filled by a denoising forward on the main stream).  So the "prefill" phase of last_profile,
+        which exists only with a prefix, closes behind the passes and times them alone, profiled or not."""
+        n = 0 if prefix is None else prefix.shape[1]
+        nf, batch_size = self.num_frame_per_block, noise.shape[0]
+        prof.start("diffusion" if prefix is None else "prefill")
+        side = self._side_decoder(noise, side_out)
+        if prefix is not None:
+            for start, f in self._prefix_blocks(n):
+                block = prefix[:, start:start + f]
+                self._clean_context_pass(block, cond, start)
+                if side is not None:
+                    side.push(block)
+                yield start, block
+            self._join_context()
+            prof.stop("prefill")
+            prof.start("diffusion")
+        for blk, off in enumerate(range(0, noise.shape[1], nf)):
+            start = n + off
+            prof.block_start()
+            if before_block is not None:
+                switched = before_block(blk, start, output)
+                cond = cond if switched is None else switched
+            denoised = self._denoise_block(noise[:, off:off + nf], cond, start, batch_size, nf)
+            if output is not None:
+                output[:, start:start + nf] = denoised
+            self._clean_context_pass(denoised, cond, start)
             if side is not None:
-                side.push(block)
-        prof.stop("prefill")
+                side.push(denoised)
+            yield start, denoised
+            prof.block_end()
+        self._join_context()
+        prof.stop("diffusion")
         return side
 
     # ------------------------------------------------------------------------------------------------------------
@@ -239,24 +256,12 @@ class CausalInferencePipeline(nn.Module):
         blocks follow at starts n, n + nf, ...; `output`, when given, holds n + T frames."""
         prefix = self._check_prefix(noise, initial_latent)
         n = 0 if prefix is None else prefix.shape[1]
-        batch_size, num_new_frames = noise.shape[:2]
-        assert num_new_frames % self.num_frame_per_block == 0
+        assert noise.shape[1] % self.num_frame_per_block == 0
         cond = self._encode(text_prompts)
-        self._setup(noise, n + num_new_frames)
-        nf = self.num_frame_per_block
-        if prefix is not None:
-            if output is not None:
-                output[:, :n] = prefix
-            for start, block in self._prefill(prefix, cond):
-                yield start, block
-        for off in range(0, num_new_frames, nf):
-            start = n + off
-            denoised = self._denoise_block(noise[:, off:off + nf], cond, start, batch_size, nf)
-            if output is not None:
-                output[:, start:start + nf] = denoised
-            self._clean_context_pass(denoised, cond, start)
-            yield start, denoised
-        self._join_context()
+        self._setup(noise, n + noise.shape[1])
+        if prefix is not None and output is not None:
+            output[:, :n] = prefix
+        yield from self._walk(noise, prefix, output, cond, _Profiler(False))
 
     @torch.no_grad()
     def stream_video(self, noise: torch.Tensor, text_prompts, output: Optional[torch.Tensor] = None,
@@ -280,42 +285,40 @@ class CausalInferencePipeline(nn.Module):
         those frames as I420, uint8 [B, T', ops.yuv420_bytes(H, W)] in `yuv_range` (limited | full), bit for bit
         ops.frames_u8_to_yuv420 of the "uint8" frames, written by the decoder's last kernel ("Planar YUV and
         Y4M")."""
-        check_frames_mode(frames, jpeg_quality, yuv_range)
+        out = FramesOut(frames, jpeg_quality, yuv_range)
         if self.vae is None:
             raise RuntimeError("stream_video needs a VAE (pass vae= to the pipeline)")
         self.vae.model.clear_cache()
-        pending = None                                   # (start, pixels, event) of the block being decoded on the side stream
-        side = None
+        side = _SideStream(self.vae, out)
+        pending = None                                   # (start, payload, event) of the block being decoded on the side stream
+
+        def handed_over(main):
+            """The pending block, with `main` made to wait for its decode (and its encode)."""
+            ps, pv, pe = pending
+            main.wait_event(pe)
+            out.record_stream(pv, main)
+            return ps, out.deliver(pv)
+
         try:
             for start, latents in self.stream(noise, text_prompts, output=output, initial_latent=initial_latent):
                 if not (overlap_decode and latents.is_cuda):
-                    yield start, _delivered(_decode_frames(self.vae, latents, True, frames, jpeg_quality, yuv_range), frames)
+                    yield start, out.deliver(out.encode(out.decode(self.vae, latents, True)))
                     continue
                 main = torch.cuda.current_stream(latents.device)
-                if side is None:
-                    side = torch.cuda.Stream(device=latents.device)
-                side.wait_stream(main)                   # the block's denoised latents are final (the context pass only reads them)
-                latents.record_stream(side)
-                with torch.cuda.stream(side):            # decodes are ordered among themselves by the side stream (streaming cache)
-                    video = _decode_frames(self.vae, latents, True, frames, jpeg_quality, yuv_range)
+                with side.decoded(latents) as video:     # decodes are ordered among themselves by the side stream (streaming cache)
+                    video = out.encode(video)            # "jpeg": every block is encoded on the stream that decoded it
                     ev = torch.cuda.Event()
-                    ev.record(side)
+                    ev.record(side.stream)
                 if pending is not None:
-                    ps, pv, pe = pending
-                    main.wait_event(pe)
-                    _record_stream(pv, main)
-                    yield ps, _delivered(pv, frames)
+                    yield handed_over(main)
                 pending = (start, video, ev)
             if pending is not None:
-                ps, pv, pe = pending
-                main = torch.cuda.current_stream(side.device)
-                main.wait_event(pe)
-                _record_stream(pv, main)
+                last = handed_over(torch.cuda.current_stream(side.stream.device))
                 pending = None
-                yield ps, _delivered(pv, frames)
+                yield last
         finally:
-            if side is not None:
-                torch.cuda.current_stream(side.device).wait_stream(side)
+            if side.stream is not None:
+                torch.cuda.current_stream(side.stream.device).wait_stream(side.stream)
             self.vae.model.clear_cache()
 
     @torch.no_grad()
@@ -328,56 +331,41 @@ class CausalInferencePipeline(nn.Module):
         "yuv420" as I420 frames uint8 [B, T', ops.yuv420_bytes(H, W)] in `yuv_range` (stream_video).
         initial_latent [B, n, 16, H/8, W/8]: the clip to continue.  `noise` then holds only the T NEW frames; the latents and the
         video cover all n + T frames (1 + 4 (n + T - 1) pixel frames), `[:, :n]` being the prefix itself."""
-        check_frames_mode(frames, jpeg_quality, yuv_range)
+        out = FramesOut(frames, jpeg_quality, yuv_range)
         prefix = self._check_prefix(noise, initial_latent)
-        n = 0 if prefix is None else prefix.shape[1]
-        batch_size, num_new_frames = noise.shape[:2]
-        assert num_new_frames % self.num_frame_per_block == 0
-        num_blocks = num_new_frames // self.num_frame_per_block
+        assert noise.shape[1] % self.num_frame_per_block == 0
         cond = self._encode(text_prompts)
         # low_memory (CPU staging) is pointless with 288 GB of HBM: ignored
-        output = torch.zeros_like(noise) if prefix is None else _timeline(noise, prefix)
+        return self._run(noise, prefix, cond, out, profile, return_latents)
 
+    def _run(self, noise, prefix, cond, out: FramesOut, profile: bool, return_latents: bool, before_block=None, switch_blocks=()):
+        """What both `inference`s do with validated arguments: set-up, the walk, the video, last_profile.  before_block: the walk's;
+        switch_blocks: where it notes the blocks that switched (read when the walk is over)."""
+        n = 0 if prefix is None else prefix.shape[1]
+        output = torch.zeros_like(noise) if prefix is None else _timeline(noise, prefix)
         prof = _Profiler(profile)
         prof.start("init")
-        self._setup(noise, n + num_new_frames)
+        self._setup(noise, n + noise.shape[1])
         prof.stop("init")
-        side = self._prefill_profiled(prefix, cond, noise, prof, frames, yuv_range)
-        prof.start("diffusion")
-        start = n
-        if prefix is None:
-            side = self._side_decoder(noise, frames, yuv_range)
-        for _ in range(num_blocks):
-            nf = self.num_frame_per_block
-            prof.block_start()
-            denoised = self._denoise_block(noise[:, start - n:start - n + nf], cond, start, batch_size, nf)
-            output[:, start:start + nf] = denoised
-            self._clean_context_pass(denoised, cond, start)
-            if side is not None:
-                side.push(denoised)
-            prof.block_end()
-            start += nf
-        self._join_context()
-        prof.stop("diffusion")
+        side = _returned(self._walk(noise, prefix, output, cond, prof, out, before_block))
         prof.start("vae")
-        video = self._finish_video(side, output, frames, jpeg_quality, yuv_range)
+        video = self._finish_video(side, output, out)
         prof.stop("vae")
-        self.last_profile = prof.report(self.num_frame_per_block, switch_blocks=())
+        self.last_profile = prof.report(self.num_frame_per_block, switch_blocks=tuple(switch_blocks))
         if return_latents:
             return video, output
         return video
 
-    def _finish_video(self, side, output, frames: str, jpeg_quality: int, yuv_range: str = "limited"):
-        """inference()'s last step: the side decoder's pieces, or the one-shot decode of the finished latents, in the form `frames`
-        names (None without a VAE)."""
+    def _finish_video(self, side, output, out: FramesOut):
+        """inference()'s last step: the side decoder's pieces -- "jpeg": the finished video is encoded once, on the main stream -- or
+        the one-shot decode of the finished latents, in the form `out` names (None without a VAE)."""
         if side is not None:
             video = side.finish()
-            if video is not None and frames == "jpeg":
-                video = _delivered(_jpeg_pairs(video, jpeg_quality), frames)
-            return video
-        if self.vae is None:
+        elif self.vae is not None:
+            video = out.decode(self.vae, output, False)
+        else:
             return None
-        return _delivered(_decode_frames(self.vae, output, False, frames, jpeg_quality, yuv_range), frames)
+        return None if video is None else out.deliver(out.encode(video))
 
     # ---- cache allocation (causal_inference.py:255-293) ----------------------------------------------------------
     def _initialize_kv_cache(self, batch_size, dtype, device, kv_cache_size_override: Optional[int] = None):
@@ -425,80 +413,62 @@ def _mk(args, name, default):
     return getattr(mk, name, default)
 
 
-FRAME_MODES = ("float", "uint8", "jpeg", "yuv420")
-YUV_RANGES = ("limited", "full")
+def _returned(gen):
+    """Runs a generator to its end and gives what it returned."""
+    while True:
+        try:
+            next(gen)
+        except StopIteration as done:
+            return done.value
 
 
 def check_frames_mode(frames, jpeg_quality=90, yuv_range="limited") -> None:
-    """The `frames=` keyword of stream_video / inference, refused before any launch.  `jpeg_quality` is read by "jpeg" alone,
-    `yuv_range` by "yuv420" alone."""
-    if frames not in FRAME_MODES:
-        raise ValueError(f"frames: {frames!r} is not one of {', '.join(FRAME_MODES)}")
-    if frames == "jpeg" and (isinstance(jpeg_quality, bool) or not isinstance(jpeg_quality, int) or not 1 <= jpeg_quality <= 100):
-        raise ValueError(f"jpeg_quality: {jpeg_quality!r} must be an integer 1..100")
-    if frames == "yuv420" and yuv_range not in YUV_RANGES:
-        raise ValueError(f"yuv_range: {yuv_range!r} is not one of {', '.join(YUV_RANGES)}")
+    """The `frames=` keyword of stream_video / inference, refused before any launch: constructing the FramesOut value is the check."""
+    FramesOut(frames, jpeg_quality, yuv_range)
 
 
-def _jpeg_pairs(video_u8: torch.Tensor, quality: int):
-    """uint8 [B, T', H, W, 3] -> [(buf, sizes) per batch item] of ops.jpeg_encode, on the current stream."""
-    from .. import ops
-    return [ops.jpeg_encode(v, quality) for v in video_u8]
+class _SideStream:
+    """Decoding blocks on a second HIP stream behind the main stream: the stream is made when the first block comes."""
+
+    def __init__(self, vae, out: FramesOut):
+        self.vae, self.out, self.stream = vae, out, None
+
+    @contextlib.contextmanager
+    def decoded(self, latents: torch.Tensor):
+        """`latents`, final on the current (main) stream, decoded on the side stream in the decoder form of `out`; the body still
+        runs on the side stream.  How the result comes back to the main stream is the caller's business."""
+        main = torch.cuda.current_stream(latents.device)
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=latents.device)
+        self.stream.wait_stream(main)                # the block's denoised latents are final (the context pass only reads them)
+        latents.record_stream(self.stream)
+        with torch.cuda.stream(self.stream):
+            yield self.out.decode(self.vae, latents, True)
 
 
-def _decode_frames(vae, latents, use_cache: bool, frames: str, jpeg_quality: int, yuv_range: str = "limited"):
-    """One decode in the form `frames` names, queued on the current stream: pixels in [0, 1], uint8 frames, the (buf, sizes)
-    pairs of their JPEG files, or I420 frames."""
-    if frames == "float":
-        video = vae.decode_to_pixel(latents, use_cache=use_cache)
-        return (video * 0.5 + 0.5).clamp(0, 1)
-    if frames == "yuv420":
-        return vae.decode_to_frames(latents, use_cache=use_cache, frames="yuv420", yuv_range=yuv_range)
-    video = vae.decode_to_frames(latents, use_cache=use_cache)
-    return video if frames == "uint8" else _jpeg_pairs(video, jpeg_quality)
-
-
-def _record_stream(payload, stream) -> None:
-    for t in ([payload] if torch.is_tensor(payload) else [t for pair in payload for t in pair]):
-        t.record_stream(stream)
-
-
-def _delivered(payload, frames: str):
-    """What the caller gets: tensors as they are, JPEG pairs as [[bytes per frame] per batch item] (the one host read)."""
-    if frames != "jpeg":
-        return payload
-    from .. import ops
-    return [ops.jpeg_bytes(buf, sizes) for buf, sizes in payload]
-
-
-class _SideDecoder:
+class _SideDecoder(_SideStream):
     """inference() with overlap_decode: every finished block goes through the VAE's streaming decode on a second HIP stream while
     the next block is generated; the pieces concatenated equal the one-shot decode of the finished latents bit for bit
-    (tests/test_vae_gpu.py).  Batch 1 only (the streaming cache holds one stream).  frames "uint8" / "jpeg": the pieces are uint8
-    frames [1, T', H, W, 3] (inference() encodes the finished video).  frames "yuv420": the pieces are I420 frames [1, T', bytes]
-    already; either way they concatenate along dim 1."""
+    (tests/test_vae_gpu.py).  Batch 1 only (the streaming cache holds one stream).  The pieces are in the decoder form of `out` --
+    pixels [1, T', 3, H, W], uint8 frames [1, T', H, W, 3] ("jpeg" too: inference() encodes the finished video) or I420 frames
+    [1, T', bytes] -- and concatenate along dim 1."""
 
-    def __init__(self, vae, frames: str = "float", yuv_range: str = "limited"):
-        self.vae, self.pieces, self.side = vae, [], None
-        self.frames = frames if frames in ("float", "yuv420") else "uint8"
-        self.yuv_range = yuv_range
+    def __init__(self, vae, out: FramesOut):
+        super().__init__(vae, out)
+        self.pieces = []
         vae.model.clear_cache()
 
     def push(self, latents: torch.Tensor):
-        main = torch.cuda.current_stream(latents.device)
-        if self.side is None:
-            self.side = torch.cuda.Stream(device=latents.device)
-        self.side.wait_stream(main)
-        latents.record_stream(self.side)
-        with torch.cuda.stream(self.side):
-            self.pieces.append(_decode_frames(self.vae, latents, True, self.frames, 0, self.yuv_range))
+        with self.decoded(latents) as piece:
+            self.pieces.append(piece)
 
     def finish(self) -> Optional[torch.Tensor]:
-        if self.side is None:                       # no block was pushed
+        side = self.stream
+        if side is None:                            # no block was pushed
             self.vae.model.clear_cache()
             return None
-        main = torch.cuda.current_stream(self.side.device)
-        main.wait_stream(self.side)
+        main = torch.cuda.current_stream(side.device)
+        main.wait_stream(side)
         for p in self.pieces:
             p.record_stream(main)
         video = torch.cat(self.pieces, 1)

@@ -6,7 +6,8 @@ from typing import List, Optional
 
 import torch
 
-from .causal_inference import CausalInferencePipeline, _Profiler, _timeline, check_frames_mode
+from .causal_inference import CausalInferencePipeline
+from .frames_out import FramesOut
 
 
 class InteractiveCausalInferencePipeline(CausalInferencePipeline):
@@ -56,50 +57,22 @@ class InteractiveCausalInferencePipeline(CausalInferencePipeline):
         text_prompts_list[0].  Frame numbers -- the switch indices too -- count on the n + T timeline and only GENERATED blocks
         switch: an index <= n switches at the first generated block, whose recache then re-encodes prefix frames under the new prompt.
         frames: the form of the video, as in CausalInferencePipeline.inference."""
-        check_frames_mode(frames, jpeg_quality, yuv_range)
+        out = FramesOut(frames, jpeg_quality, yuv_range)
         prefix = self._check_prefix(noise, initial_latent)
-        n = 0 if prefix is None else prefix.shape[1]
-        batch_size, num_output_frames = noise.shape[:2]
         assert len(text_prompts_list) >= 1, "text_prompts_list must not be empty"
         assert len(switch_frame_indices) == len(text_prompts_list) - 1, (
             "length of switch_frame_indices should be one less than text_prompts_list")
-        assert num_output_frames % self.num_frame_per_block == 0
-        num_blocks = num_output_frames // self.num_frame_per_block
+        assert noise.shape[1] % self.num_frame_per_block == 0
         cond_list = [self._encode(p) for p in text_prompts_list]
-        output = torch.zeros_like(noise) if prefix is None else _timeline(noise, prefix)
+        switch_blocks = []
 
-        prof = _Profiler(profile)
-        prof.start("init")
-        self._setup(noise, n + num_output_frames)
-        prof.stop("init")
-        side = self._prefill_profiled(prefix, cond_list[0], noise, prof, frames, yuv_range)
-        prof.start("diffusion")
-        seg, start, switch_blocks = 0, n, []
-        next_switch = switch_frame_indices[0] if switch_frame_indices else None
-        if prefix is None:
-            side = self._side_decoder(noise, frames, yuv_range)
-        for blk in range(num_blocks):
-            nf = self.num_frame_per_block
-            prof.block_start()
-            if next_switch is not None and start >= next_switch:
-                seg += 1
-                self._recache_after_switch(output, start, cond_list[seg])
-                switch_blocks.append(blk)
-                next_switch = switch_frame_indices[seg] if seg < len(switch_frame_indices) else None
-            cond = cond_list[seg]
-            denoised = self._denoise_block(noise[:, start - n:start - n + nf], cond, start, batch_size, nf)
-            output[:, start:start + nf] = denoised
-            self._clean_context_pass(denoised, cond, start)
-            if side is not None:
-                side.push(denoised)
-            prof.block_end()
-            start += nf
-        self._join_context()
-        prof.stop("diffusion")
-        prof.start("vae")
-        video = self._finish_video(side, output, frames, jpeg_quality, yuv_range)
-        prof.stop("vae")
-        self.last_profile = prof.report(self.num_frame_per_block, switch_blocks=tuple(switch_blocks))
-        if return_latents:
-            return video, output
-        return video
+        def before_block(blk, start, output):
+            """The next segment's turn: its conditioning, after the recache under it (None: the block continues the segment)."""
+            seg = len(switch_blocks)                # one switch per segment so far
+            if seg == len(switch_frame_indices) or start < switch_frame_indices[seg]:
+                return None
+            self._recache_after_switch(output, start, cond_list[seg + 1])
+            switch_blocks.append(blk)
+            return cond_list[seg + 1]
+
+        return self._run(noise, prefix, cond_list[0], out, profile, return_latents, before_block, switch_blocks)

@@ -459,16 +459,16 @@ class WanVAEWrapper(nn.Module):
                 self.encoder.load_state_dict(enc, strict=False)
         return self.model.load_state_dict(sd, strict=strict)
 
-    def _decode(self, latent: torch.Tensor, use_cache: bool, frames: str, yuv_range: str = "limited") -> torch.Tensor:
+    def _decode(self, latent: torch.Tensor, use_cache: bool, frames: str, yuv_range: str) -> torch.Tensor:
+        """`frames` / `yuv_range` are the model's to check (WanVAEDecoderHIP.decode reads the range for "yuv420" alone)."""
         if latent.dtype != bf16:
             latent = latent.to(bf16)
         if use_cache:      # ONE streaming feature cache: a second sample would continue the first one's stream
             assert latent.shape[0] == 1, "Batch size must be 1 when using cache"          # utils/wan_wrapper.py:99
-        more = {"yuv_range": yuv_range} if frames == "yuv420" else {}
-        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames=frames, **more) for u in latent], 0)
+        return torch.stack([self.model.decode(u, keep_cache=use_cache, frames=frames, yuv_range=yuv_range) for u in latent], 0)
 
     def decode_to_pixel(self, latent: torch.Tensor, use_cache: bool = False) -> torch.Tensor:
-        return self._decode(latent, use_cache, "float")
+        return self._decode(latent, use_cache, "float", "limited")
 
     def decode_to_frames(self, latent: torch.Tensor, use_cache: bool = False, frames: str = "uint8",
                          yuv_range: str = "limited") -> torch.Tensor:
