@@ -432,7 +432,9 @@ int ll_flash_attn_qnorm(const ll_bf16* q, const float* ssq, const ll_bf16* norm_
  *       one contiguous range after merging adjacent ones, that range is long enough for it (tuning key attn_asm_min_keys, at least
  *       two key tiles), H is even for LL_QFMT_MX6 / MX4.  Otherwise 0, and the caller runs ll_flash_attn + ll_quantize_<fmt>:
  *   ll_flash_attn_q returns LL_ERR_INVALID_ARG where ll_flash_attn_q_ok is 0 (no fall-back inside the library).  ldc: a multiple of
- *       16 bytes, lds: a multiple of 4.
+ *       16 bytes, at least the row's H*16*bits bytes; lds: a multiple of 4, at least 4*H; ldq and ldk (elements): multiples of 8, at
+ *       least H*128; k_batch_stride in elements, the ranges may not overlap.  ll_flash_attn_q_ok assumes ldk = H*128: with wider key
+ *       rows the call also needs seg_len * ldk * 2 bytes below 2^31.  A refused call launches nothing and writes nothing.
  *   ll_flash_attn_q_plan: the kernel and grid of such a launch, or that it is not covered (host only).
  *   ll_flash_attn_mx_q: ll_flash_attn_mx with the same output forms; every launch ll_flash_attn_mx takes is covered (even H for the
  *       packed formats). */

@@ -34,7 +34,8 @@ NPROBE = 9
 # Data seeds: the first seed (from 1) at which no expected element of the case lies within 3 fp32 ulp of a bf16 rounding tie
 # (tests/test_mx_attn_edges_host.py asserts it); unlisted cases use 1.
 SEEDS = {"s0n63": 3, "s0n65": 2, "s0n129": 3, "s1n32": 5, "s31n32": 4, "s31n64": 4, "s96n31": 3, "s96n65": 3, "s33n32": 2, "s33n64": 2,
-         "s127n31": 3, "s127n63": 2, "s127n64": 5, "clamp_S90_two": 2, "two_share_block": 5, "batch2_heads3": 4}
+         "s127n31": 3, "s127n63": 2, "s127n64": 5, "clamp_S90_two": 2, "two_share_block": 5, "batch2_heads3": 4,
+         "q_batch2_heads4": 4, "q_heads12": 29, "q_s31n65_h2": 4}
 
 
 class Case:
@@ -326,6 +327,15 @@ RANDOM = {          # one random-data case per geometry class: (B, Lq, H, S, seg
 }
 
 EXACT_CASES = GEOMETRY + ENDS + TWO + ZERO + LAZY + [ROWS, BATCH]
+
+# Even head counts, for the packed output formats of ll_flash_attn_mx_q (they pair heads in a super-block; every case above has
+# H = 1 or 3 and serves the 8-bit format as it is): ROWS and BATCH again, one clamp case, H = 12, two single-range sweeps
+QOUT_ROWS = _sweep("q_rows_h2", 1, 257, 2, 160, [(1, 40), (50, 131)])
+QOUT_BATCH = _sweep("q_batch2_heads4", 2, 129, 4, 200, [(130, 199), (31, 97)])
+QOUT_EVEN = [
+    QOUT_ROWS, QOUT_BATCH, _sweep("q_clamp_S96_h2", 1, 33, 2, 96, [(70, 96)]), _sweep("q_heads12", 1, 33, 12, 200, [(33, 130)]),
+    _sweep("q_s31n65_h2", 1, 33, 2, 166, [(31, 96)]), _sweep("q_s33n129_h2", 1, 33, 2, 232, [(33, 162)]),
+]
 
 
 def random_data(B, Lq, H, S, seed=23):

@@ -19,7 +19,7 @@ from longlive_amd import _lib
 KERNEL_BOUND = 3e-3          # tests/test_mx_attn_gpu.py's
 
 
-@pytest.mark.parametrize("case", X.EXACT_CASES, ids=repr)
+@pytest.mark.parametrize("case", X.EXACT_CASES + X.QOUT_EVEN, ids=repr)
 def test_case_is_exact_in_any_order(case):
     b = X.Built.get(case)
     # operands: the shadows and Q^ dequantise to the bf16 inputs
@@ -38,7 +38,7 @@ def test_case_is_exact_in_any_order(case):
     assert X.tie_distance(b.want32).min().item() > 3
 
 
-@pytest.mark.parametrize("case", X.EXACT_CASES, ids=repr)
+@pytest.mark.parametrize("case", X.EXACT_CASES + X.QOUT_EVEN, ids=repr)
 def test_restatement_vs_independent_fp64_softmax(case):
     b = X.Built.get(case)
     out, bound = X.rounding_error_bound(b)
@@ -103,7 +103,7 @@ def test_lazy_reference_moves_where_the_constructions_say():
             assert top == [1.0, 1.0, 256.0]
 
 
-@pytest.mark.parametrize("case", X.EXACT_CASES, ids=repr)
+@pytest.mark.parametrize("case", X.EXACT_CASES + X.QOUT_EVEN, ids=repr)
 def test_plan_counts(case):
     from longlive_amd import ops
     nt, nr = case.plan_counts()
@@ -121,6 +121,15 @@ def test_geometry_lists_cover_what_they_claim():
             assert (c.S32 // 32) % 2 == 1 and c.segs[0][0] // 32 == c.S32 // 32 - 1, c
     shared = next(c for c in X.TWO if c.name == "two_share_block")
     assert shared.segs[0][1] // 32 == shared.segs[1][0] // 32
+    # the even-head list of the packed output formats: ROWS and BATCH again, a clamp case, H = 12, sweeps from 31 and 33
+    assert all(c.H % 2 == 0 for c in X.QOUT_EVEN) and {c.H for c in X.QOUT_EVEN} == {2, 4, 12}
+    assert (X.QOUT_ROWS.Lq, X.QOUT_ROWS.S, X.QOUT_ROWS.segs) == (X.ROWS.Lq, X.ROWS.S, X.ROWS.segs)
+    assert (X.QOUT_BATCH.B, X.QOUT_BATCH.Lq, X.QOUT_BATCH.segs) == (X.BATCH.B, X.BATCH.Lq, X.BATCH.segs)
+    assert X.QOUT_BATCH.segs[0][0] > X.QOUT_BATCH.segs[1][0]                  # two ranges in reverse order
+    clamp = [c for c in X.QOUT_EVEN if "clamp" in c.name]
+    assert clamp and all((c.S32 // 32) % 2 == 1 and c.segs[0][0] // 32 == c.S32 // 32 - 1 for c in clamp)
+    assert {c.segs[0][0] for c in X.QOUT_EVEN if len(c.segs) == 1 and c.H == 2} >= {31, 33}
+    assert any(c.H == 12 and c.Lq == 33 for c in X.QOUT_EVEN)
 
 
 # ---- refusals: nothing is launched (no GPU here), the message names the argument --------------------------------------------------
