@@ -1,6 +1,6 @@
 """Data of the code-emitting attention edge suites (plain helpers, no tests): an exact "picked row" construction for the generated
 kernels flash_attn_asm_mx / mx6 / mx4_kernel over a geometry (B, Lq, H, [(start, len)...]), and the geometry list.  The formats, the
-host quantisers (QUANT), the packed-row layout (head_code_bytes, expected) and the edge blocks are tests/test_attn_asm_qout_emu.py's;
+host quantisers (QUANT), the packed-row layout (head_code_bytes, expected) and the edge blocks are tests/attn_qout_emu.py's;
 nothing of them is restated here.
 
 Every in-range key slot j of (b, head) carries its own +-1 pattern s_j of 128 entries, k_j = 20 s_j; query row r picks the slot
@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 import bf16_exact
-from test_attn_asm_qout_emu import BITS, QUANT, bf16_bits, bf16_val, edge_blocks, head_code_bytes  # noqa: F401  (re-exported)
+from attn_qout_emu import BITS, QUANT, bf16_bits, bf16_val, edge_blocks, head_code_bytes  # noqa: F401  (re-exported)
+from longlive_amd import synth
 
 D = 128
 KT = 64
@@ -47,6 +48,17 @@ QOUT_ASM_ODD = [(1, 33, 1, [(63, 512)]), (1, 33, 3, [(1, 129)]), (1, 257, 1, [(6
 
 EDGE_COMBOS = [("zero", 0), ("clamp", 0), ("amax_at_max", 0), ("amax_one_ulp_above", 0), ("amax_one_ulp_below", 0), ("clamp", 4),
                ("amax_at_max", 4), ("amax_one_ulp_above", 4), ("amax_one_ulp_below", 4), ("zero", 0)]
+
+
+def hash_qkv(tag, B, Lq, H, Sk, dev="cuda"):
+    """Hash q [B, Lq, H, 128], k and v [B, Sk, H, 128] (bf16, on dev): V with block maxima over several binades and exact zeros, so
+    scale bytes, subnormal codes and zero codes all occur."""
+    def hn(name, shape):
+        return synth.hash_normal(151, name, shape).to(torch.bfloat16).to(dev)
+    v = synth.hash_normal(151, tag + "v", (B, Sk, H, 128)) * torch.exp2(torch.arange(B * Sk * H * 4).view(B, Sk, H, 4).remainder(9).sub(4).float()
+                                                                        ).repeat_interleave(32, -1)
+    v[..., ::7] = 0.0
+    return hn(tag + "q", (B, Lq, H, 128)), hn(tag + "k", (B, Sk, H, 128)), v.to(torch.bfloat16).to(dev)
 
 
 def case_id(g):

@@ -248,3 +248,25 @@ QNORM_CASES = [      # flash_attn_asm_qn_kernel: the gather through ll_flash_att
     (2, 257, 3, [(64, 128)]), (1, 328, 12, [(1, 1437)]),
 ]
 ALL_SMALL_CASES = PIPE0_CASES + PIPE1_CASES + ASM_CASES + TWO_RANGE_CASES + PLAIN_ONE_RANGE_CASES + ADJACENT_CASES
+
+
+# ---- plumbing of the edge suites that call the C entry points directly ------------------------------------------------------------------
+def lib():
+    from longlive_amd import _lib as L
+    return L, L.load()
+
+
+def run(fn, *args):
+    """A C entry point with tensors as device pointers (None = NULL) and the current stream appended; a nonzero return raises."""
+    from longlive_amd import ops as O
+    L, l = lib()
+    a = [t.data_ptr() if isinstance(t, torch.Tensor) else t for t in args]
+    L.check(getattr(l, fn)(*a, O._stream()), fn)
+
+
+def nan_bf16(*shape):
+    return torch.full(shape, NAN16, dtype=torch.int16, device="cuda").view(torch.bfloat16)
+
+
+def untouched_bf16(t):
+    return bool((t.contiguous().view(torch.int16) == NAN16).all())

@@ -6,14 +6,12 @@
   * y = bf16(acc * (sx[m] * sw[n]) + bias) with acc = sum_k dec(xq[m, k]) dec(wq[n, k]) (fp32), then the epilogue's tail -- the
     rounding points of the oracle's int8 linears (oracle/ref_model.py RefModel.lin).
 
-Fp8RefModel is the oracle's RefModel with the six per-token block linears on that scheme (the oracle itself is untouched)."""
+tests/quant_ref.py puts the oracle's six per-token block linears on this scheme (mode "fp8_rowwise")."""
 from typing import Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
-
-from oracle import ref_model as RM
 
 FP8 = torch.float8_e4m3fn
 MAX = 448.0
@@ -62,20 +60,3 @@ def f8_linear(x: Tensor, wq: Tensor, sw: Tensor, bias: Tensor) -> Tensor:
     acc = (decode(xq) @ decode(wq).t()).float()          # products of two e4m3 values are exact; the fp32 sum is the kernel's to ~1 ulp
     y = acc * (sx.float().unsqueeze(1) * sw.float().unsqueeze(0)) + bias.float()
     return y.to(torch.bfloat16)
-
-
-class Fp8RefModel(RM.RefModel):
-    """RefModel whose six per-token block linears (self_attn q/k/v/o, cross_attn q/o, ffn.0, ffn.2) run FP8 rowwise."""
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self._wf8 = {}
-
-    def lin(self, x: Tensor, name: str) -> Tensor:
-        if not (name.startswith("blocks.") and name.endswith(self._W8A8)):
-            return super().lin(x, name)
-        assert name not in self.lora
-        if name not in self._wf8:
-            self._wf8[name] = quantize(self.sd[name + ".weight"])
-        y = f8_linear(x.to(self.dtype).reshape(-1, x.shape[-1]), *self._wf8[name], self.sd[name + ".bias"])
-        return y.to(self.dtype).reshape(*x.shape[:-1], -1)

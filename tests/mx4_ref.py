@@ -11,14 +11,13 @@
     GEMM's epilogues.
 
 The rounding here is a nearest-value search over the 8 magnitudes in float64, independent of the kernels' integer bit arithmetic.
-Mx4a6RefModel is Mx6RefModel with E2M1-dequantised weights (the oracle itself is untouched)."""
+tests/quant_ref.py puts the oracle's six per-token block linears on this scheme: mode "mxfp4_a6" (these weights, MXFP6 activations)
+and mode "mxfp4_a4" (this scheme on both sides)."""
 from typing import Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
-
-import mx6_ref
 
 BLOCK = 32
 SUPER = 256
@@ -97,12 +96,3 @@ def dequantize(packed: Tensor, scales: Tensor) -> Tensor:
     K = c.shape[-1]
     s = torch.pow(2.0, scales.cpu().double() - 127).reshape(c.shape[0], K // BLOCK, 1)
     return (c.reshape(-1, K // BLOCK, BLOCK) * s).reshape(-1, K)
-
-
-class Mx4a6RefModel(mx6_ref.Mx6RefModel):
-    """Mx6RefModel whose six per-token block linears take E2M1-dequantised weights (activations stay MXFP6)."""
-
-    def lin(self, x: Tensor, name: str) -> Tensor:
-        if name.startswith("blocks.") and name.endswith(self._W8A8) and name not in self._wmx6:
-            self._wmx6[name] = dequantize(*quantize(self.sd[name + ".weight"]))
-        return super().lin(x, name)

@@ -10,14 +10,12 @@
   * y = epilogue(sum_k (cx 2^ex)(cw 2^ew) + bias) in fp32, written as bf16 by the bf16 GEMM's epilogues.
 
 The rounding here is a nearest-value search over the 32 magnitudes in float64, independent of the kernels' integer bit arithmetic.
-Mx6RefModel is the oracle's RefModel with the six per-token block linears on that scheme (the oracle itself is untouched)."""
+tests/quant_ref.py puts the oracle's six per-token block linears on this scheme (mode "mxfp6")."""
 from typing import Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
-
-from oracle import ref_model as RM
 
 BLOCK = 32
 SUPER = 256
@@ -114,21 +112,3 @@ def dequantize(packed: Tensor, scales: Tensor) -> Tensor:
 def mx6_matmul(x: Tensor, w_deq: Tensor) -> Tensor:
     """fp64 sum of the dequantised products: x bf16 [..., K] quantised here, w_deq [N, K] fp64."""
     return dequantize(*quantize(x.reshape(-1, x.shape[-1]))) @ w_deq.t()
-
-
-class Mx6RefModel(RM.RefModel):
-    """RefModel whose six per-token block linears (self_attn q/k/v/o, cross_attn q/o, ffn.0, ffn.2) run MXFP6."""
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self._wmx6 = {}
-
-    def lin(self, x: Tensor, name: str) -> Tensor:
-        if not (name.startswith("blocks.") and name.endswith(self._W8A8)):
-            return super().lin(x, name)
-        assert name not in self.lora
-        if name not in self._wmx6:
-            self._wmx6[name] = dequantize(*quantize(self.sd[name + ".weight"]))
-        acc = mx6_matmul(x.to(self.dtype), self._wmx6[name]).float()
-        y = acc + self.sd[name + ".bias"].float()
-        return y.to(self.dtype).reshape(*x.shape[:-1], -1)

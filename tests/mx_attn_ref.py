@@ -12,16 +12,17 @@ ll_flash_attn_mx).  The MX rule is tests/mx_ref.py's.
   * P^ = e4m3fn(RNE(exp2(c s - M))) (unit scale: P <= 2^8 < 448), l = sum P^, O = sum P^ V^, output bf16(O / l).
 
 The kernel and this restatement differ only by the fp32 summation order and v_exp_f32's ulp.
-MXAttnRefModel is the oracle's RefModel (optionally with tests/mx_ref.py's MX block linears) with self-attention on this scheme."""
+MXAttnRefModel is the oracle's RefModel (optionally with tests/quant_ref.py's quantised block linears) with self-attention on this
+scheme."""
 import math
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 import mx_ref
-from oracle import ref_model as RM
 from oracle import ref_ops as R
+from quant_ref import QuantRefModel
 
 FP8 = torch.float8_e4m3fn
 KT = 64
@@ -170,19 +171,13 @@ def mx_attention_cache(q: Tensor, k: Tensor, v: Tensor, segments, scale: float =
     return mx_attention(q, kd, vd, segments, scale, dtype, rcp)
 
 
-class MXAttnRefModel(mx_ref.MXRefModel):
-    """RefModel with self-attention on the MX shadow scheme.  mx_linears: also the six MX block linears (set_quant("mxfp8")),
-    otherwise the bf16 linears of the oracle.  The cache is the oracle's (bf16 k / v written as RefModel writes them); attention
-    reads it through the shadow with ABSOLUTE slot indices, so the V^ blocks are the kernel's."""
+class MXAttnRefModel(QuantRefModel):
+    """RefModel with self-attention on the MX shadow scheme.  linears: the mode of the six block linears (a set_quant name that
+    tests/quant_ref.py restates), or None for the bf16 linears of the oracle.  The cache is the oracle's (bf16 k / v written as
+    RefModel writes them); attention reads it through the shadow with ABSOLUTE slot indices, so the V^ blocks are the kernel's."""
 
-    def __init__(self, *a, mx_linears: bool = False, **kw):
-        super().__init__(*a, **kw)
-        self.mx_linears = mx_linears
-
-    def lin(self, x: Tensor, name: str) -> Tensor:
-        if self.mx_linears:
-            return super().lin(x, name)
-        return RM.RefModel.lin(self, x, name)
+    def __init__(self, *a, linears: Optional[str] = None, **kw):
+        super().__init__(*a, mode=linears, **kw)
 
     def self_attn(self, x: Tensor, p: str, grid, kv_cache: dict, current_start: int, sink_recache_after_switch: bool):
         c = self.cfg

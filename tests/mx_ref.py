@@ -6,13 +6,11 @@
   * codes = e4m3fn(RNE(x 2^-e)), OCP e4m3fn, subnormals kept, saturating at +-448 (reached only under the clamp);
   * y = epilogue(sum_k (cx 2^ex)(cw 2^ew) + bias) in fp32, written as bf16 by the bf16 GEMM's epilogues.
 
-MXRefModel is the oracle's RefModel with the six per-token block linears on that scheme (the oracle itself is untouched)."""
+tests/quant_ref.py puts the oracle's six per-token block linears on this scheme (mode "mxfp8")."""
 from typing import Tuple
 
 import torch
 from torch import Tensor
-
-from oracle import ref_model as RM
 
 FP8 = torch.float8_e4m3fn
 BLOCK = 32
@@ -47,21 +45,3 @@ def dequantize(codes: Tensor, scales: Tensor) -> Tensor:
 def mx_matmul(x: Tensor, w_deq: Tensor) -> Tensor:
     """fp64 sum of the dequantised products: x bf16 [..., K] quantised here, w_deq [N, K] fp64."""
     return dequantize(*quantize(x.reshape(-1, x.shape[-1]))) @ w_deq.t()
-
-
-class MXRefModel(RM.RefModel):
-    """RefModel whose six per-token block linears (self_attn q/k/v/o, cross_attn q/o, ffn.0, ffn.2) run MXFP8."""
-
-    def __init__(self, *a, **kw):
-        super().__init__(*a, **kw)
-        self._wmx = {}
-
-    def lin(self, x: Tensor, name: str) -> Tensor:
-        if not (name.startswith("blocks.") and name.endswith(self._W8A8)):
-            return super().lin(x, name)
-        assert name not in self.lora
-        if name not in self._wmx:
-            self._wmx[name] = dequantize(*quantize(self.sd[name + ".weight"]))
-        acc = mx_matmul(x.to(self.dtype), self._wmx[name]).float()
-        y = acc + self.sd[name + ".bias"].float()
-        return y.to(self.dtype).reshape(*x.shape[:-1], -1)

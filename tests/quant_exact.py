@@ -42,6 +42,19 @@ def epi_tail(v, epi, res=None, e=None, mod=None, gate_idx=0, fs=1):
     return (res.float() + gv.float()).to(bf)
 
 
+def epi_ref(acc, bias, epi, *tail, **kw):
+    """The bf16 epilogues' rounding points on the fp64 accumulator (ll_gemm_bf16): the bias output, then its tail."""
+    return epi_tail((acc.float() + bias.float()).to(bf), epi, *tail, **kw)
+
+
+def within_1ulp(got, want):
+    """Every element within 1 bf16 ulp of want, or within 2^-8 of want's RMS (elements near zero)."""
+    from util import bf16_ulp_distance
+    d = bf16_ulp_distance(got.cpu(), want)
+    atol = want.float().pow(2).mean().sqrt().item() * 2 ** -8
+    return bool(((d <= 1) | ((got.cpu().float() - want.float()).abs() <= atol)).all())
+
+
 def hard_x_mx(rows, K, seed):
     """Gaussian rows with x100 outlier channels, a few all-zero blocks, and blocks of tiny values next to a large one (codes in the
     e4m3 subnormal range) or entirely tiny (bf16 subnormals, exponent clamped)."""

@@ -18,8 +18,7 @@ import torch
 import attn_qout_exact as Q
 import mx_attn_exact as X
 from quant_exact import unit_c_scale
-from test_attn_asm_qout_emu import BITS, QUANT
-from test_attn_qout_gpu import _qkv
+from attn_qout_emu import BITS, QUANT
 from util import bf
 
 pytestmark = pytest.mark.gpu
@@ -155,7 +154,7 @@ def random_rows(ops):
         key = (Q.case_id(geom), scale)
         if key not in cache:
             p = Q.Picked.get(geom, "mx")
-            q, k, v = _qkv("qe" + Q.case_id(geom), p.B, p.Lq, p.H, p.Sk)
+            q, k, v = Q.hash_qkv("qe" + Q.case_id(geom), p.B, p.Lq, p.H, p.Sk)
             with min_keys(128):
                 rows = ops.flash_attn(q, k, v, p.segments(), scale=scale).view(p.B, p.Lq, p.H * 128)
             cache[key] = (q, k, v, rows)

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import attn_qout_exact as Q
-from test_attn_asm_qout_emu import BITS, G, QUANT, SENT, expected, head_code_bytes, run
+from attn_qout_emu import BITS, G, QUANT, SENT, expected, head_code_bytes, run
 
 ALL = [(g, f) for g in Q.QOUT_ASM_CASES for f in Q.FMTS] + [(g, "mx") for g in Q.QOUT_ASM_ODD]
 _ids = lambda v: Q.case_id(v) if isinstance(v, tuple) else str(v)

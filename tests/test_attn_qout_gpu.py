@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_qout_exact import hash_qkv as _qkv
 from longlive_amd import _lib, synth
 from util import bf
 
@@ -60,15 +61,6 @@ def _u8(t):
 def _same(got, want, what):
     assert torch.equal(_u8(got[1]).reshape(-1), _u8(want[1]).reshape(-1)), what + ": scales"
     assert torch.equal(_u8(got[0]).reshape(-1), _u8(want[0]).reshape(-1)), what + ": codes"
-
-
-def _qkv(tag, B, Lq, H, Sk):
-    q, k = hn(tag + "q", (B, Lq, H, 128)), hn(tag + "k", (B, Sk, H, 128))
-    # V with block maxima over several binades and exact zeros, so scale bytes, subnormal codes and zero codes all occur
-    v = synth.hash_normal(151, tag + "v", (B, Sk, H, 128)) * torch.exp2(torch.arange(B * Sk * H * 4).view(B, Sk, H, 4).remainder(9).sub(4).float()
-                                                                        ).repeat_interleave(32, -1)
-    v[..., ::7] = 0.0
-    return q, k, v.to(bf).to(DEV)
 
 
 def _raw_q(lib, fmt, q, k, v, segs, scale=None):
@@ -133,10 +125,10 @@ def test_generated_kernel_writes_the_quantiser_bytes(ops, bf16_rows, fmt, shape)
 
 @pytest.mark.parametrize("fmt", FMTS)
 def test_edge_values_through_one_hot_rows(ops, fmt):
-    """tests/test_attn_asm_qout_emu.py's construction (every output row is a chosen V row: all-zero blocks, amax at, one ulp above
+    """tests/attn_qout_emu.py's construction (every output row is a chosen V row: all-zero blocks, amax at, one ulp above
     and below the largest code, ties, values that round to the smallest subnormal code and to zero, a block whose exponent clamps
     at -127, one row of halved values) on the device."""
-    from test_attn_asm_qout_emu import one_hot_case
+    from attn_qout_emu import one_hot_case
     qb, kb, vb, rows, nkeys, pos = one_hot_case(fmt)
 
     def t(bits):
@@ -263,7 +255,7 @@ def test_toy_model_is_bit_identical_with_the_fusion_on_and_off(ops, lin, attn):
 def test_real_width_block_is_bit_identical_with_the_fusion_on_and_off(ops):
     """dim 1536, 12 heads, three frames (L = 4680) in steady state (roll + insert, keys = [sink | window]) in mxfp4_a4"""
     from longlive_amd.model import CausalWanModelHIP
-    from test_shipped_sizes_gpu import _kv_fill
+    from model_runs import kv_fill as _kv_fill
     cfg = synth.longlive_1_3b(num_layers=1)
     fs, S = cfg.frame_seqlen, 12 * cfg.frame_seqlen
     sd = synth.synth_state_dict(cfg, seed=0, device=DEV, layers=[0])

@@ -22,6 +22,10 @@ import torch
 import torch.nn.functional as Fn
 
 import bf16_exact as E
+from bf16_exact import lib as _lib
+from bf16_exact import nan_bf16 as _nan_bf16
+from bf16_exact import run as _run
+from bf16_exact import untouched_bf16 as _untouched_bf16
 from quant_exact import epi_tail
 from util import bf, bf16_ulp_distance
 
@@ -35,19 +39,6 @@ SCALE = 1.0 / math.sqrt(128)
 
 
 # ---- plumbing -------------------------------------------------------------------------------------------------------------------------
-def _lib():
-    from longlive_amd import _lib as L
-    return L, L.load()
-
-
-def _run(fn, *args):
-    """A C entry point with tensors as device pointers (None = NULL) and the current stream appended; a nonzero return raises."""
-    from longlive_amd import ops as O
-    L, lib = _lib()
-    a = [t.data_ptr() if isinstance(t, torch.Tensor) else t for t in args]
-    L.check(getattr(lib, fn)(*a, O._stream()), fn)
-
-
 def _tune(**kv):
     L, lib = _lib()
     for k, v in kv.items():
@@ -74,14 +65,6 @@ def _plan_epi(M, N, K, epi, plain=1):
 
 def _attn_plan(B, Lq, H, n0, n1=0, adjacent=0):
     return _text("ll_flash_attn_plan", Lq, H, B, n0, n1, adjacent)
-
-
-def _nan_bf16(*shape):
-    return torch.full(shape, NAN16, dtype=torch.int16, device=DEV).view(bf)
-
-
-def _untouched_bf16(t):
-    return bool((t.contiguous().view(torch.int16) == NAN16).all())
 
 
 def _assert_gelu_close(got, want, what):

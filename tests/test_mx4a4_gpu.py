@@ -2,30 +2,24 @@
 the scheme's definition (tests/mx4_ref.py, tests/mx4a4_ref.py): the lane map with exact data on both sides, every epilogue and the QKV
 cache slots bit for bit against ll_gemm_mx4w6 on the same activations re-encoded as E2M3 under the same scale bytes (every E2M1 value
 is an E2M3 value), the MXFP4 outputs of the FFN1 epilogue and the producers against ll_quantize_mx4, random data against the fp64
-product of the dequantised operands (a bound ll_gemm_mx4w6 fails), one real-shape block against Mx4a4RefModel, the 30-layer steady
-state and config 2 free-running against the reference's bf16 goldens, and the mode beside MX self-attention."""
+product of the dequantised operands (a bound ll_gemm_mx4w6 fails).  The mode at model level (its weight packs equal mxfp4_a6's, one
+real-shape block against its oracle, the 30-layer steady state, config 2 free-running, the mode beside MX self-attention) is
+tests/test_quant_model_gpu.py's "mxfp4_a4" row."""
 import pytest
 import torch
 
 import mx4_ref
-import mx4a4_ref
 import mx6_ref
-from conftest import load_golden
 from longlive_amd import synth
-from test_mx4_gpu import _codes_and_scales, _within_1ulp
-from test_mx_gpu import _epi_ref, _hard_x
-from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
-from util import assert_bf16_close, bf, cosine, rel_l2
+from quant_exact import codes_and_scales as _codes_and_scales
+from quant_exact import epi_ref as _epi_ref
+from quant_exact import hard_x_mx as _hard_x
+from quant_exact import within_1ulp as _within_1ulp
+from util import assert_bf16_close, bf
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 U8 = torch.uint8
-
-# measured on one MI355X (DESIGN.md 5b.6); the model-level bounds are about twice these (rel-L2, and 1 - cos).  The block bound is
-# 1.7x its measured distance: Mx4a4RefModel itself sits 3.06e-2 from Mx4a6RefModel (3.86e-2 from the bf16 oracle), and the bound must
-# stay below both.
-MEASURED = dict(block=1.50e-2, steady_ref=0.203, steady_cos=0.97952, config2=0.155, config2_cos=0.98793, toy_attn=3.23e-3)
-BLOCK_BOUND = 2.5e-2
 
 
 @pytest.fixture(scope="module")
@@ -171,160 +165,3 @@ def test_random_data_vs_fp64_and_not_mx4w6(ops, N, K):
     want = (acc.float() + bias.float()).to(bf)
     assert_bf16_close(ops.gemm_mx4(xm, wm, bd), want, 1, 0.97, f"mx4 {N}x{K}")
     assert not _within_1ulp(ops.gemm_mx4w6(ops.quantize_mx6(xd), wm, bd), want), "mxfp4_a6 passes the W4A4 bound"
-
-
-# ---- 7. one block -------------------------------------------------------------------------------------------------------------------
-def test_mxfp4_a4_block_vs_mx4a4_oracle():
-    """One real-shape block in steady state (Lk = 18720, roll + insert) against Mx4a4RefModel.  The bound (about twice the measured
-    distance) must exclude the bf16 oracle and Mx4a6RefModel: Mx4a4RefModel's own distance to each is asserted above it.  The weight
-    packs of mxfp4_a4 are those of mxfp4_a6."""
-    from longlive_amd.model import CausalWanModelHIP, _kv_commit
-    from oracle import ref_model as RM
-    cfg = synth.longlive_1_3b(num_layers=1)
-    fs, S = cfg.frame_seqlen, 12 * cfg.frame_seqlen
-    sd = synth.synth_state_dict(cfg, seed=0, device=DEV, layers=[0])
-    m = CausalWanModelHIP(cfg, device=DEV)
-    m.load_state_dict(sd)
-    for mod in m.modules():
-        if hasattr(mod, "max_attention_size"):
-            mod.max_attention_size = S
-    x0 = synth.hash_normal(73, "blk.x", (1, 3 * fs, cfg.dim), device=DEV).to(bf)
-    e0 = (0.3 * synth.hash_normal(73, "blk.e0", (1, 3, 6, cfg.dim), device=DEV)).to(bf)
-    ctx = synth.hash_normal(73, "blk.ctx", (1, cfg.text_len, cfg.dim), device=DEV).to(bf)
-    k, v = _kv_fill(cfg, 0, S)
-    m.set_quant("mxfp4_a6")
-    p6 = {kk: vv.clone() for kk, vv in m._pack()[0].items() if kk[:2] in ("q_", "s_")}
-    m.set_quant("mxfp4_a4")
-    p4 = m._pack()[0]
-    assert len(p6) == 12 and all(torch.equal(p4[kk], vv) for kk, vv in p6.items())
-    xs = x0.clone()
-    kv = dict(k=k.clone(), v=v.clone(), global_end_index=S, local_end_index=S)
-    ca = {"k": torch.zeros(1, 512, 12, 128, dtype=bf, device=DEV), "v": torch.zeros(1, 512, 12, 128, dtype=bf, device=DEV), "is_init": False}
-    plan = m.block_forward(0, xs, e0, ctx, kv, ca, 3, (30, 52), current_start=S)
-    _kv_commit(kv, plan.G_new, plan.E_new)
-    m.set_quant(None)
-    got = xs.cpu()
-    sdc = {kk: vv.cpu() for kk, vv in sd.items()}
-    outs = {}
-    for name, cls in (("a4", mx4a4_ref.Mx4a4RefModel), ("a6", mx4_ref.Mx4a6RefModel), ("bf16", RM.RefModel)):
-        ref = cls(RM.RefConfig.from_cfg(cfg), sdc, frame_seqlen_for_max_attn=fs)
-        ref.max_attention_size = S
-        kvr = dict(k=k.cpu().clone(), v=v.cpu().clone(), global_end_index=S, local_end_index=S)
-        car = dict(k=torch.zeros(1, 512, 12, 128, dtype=bf), v=torch.zeros(1, 512, 12, 128, dtype=bf), is_init=False)
-        y, planr = ref.block(x0.cpu(), 0, e0.cpu(), (3, 30, 52), ctx.cpu(), kvr, car, S, False)
-        outs[name] = (y, kvr, planr)
-    r = rel_l2(got, outs["a4"][0])
-    o_bf, o_a6 = rel_l2(outs["a4"][0], outs["bf16"][0]), rel_l2(outs["a4"][0], outs["a6"][0])
-    print(f"mxfp4_a4 block: vs Mx4a4RefModel relL2 {r:.2e} (cos {cosine(got, outs['a4'][0]):.6f}); vs bf16 oracle "
-          f"{rel_l2(got, outs['bf16'][0]):.2e}, vs Mx4a6RefModel {rel_l2(got, outs['a6'][0]):.2e}; Mx4a4RefModel vs bf16 oracle {o_bf:.2e}, "
-          f"vs Mx4a6RefModel {o_a6:.2e}; bound {BLOCK_BOUND:.2e}")
-    assert o_bf > BLOCK_BOUND and o_a6 > BLOCK_BOUND, (o_bf, o_a6, BLOCK_BOUND)
-    assert r < BLOCK_BOUND, r
-    kvr, planr = outs["a4"][1], outs["a4"][2]
-    assert (kv["global_end_index"], kv["local_end_index"]) == (planr["G_new"], planr["E_new"])
-    sl = torch.linspace(0, S - 1, 64).round().long()
-    gk, gv = kv["k"].cpu(), kv["v"].cpu()
-    rk, rv = rel_l2(gk[0, sl], kvr["k"][0, sl]), rel_l2(gv[0, sl], kvr["v"][0, sl])
-    print(f"mxfp4_a4 block: cache slots vs Mx4a4RefModel k {rk:.2e} v {rv:.2e}")
-    assert rk < 5e-3 and rv < 5e-3, (rk, rv)
-
-
-# ---- 8. model level -----------------------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not _have("real_fwd.pt"), reason="golden missing")
-def test_mxfp4_a4_steady_state_vs_reference(real30):
-    rec = load_golden("real_fwd.pt")
-    cfg, gen = real30
-    S = 12 * cfg.frame_seqlen
-    prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=1, device=DEV)}
-    noise = synth.synth_noise(cfg, 3, seed=0, device=DEV)
-    outs = {}
-    try:
-        for mode in ("mxfp4_a6", "mxfp4_a4"):
-            gen.model.set_quant(mode)
-            kv, ca = _new_caches(30, S)
-            for i in range(30):
-                kv[i]["k"], kv[i]["v"] = _kv_fill(cfg, i, S)
-                kv[i]["global_end_index"] = S; kv[i]["local_end_index"] = S
-            flow, _ = gen(noise, prompt, torch.full((1, 3), 625.0, device=DEV), kv_cache=kv, crossattn_cache=ca, current_start=S)
-            outs[mode] = flow.cpu()
-            assert (kv[0]["global_end_index"], kv[0]["local_end_index"]) == tuple(rec["idx_steady"])
-    finally:
-        gen.model.set_quant(None)
-    r, c = rel_l2(outs["mxfp4_a4"], rec["flow_steady"]), cosine(outs["mxfp4_a4"], rec["flow_steady"])
-    r6 = rel_l2(outs["mxfp4_a4"], outs["mxfp4_a6"])
-    print(f"mxfp4_a4 steady: vs reference bf16 {r:.2e} (cos {c:.6f}); vs the mxfp4_a6 run {r6:.2e}")
-    assert r < 2 * MEASURED["steady_ref"] and 1 - c < 2 * (1 - MEASURED["steady_cos"]), (r, c)
-    assert r6 > 1e-2, r6
-
-
-@pytest.mark.skipif(not _have("config2_pipe.pt"), reason="golden missing")
-def test_config2_mxfp4_a4_free_running_vs_reference_bf16(real30):
-    """Config 2's 21 frames free-running: per block within about twice the measured distance to the reference's bf16 latents, flat
-    along the stream (last block <= 1.25x the first), and different from the same run in mxfp4_a6 in every block."""
-    cfg, gen = real30
-    lats = {}
-    try:
-        for mode in ("mxfp4_a6", "mxfp4_a4"):
-            gen.model.set_quant(mode)
-            rec, P, lat, spy = _config2_run(real30, teacher=False, check=False)
-            lats[mode] = lat.cpu()
-    finally:
-        gen.model.set_quant(None)
-    rs = []
-    for blk in range(7):
-        sl = slice(3 * blk, 3 * blk + 3)
-        a, b = lats["mxfp4_a4"][:, sl], rec["latents"][:, sl]
-        r, c, r6 = rel_l2(a, b), cosine(a, b), rel_l2(a, lats["mxfp4_a6"][:, sl])
-        rs.append(r)
-        print(f"config 2 mxfp4_a4 free-running: block {blk} vs reference bf16 relL2 {r:.2e} cos {c:.6f}; vs mxfp4_a6 run {r6:.2e}")
-        assert r < 2 * MEASURED["config2"] and 1 - c < 2 * (1 - MEASURED["config2_cos"]), (blk, r, c)
-        assert r6 > 1e-2, (blk, r6)
-    assert rs[-1] <= 1.25 * rs[0], rs
-
-
-def test_mxfp4_a4_with_mx_attention_toy_vs_oracle():
-    """set_quant("mxfp4_a4") + set_attn_quant("mxfp8") on the toy model over fill, roll and the next frames, against a host model with
-    Mx4a4RefModel's linears and tests/mx_attn_ref.py's attention; it must sit closer to that oracle than to the one with W4A6 linears."""
-    import mx_attn_ref as MA
-    from oracle import ref_model as RM
-    from test_mx_attn_gpu import _toy, _toy_caches
-
-    class MxLinMXAttnRef(MA.MXAttnRefModel):
-        def __init__(self, *a, matmul, **kw):
-            super().__init__(*a, mx_linears=False, **kw)
-            self.matmul, self._w = matmul, {}
-
-        def lin(self, x, name):
-            if name.startswith("blocks.") and name.endswith(self._W8A8):
-                if name not in self._w:
-                    self._w[name] = mx4_ref.dequantize(*mx4_ref.quantize(self.sd[name + ".weight"]))
-                acc = self.matmul(x.to(self.dtype), self._w[name]).float()
-                return (acc + self.sd[name + ".bias"].float()).to(self.dtype).reshape(*x.shape[:-1], -1)
-            return RM.RefModel.lin(self, x, name)
-
-    cfg, sd, gen, S = _toy("mxfp8", "mxfp4_a4")
-    fs = cfg.frame_seqlen
-    kv, ca = _toy_caches(cfg, S, DEV)
-    noise = synth.synth_noise(cfg, 5, seed=5)
-    prompt = synth.synth_prompt_embeds(cfg, seed=7, valid_tokens=9)
-    oracles = {}
-    for name, mm in (("w4a4", mx4a4_ref.mx4_matmul), ("w4a6", mx6_ref.mx6_matmul)):
-        om = MxLinMXAttnRef(RM.RefConfig.from_cfg(cfg), sd, frame_seqlen_for_max_attn=fs, matmul=mm)
-        oracles[name] = (RM.RefGenerator(om, 5.0), RM.new_kv_cache(1, S, cfg.num_layers, cfg.num_heads, 128),
-                         RM.new_crossattn_cache(1, cfg.text_len, cfg.num_layers, cfg.num_heads, 128))
-    worst = {"w4a4": 0.0, "w4a6": 0.0}
-    try:
-        for f in range(5):                       # fill, then rolls
-            x = noise[:, f:f + 1]
-            t = torch.full((1, 1), 937.5)
-            _, x0 = gen(x.to(DEV), {"prompt_embeds": prompt.to(DEV)}, t.to(DEV), kv_cache=kv, crossattn_cache=ca, current_start=f * fs)
-            for name, (og, okv, oca) in oracles.items():
-                _, r0 = og(x, prompt, t, okv, oca, f * fs)
-                worst[name] = max(worst[name], rel_l2(x0.cpu(), r0))
-    finally:
-        gen.model.set_quant(None).set_attn_quant(None)
-    bound = 2 * MEASURED["toy_attn"]
-    print(f"mxfp4_a4 + MX attention, toy: worst x0 rel-L2 vs the W4A4 + MX-attention oracle {worst['w4a4']:.2e}, vs the W4A6-linear "
-          f"one {worst['w4a6']:.2e}; bound {bound:.2e}")
-    assert worst["w4a4"] < bound, worst
-    assert worst["w4a4"] < worst["w4a6"], worst

@@ -1,13 +1,11 @@
 """W4A4 mode (MXFP4 E2M1 weights and activations), host side: the new entry points in the header and the bindings under the unchanged
 ABI version, argument validation of every new entry point before anything is launched (the library loads without a GPU), the plan
-strings, the switches that reach the mode, and the restatement's activation path (tests/mx4a4_ref.py)."""
+strings and the switches that reach the mode.  (The restatement's activation path is pinned in tests/test_quant_ref_host.py.)"""
 import os
 
 import pytest
 import torch
 
-import mx4_ref
-import mx4a4_ref
 from longlive_amd import _lib
 
 bf = torch.bfloat16
@@ -135,19 +133,3 @@ def test_weight_packs_use_the_mxfp4_quantiser():
         MD.ops.quantize_mx4, MD.ops.quantize_mx6 = orig4, orig6
     assert len(calls) == 6 * len(m.blocks)
     assert P[0]["q_f2"].shape[-1] == blk.ffn[2].weight.shape[1] // 2
-
-
-# ---- restatement -------------------------------------------------------------------------------------------------------------------
-def test_mx4_matmul_quantises_the_activations_as_mxfp4():
-    """The activations of Mx4a4RefModel's linears go through the E2M1 scheme: the product equals the one of the dequantised MXFP4
-    activations, and differs from the MXFP6 activations' (tests/mx6_ref.py) on Gaussian data."""
-    import mx6_ref
-    g = torch.Generator().manual_seed(3)
-    x = torch.randn(16, 512, generator=g).to(bf)
-    w = mx4_ref.dequantize(*mx4_ref.quantize(torch.randn(8, 512, generator=g).to(bf)))
-    got = mx4a4_ref.mx4_matmul(x, w)
-    xd = mx4_ref.dequantize(*mx4_ref.quantize(x))
-    assert torch.equal(got, xd @ w.t())
-    assert set(torch.unique(xd.abs() / torch.pow(2.0, mx4_ref.quantize(x)[1].double() - 127).repeat_interleave(32, 1)).tolist()) <= \
-        {0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0}
-    assert not torch.allclose(got, mx6_ref.mx6_matmul(x, w))

@@ -11,7 +11,10 @@ import torch
 
 import mx_attn_exact as X
 import mx_attn_ref as MA
-from test_bf16_edges_gpu import _lib, _nan_bf16, _run, _untouched_bf16
+from bf16_exact import lib as _lib
+from bf16_exact import nan_bf16 as _nan_bf16
+from bf16_exact import run as _run
+from bf16_exact import untouched_bf16 as _untouched_bf16
 from util import bf, rel_l2
 
 pytestmark = pytest.mark.gpu

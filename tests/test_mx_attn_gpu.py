@@ -11,8 +11,15 @@ import torch
 import mx_attn_ref as MA
 from conftest import load_golden
 from longlive_amd import synth
+from model_runs import config2_run as _config2_run
+from model_runs import have as _have
+from model_runs import kv_fill as _kv_fill
+from model_runs import new_caches as _new_caches
+from model_runs import real30  # noqa: F401  (module fixture)
+from model_runs import toy as _toy
+from model_runs import toy_caches as _toy_caches
 from quant_exact import unit_c_scale as _unit_c_scale
-from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
+from quant_ref import make_ref
 from util import bf, cosine, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -152,7 +159,6 @@ def test_no_nan_when_a_tile_is_mostly_masked(ops):
 def test_block_vs_mx_attention_oracle(lin):
     """One real-shape block in steady state (Lk = 18720, roll + insert) with MX attention (and bf16 or MX linears) against
     MXAttnRefModel; it must sit closer to it than to the oracle without MX attention."""
-    import mx_ref
     from longlive_amd.model import CausalWanModelHIP, _kv_commit
     from oracle import ref_model as RM
     cfg = synth.longlive_1_3b(num_layers=1)
@@ -177,8 +183,8 @@ def test_block_vs_mx_attention_oracle(lin):
     _check_shadow(kv["_ll_mx"], kv["k"], kv["v"])
     sdc = {kk: vv.cpu() for kk, vv in sd.items()}
     outs = {}
-    refs = (("mxattn", lambda *a, **kw: MA.MXAttnRefModel(*a, mx_linears=lin == "mxfp8", **kw)),
-            ("plain", mx_ref.MXRefModel if lin == "mxfp8" else RM.RefModel))
+    refs = (("mxattn", lambda *a, **kw: MA.MXAttnRefModel(*a, linears=lin, **kw)),
+            ("plain", lambda *a, **kw: make_ref(lin, *a, **kw)))
     for name, cls in refs:
         ref = cls(RM.RefConfig.from_cfg(cfg), sdc, frame_seqlen_for_max_attn=fs)
         ref.max_attention_size = S
@@ -263,27 +269,6 @@ def test_config2_free_running_vs_reference_bf16(real30, lin):
     assert rs[-1] < 1.25 * rs[0], rs
 
 
-def _toy(attn_quant, lin=None):
-    from longlive_amd.wan_wrapper import WanDiffusionWrapper
-    cfg = synth.toy_config(local_attn_size=3, sink_size=1)
-    sd = synth.synth_state_dict(cfg, seed=3)
-    gen = WanDiffusionWrapper(timestep_shift=5.0, local_attn_size=3, sink_size=1, cfg=cfg, device=DEV, state_dict=sd)
-    S = 3 * cfg.frame_seqlen
-    for m in gen.model.modules():
-        if hasattr(m, "max_attention_size"):
-            m.max_attention_size = S
-    gen.model.set_quant(lin).set_attn_quant(attn_quant)
-    return cfg, sd, gen, S
-
-
-def _toy_caches(cfg, S, dev):
-    kv = [dict(k=torch.zeros(1, S, cfg.num_heads, 128, dtype=bf, device=dev), v=torch.zeros(1, S, cfg.num_heads, 128, dtype=bf, device=dev),
-               global_end_index=0, local_end_index=0) for _ in range(cfg.num_layers)]
-    ca = [dict(k=torch.zeros(1, cfg.text_len, cfg.num_heads, 128, dtype=bf, device=dev),
-               v=torch.zeros(1, cfg.text_len, cfg.num_heads, 128, dtype=bf, device=dev), is_init=False) for _ in range(cfg.num_layers)]
-    return kv, ca
-
-
 def _interactive_run(lin, attn):
     """Fill + roll, then the interactive pipelines' global_sink=False switch: k / v zeroed in place outside the model, one recache
     forward (sink_recache_after_switch) and the next frame, against MXAttnRefModel (with the same linears) doing the same.  Returns
@@ -292,7 +277,7 @@ def _interactive_run(lin, attn):
     cfg, sd, gen, S = _toy(attn, lin)
     fs = cfg.frame_seqlen
     kv, ca = _toy_caches(cfg, S, DEV)
-    om = MA.MXAttnRefModel(RM.RefConfig.from_cfg(cfg), sd, frame_seqlen_for_max_attn=fs, mx_linears=lin == "mxfp8")
+    om = MA.MXAttnRefModel(RM.RefConfig.from_cfg(cfg), sd, frame_seqlen_for_max_attn=fs, linears=lin)
     og = RM.RefGenerator(om, 5.0)
     okv = RM.new_kv_cache(1, S, cfg.num_layers, cfg.num_heads, 128)
     oca = RM.new_crossattn_cache(1, cfg.text_len, cfg.num_layers, cfg.num_heads, 128)

@@ -1,16 +1,15 @@
 """MXFP8 block linears on the MI355X (v_mfma_scale_f32_16x16x128_f8f6f4), pinned to the scheme's definition (tests/mx_ref.py):
 quantiser bytes, the operand / scale lane map with exact data, every GEMM epilogue against the fp64 product of the dequantised
-operands, the fused producers and the FFN1 MX epilogue bit for bit, outlier robustness against int8, one real-shape block against
-the MX oracle, a 30-layer steady-state forward and config 2 free-running against the reference's bf16 goldens."""
+operands, the fused producers and the FFN1 MX epilogue bit for bit, outlier robustness against int8.  The mode at model level (one
+real-shape block against its oracle, the 30-layer steady state, config 2 free-running) is tests/test_quant_model_gpu.py's "mxfp8" row."""
 import pytest
 import torch
 
 import mx_ref
-from conftest import load_golden
 from longlive_amd import synth
+from quant_exact import epi_ref as _epi_ref
 from quant_exact import hard_x_mx as _hard_x
-from test_shipped_sizes_gpu import _config2_run, _have, _kv_fill, _new_caches, real30  # noqa: F401  (real30: module fixture)
-from util import assert_bf16_close, bf, cosine, rel_l2
+from util import assert_bf16_close, bf, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -59,21 +58,6 @@ def test_gemm_lane_map_with_exact_data(ops):
     want = (mx_ref.dequantize(xq, sx) @ mx_ref.dequantize(wq, sw).t()).to(bf)
     got = ops.gemm_mx((xq.to(DEV), sx.to(DEV)), (wq.to(DEV), sw.to(DEV)), torch.zeros(N, dtype=bf, device=DEV)).cpu()
     assert torch.equal(got, want), (got.float() - want.float()).abs().max()
-
-
-def _epi_ref(acc, bias, epi, res=None, e=None, mod=None, gate_idx=0, fs=1):
-    """The bf16 epilogues' rounding points on the fp64 accumulator (ll_gemm_bf16, include/longlive_hip.h LL_EPI_*)."""
-    v = (acc.float() + bias.float()).to(bf)
-    if epi == 0:
-        return v
-    if epi == 1:
-        return torch.nn.functional.gelu(v, approximate="tanh")
-    if epi == 3:
-        return (res.float() + v.float()).to(bf)
-    B, F = e.shape[:2]
-    gate = e[:, :, gate_idx] if mod is None else (mod[gate_idx].float() + e[:, :, gate_idx].float()).to(bf)
-    gv = (v.view(B, F, fs, -1).float() * gate.float().unsqueeze(2)).to(bf).reshape(v.shape)
-    return (res.float() + gv.float()).to(bf)
 
 
 @pytest.mark.parametrize("N,K", [(4608, 1536), (1536, 1536), (8960, 1536), (1536, 8960)])
@@ -167,96 +151,3 @@ def test_outlier_channels_mx_vs_int8(ops, N):
     r_mx, r_i8 = rel_l2(y_mx, exact), rel_l2(y_i8, exact)
     print(f"outliers, N={N}: rel-L2 to the exact product: mxfp8 {r_mx:.3e}, int8 {r_i8:.3e} (ratio {r_mx / r_i8:.3f})")
     assert r_mx <= 0.5 * r_i8, (r_mx, r_i8)
-
-
-def test_mxfp8_block_vs_mx_oracle():
-    """One real-shape block in steady state (Lk = 18720, roll + insert) with MXFP8 linears against MXRefModel, and against the bf16
-    oracle: it must sit closer to the MX restatement than to bf16 (so the pass band excludes "did not quantise")."""
-    from longlive_amd.model import CausalWanModelHIP, _kv_commit
-    from oracle import ref_model as RM
-    cfg = synth.longlive_1_3b(num_layers=1)
-    fs, S = cfg.frame_seqlen, 12 * cfg.frame_seqlen
-    sd = synth.synth_state_dict(cfg, seed=0, device=DEV, layers=[0])
-    m = CausalWanModelHIP(cfg, device=DEV)
-    m.load_state_dict(sd)
-    for mod in m.modules():
-        if hasattr(mod, "max_attention_size"):
-            mod.max_attention_size = S
-    x0 = synth.hash_normal(71, "blk.x", (1, 3 * fs, cfg.dim), device=DEV).to(bf)
-    e0 = (0.3 * synth.hash_normal(71, "blk.e0", (1, 3, 6, cfg.dim), device=DEV)).to(bf)
-    ctx = synth.hash_normal(71, "blk.ctx", (1, cfg.text_len, cfg.dim), device=DEV).to(bf)
-    k, v = _kv_fill(cfg, 0, S)
-    m.set_quant("mxfp8")
-    xs = x0.clone()
-    kv = dict(k=k.clone(), v=v.clone(), global_end_index=S, local_end_index=S)
-    ca = {"k": torch.zeros(1, 512, 12, 128, dtype=bf, device=DEV), "v": torch.zeros(1, 512, 12, 128, dtype=bf, device=DEV), "is_init": False}
-    plan = m.block_forward(0, xs, e0, ctx, kv, ca, 3, (30, 52), current_start=S)
-    _kv_commit(kv, plan.G_new, plan.E_new)
-    m.set_quant(None)
-    got, gk, gv = xs.cpu(), kv["k"].cpu(), kv["v"].cpu()
-    sdc = {kk: vv.cpu() for kk, vv in sd.items()}
-    outs = {}
-    for name, cls in (("mx", mx_ref.MXRefModel), ("bf16", RM.RefModel)):
-        ref = cls(RM.RefConfig.from_cfg(cfg), sdc, frame_seqlen_for_max_attn=fs)
-        ref.max_attention_size = S
-        kvr = dict(k=k.cpu().clone(), v=v.cpu().clone(), global_end_index=S, local_end_index=S)
-        car = dict(k=torch.zeros(1, 512, 12, 128, dtype=bf), v=torch.zeros(1, 512, 12, 128, dtype=bf), is_init=False)
-        y, planr = ref.block(x0.cpu(), 0, e0.cpu(), (3, 30, 52), ctx.cpu(), kvr, car, S, False)
-        outs[name] = (y, kvr, planr)
-    r_mx, r_bf = rel_l2(got, outs["mx"][0]), rel_l2(got, outs["bf16"][0])
-    d_block = rel_l2(x0.cpu(), outs["bf16"][0])
-    print(f"mxfp8 block: vs MX oracle relL2 {r_mx:.2e} (cos {cosine(got, outs['mx'][0]):.6f}); vs bf16 oracle {r_bf:.2e}; "
-          f"MX oracle vs bf16 oracle {rel_l2(outs['mx'][0], outs['bf16'][0]):.2e}; block update size {d_block:.2e}")
-    assert r_mx < r_bf, (r_mx, r_bf)
-    assert r_mx < 6e-3 and cosine(got, outs["mx"][0]) > 0.9999, r_mx
-    kvr, planr = outs["mx"][1], outs["mx"][2]
-    assert (kv["global_end_index"], kv["local_end_index"]) == (planr["G_new"], planr["E_new"])
-    sl = torch.linspace(0, S - 1, 64).round().long()
-    assert rel_l2(gk[0, sl], kvr["k"][0, sl]) < 5e-3 and rel_l2(gv[0, sl], kvr["v"][0, sl]) < 5e-3
-
-
-@pytest.mark.skipif(not _have("real_fwd.pt"), reason="golden missing")
-def test_mxfp8_steady_state_vs_reference(real30):
-    """30 layers, steady state (roll + insert, Lk = 18720) with MXFP8 linears, against the reference's bf16 golden and our bf16 path,
-    within the int8 test's bounds."""
-    rec = load_golden("real_fwd.pt")
-    cfg, gen = real30
-    S = 12 * cfg.frame_seqlen
-    prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=1, device=DEV)}
-    noise = synth.synth_noise(cfg, 3, seed=0, device=DEV)
-    outs = {}
-    for mode in (None, "mxfp8"):
-        gen.model.set_quant(mode)
-        kv, ca = _new_caches(30, S)
-        for i in range(30):
-            kv[i]["k"], kv[i]["v"] = _kv_fill(cfg, i, S)
-            kv[i]["global_end_index"] = S; kv[i]["local_end_index"] = S
-        flow, _ = gen(noise, prompt, torch.full((1, 3), 625.0, device=DEV), kv_cache=kv, crossattn_cache=ca, current_start=S)
-        outs[mode] = flow.cpu()
-        assert (kv[0]["global_end_index"], kv[0]["local_end_index"]) == tuple(rec["idx_steady"])
-    gen.model.set_quant(None)
-    r_ref, r_bf = rel_l2(outs["mxfp8"], rec["flow_steady"]), rel_l2(outs["mxfp8"], outs[None])
-    c_ref, c_bf = cosine(outs["mxfp8"], rec["flow_steady"]), cosine(outs["mxfp8"], outs[None])
-    print(f"mxfp8 steady: vs reference bf16 {r_ref:.2e} (cos {c_ref:.6f}); vs HIP bf16 {r_bf:.2e} (cos {c_bf:.6f})")
-    assert r_bf < 6e-2 and c_bf > 0.998
-    assert r_ref < 7e-2 and c_ref > 0.997
-
-
-@pytest.mark.skipif(not _have("config2_pipe.pt"), reason="golden missing")
-def test_config2_mxfp8_free_running_vs_reference_bf16(real30):
-    """Config 2's 21 frames with MXFP8 linears, free-running, against the reference's bf16 latents: per block rel-L2 <= 7e-2 and
-    cosine >= 0.997, and no growth along the stream (the last block within 1.25x of the first)."""
-    cfg, gen = real30
-    gen.model.set_quant("mxfp8")
-    try:
-        rec, P, lat, spy = _config2_run(real30, teacher=False, check=False)
-    finally:
-        gen.model.set_quant(None)
-    rs = []
-    for blk in range(7):
-        a, b = lat[:, 3 * blk: 3 * blk + 3].cpu(), rec["latents"][:, 3 * blk: 3 * blk + 3]
-        r, c = rel_l2(a, b), cosine(a, b)
-        rs.append(r)
-        print(f"config 2 mxfp8 free-running: block {blk} latents vs reference bf16: relL2 {r:.2e} cos {c:.6f}")
-        assert r < 7e-2 and c > 0.997, (blk, r, c)
-    assert rs[-1] < 1.25 * rs[0], rs

@@ -6,28 +6,30 @@
   * config 1 ("G5"): the reference's CausalInferencePipeline at the real 1.3B shape, 4 latent frames, one step;
   * config 4's prompt-switch forward (reference `_recache_after_switch`) at the real shape, both global_sink settings;
   * one real-shape block against the reference's CausalWanAttentionBlock (tests/golden/real_block.pt);
-  * INT8 (config 5) at steady state; full-length property runs of config 3 (240 latent frames) and config 5 (INT8).
+  * full-length property runs of config 3 (240 latent frames) and config 5 (INT8).  (INT8 against its oracle, at steady state and
+    through config 2 is tests/test_quant_model_gpu.py's "int8" row.)
 
 Tolerances: attention max-abs <= 1.2e-2 vs fp64 (bf16 P and O, fp32 accumulation); end to end rel-L2 <= 3e-2 and cosine
 >= 0.9995 per forward against the reference's bf16 CPU run; integer state exact."""
 import math
 import os
-from types import SimpleNamespace
 
 import pytest
 import torch
 
-from conftest import GOLDEN, load_golden
+from conftest import load_golden
 from longlive_amd import synth
+from model_runs import config2_run as _config2_run
+from model_runs import have as _have
+from model_runs import kv_fill as _kv_fill
+from model_runs import new_caches as _new_caches
+from model_runs import pipe_args as _pipe_args
+from model_runs import real30  # noqa: F401  (module fixture)
 import trace_driver as TD
 from util import bf, cosine, rel_l2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _have(name):
-    return os.path.exists(os.path.join(GOLDEN, name))
 
 
 def _tuning(key, value):
@@ -98,45 +100,6 @@ def test_flash_attn_production_grids(Lq):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _pipe_args(steps=(1000, 750, 500, 250), nfb=3, global_sink=True):
-    return SimpleNamespace(model_kwargs=SimpleNamespace(local_attn_size=12, sink_size=3, timestep_shift=5.0),
-                           denoising_step_list=list(steps), warp_denoising_step=True, num_frame_per_block=nfb,
-                           context_noise=0, global_sink=global_sink)
-
-
-@pytest.fixture(scope="module")
-def real30():
-    """One random-init LongLive-1.3B (30 layers) generator shared by the tests of this file."""
-    from longlive_amd.wan_wrapper import WanDiffusionWrapper
-    cfg = synth.longlive_1_3b()
-    gen = WanDiffusionWrapper(timestep_shift=5.0, local_attn_size=12, sink_size=3, cfg=cfg, device=DEV,
-                              state_dict=synth.synth_state_dict(cfg, seed=0, device=DEV))
-    for mod in gen.model.modules():
-        if hasattr(mod, "max_attention_size"):
-            mod.max_attention_size = 12 * cfg.frame_seqlen
-    yield cfg, gen
-    gen.model.set_quant(None)
-
-
-def _new_caches(n_layers, S, ref_style=False):
-    if ref_style:      # exactly what the reference allocates (pipeline/causal_inference.py:255-293)
-        kv = [{"k": torch.zeros([1, S, 12, 128], dtype=bf, device=DEV), "v": torch.zeros([1, S, 12, 128], dtype=bf, device=DEV),
-               "global_end_index": torch.tensor([0], dtype=torch.long, device=DEV),
-               "local_end_index": torch.tensor([0], dtype=torch.long, device=DEV)} for _ in range(n_layers)]
-    else:
-        kv = [dict(k=torch.zeros(1, S, 12, 128, dtype=bf, device=DEV), v=torch.zeros(1, S, 12, 128, dtype=bf, device=DEV),
-                   global_end_index=0, local_end_index=0) for _ in range(n_layers)]
-    ca = [{"k": torch.zeros([1, 512, 12, 128], dtype=bf, device=DEV), "v": torch.zeros([1, 512, 12, 128], dtype=bf, device=DEV),
-           "is_init": False} for _ in range(n_layers)]
-    return kv, ca
-
-
-def _kv_fill(cfg, layer, S, seed=61):
-    k = synth.hash_normal(seed, f"kv.{layer}.k", (1, S, cfg.num_heads, cfg.head_dim), device=DEV).to(bf)
-    v = (0.5 * synth.hash_normal(seed, f"kv.{layer}.v", (1, S, cfg.num_heads, cfg.head_dim), device=DEV)).to(bf)
-    return k, v
-
-
 @pytest.mark.skipif(not _have("config1_pipe.pt"), reason="golden missing")
 def test_config1_pipeline_vs_reference(real30):
     """BASELINE config 1: 4-frame clip, one denoising step, through OUR CausalInferencePipeline with the HIP generator,
@@ -265,84 +228,6 @@ def _real_shape_block(kernels):
     assert abs(float(xs.float().mean()) - rec["y_mean"]) < 2e-3 and abs(float(xs.float().std()) / rec["y_std"] - 1) < 2e-3
 
 
-def test_int8_block_vs_int8_oracle():
-    """BASELINE config 5's arithmetic pinned to its DEFINITION, not just to "close to bf16": one real-shape block in steady state
-    (Lk = 18720, roll + insert) with W8A8 linears on the MI355X against the CPU oracle's restatement of the same scheme
-    (oracle/ref_model.py quant="int8": per-token / per-channel symmetric scales, q = rint(x / scale), exact integer sums,
-    y = bf16(float(acc) * (sx * sw) + bias)).  Bound: the bf16 block test's rel-L2 < 6e-3 (measured 3.0e-3; the same block int8 vs
-    bf16: 3.9e-3).  It cannot be much tighter: a 1-ulp bf16 difference in a row's LARGEST activation (GPU vs CPU accumulation order)
-    changes that token's scale, and with it the int8 codes of a few per cent of the row -- two valid quantisations whose rounding
-    noise is partly independent.  What IS exact is checked at op level (tests/test_ops_gpu.py: codes and scales equal the oracle's
-    bit for bit on identical inputs, the GEMM equals the exact integer product)."""
-    from longlive_amd.model import CausalWanModelHIP, _kv_commit
-    from oracle import ref_model as RM
-    cfg = synth.longlive_1_3b(num_layers=1)
-    fs, S = cfg.frame_seqlen, 12 * cfg.frame_seqlen
-    sd = synth.synth_state_dict(cfg, seed=0, device=DEV, layers=[0])
-    m = CausalWanModelHIP(cfg, device=DEV)
-    m.load_state_dict(sd)
-    for mod in m.modules():
-        if hasattr(mod, "max_attention_size"):
-            mod.max_attention_size = S
-    x0 = synth.hash_normal(71, "blk.x", (1, 3 * fs, cfg.dim), device=DEV).to(bf)
-    e0 = (0.3 * synth.hash_normal(71, "blk.e0", (1, 3, 6, cfg.dim), device=DEV)).to(bf)
-    ctx = synth.hash_normal(71, "blk.ctx", (1, cfg.text_len, cfg.dim), device=DEV).to(bf)
-    k, v = _kv_fill(cfg, 0, S)
-    outs = {}
-    for mode in ("int8", None):
-        m.set_quant(mode)
-        xs = x0.clone()
-        kv = dict(k=k.clone(), v=v.clone(), global_end_index=S, local_end_index=S)
-        ca = {"k": torch.zeros(1, 512, 12, 128, dtype=bf, device=DEV), "v": torch.zeros(1, 512, 12, 128, dtype=bf, device=DEV), "is_init": False}
-        plan = m.block_forward(0, xs, e0, ctx, kv, ca, 3, (30, 52), current_start=S)
-        _kv_commit(kv, plan.G_new, plan.E_new)
-        outs[mode] = (xs.cpu(), kv["k"].cpu(), kv["v"].cpu(), (kv["global_end_index"], kv["local_end_index"]))
-    m.set_quant(None)
-    # the oracle, int8 mode, on the host
-    ref = RM.RefModel(RM.RefConfig.from_cfg(cfg), {kk: vv.cpu() for kk, vv in sd.items()}, frame_seqlen_for_max_attn=fs, quant="int8")
-    ref.max_attention_size = S
-    kvr = dict(k=k.cpu().clone(), v=v.cpu().clone(), global_end_index=S, local_end_index=S)
-    car = dict(k=torch.zeros(1, 512, 12, 128, dtype=bf), v=torch.zeros(1, 512, 12, 128, dtype=bf), is_init=False)
-    y, planr = ref.block(x0.cpu(), 0, e0.cpu(), (3, 30, 52), ctx.cpu(), kvr, car, S, False)
-    got, gk, gv, idx = outs["int8"]
-    r, c = rel_l2(got, y), cosine(got, y)
-    r_bf = rel_l2(got, outs[None][0])
-    print(f"int8 block vs int8 oracle: relL2 {r:.2e} cos {c:.6f}  (the same block, int8 vs bf16 on the GPU: {r_bf:.2e})")
-    assert r < 6e-3 and c > 0.9999, (r, c)
-    assert idx == (planr["G_new"], planr["E_new"])
-    sl = torch.linspace(0, S - 1, 64).round().long()
-    assert rel_l2(gk[0, sl], kvr["k"][0, sl]) < 5e-3 and rel_l2(gv[0, sl], kvr["v"][0, sl]) < 5e-3
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.skipif(not _have("real_fwd.pt"), reason="golden missing")
-def test_int8_steady_state_vs_reference(real30):
-    """Config 5's arithmetic in the regime it runs in: W8A8 block linears on a steady-state forward (roll + insert,
-    Lk = 18720) against the reference's bf16 CPU golden (`real_fwd.pt:flow_steady`) and against our bf16 path."""
-    rec = load_golden("real_fwd.pt")
-    cfg, gen = real30
-    fs, S = cfg.frame_seqlen, 12 * cfg.frame_seqlen
-    prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=1, device=DEV)}
-    noise = synth.synth_noise(cfg, 3, seed=0, device=DEV)
-    outs = {}
-    for mode in (None, "int8"):
-        gen.model.set_quant(mode)
-        kv, ca = _new_caches(30, S)
-        for i in range(30):
-            kv[i]["k"], kv[i]["v"] = _kv_fill(cfg, i, S)
-            kv[i]["global_end_index"] = S; kv[i]["local_end_index"] = S
-        flow, _ = gen(noise, prompt, torch.full((1, 3), 625.0, device=DEV), kv_cache=kv, crossattn_cache=ca, current_start=S)
-        outs[mode] = flow.cpu()
-        assert (kv[0]["global_end_index"], kv[0]["local_end_index"]) == tuple(rec["idx_steady"])
-    gen.model.set_quant(None)
-    r_ref = rel_l2(outs["int8"], rec["flow_steady"])
-    r_bf = rel_l2(outs["int8"], outs[None])
-    print(f"int8 steady: vs reference bf16 {r_ref:.2e} (cos {cosine(outs['int8'], rec['flow_steady']):.6f}); vs HIP bf16 {r_bf:.2e}; "
-          f"HIP bf16 vs reference {rel_l2(outs[None], rec['flow_steady']):.2e}")
-    assert r_bf < 6e-2 and cosine(outs["int8"], outs[None]) > 0.998
-    assert r_ref < 7e-2 and cosine(outs["int8"], rec["flow_steady"]) > 0.997
-
-
 def _long_run(gen, cfg, T, quant):
     from longlive_amd.pipeline import CausalInferencePipeline
     gen.model.set_quant(quant)
@@ -366,85 +251,6 @@ def _check_long(P, lat, cfg, T):
     # the sink (first 3 frames' K) is still in place and untouched by 70+ rolls: slots [0, 3 fs) are non-zero and identical
     # in every later block (checked: they equal what block 0 wrote, because the window never overwrites them)
     assert float(P.kv_cache1[0]["k"][0, : 3 * fs].float().abs().sum()) > 0
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# BASELINE config 2 EXACTLY, against the reference's own pipeline at full depth and size (oracle/make_golden.py::gen_config2):
-# 30 layers, 60x104, T = 21, steps [1000, 750, 500, 250] + re-noise + clean-context pass, window 12 / sink 3 -- 7 blocks, the
-# window fills in blocks 0-3 and ROLLS in blocks 4-6, every cache entry written by the model itself (no synthetic cache content).
-class _Config2Spy:
-    """Sits on generator.forward while OUR CausalInferencePipeline runs.  Call n = 5 * block + j: j < 4 are the denoising
-    forwards, j = 4 the clean-context pass.  Records rel-L2 / cosine of every x0 against the reference's; after the context pass
-    compares the sampled K / V slots and the end indices.  teacher=True: the reference's x0 is handed back to the pipeline instead
-    of ours wherever the golden stores it whole (every block's last step = the latents; all steps of blocks 0 / 4 / 6), so that
-    every forward is entered from the REFERENCE's history (latents, re-noise input, and caches that OUR kernels wrote from the
-    reference's latents) -- errors cannot compound across blocks."""
-
-    def __init__(self, gen, rec, teacher, check=True):
-        self.gen, self.rec, self.teacher, self.orig, self.check = gen, rec, teacher, gen.forward, check
-        self.n, self.rows, self.kv_rows = 0, [], []
-
-    def __enter__(self):
-        self.gen.forward = self
-        return self
-
-    def __exit__(self, *exc):
-        self.gen.forward = self.orig
-
-    def __call__(self, *a, **k):
-        out = self.orig(*a, **k)
-        blk, j = divmod(self.n, 5)
-        self.n += 1
-        b = self.rec["blocks"][blk]
-        want_call = self.rec["calls"][self.n - 1]
-        assert int(k["current_start"]) == want_call["current_start"], (self.n - 1, k["current_start"], want_call)
-        assert abs(float(k["timestep"].flatten()[0]) - want_call["t"]) < 1e-3, (self.n - 1, want_call)
-        if j < 4:
-            x0 = out[1]
-            full = self.rec["latents"][:, 3 * blk: 3 * blk + 3] if j == 3 else (b["x0_steps"][j] if b["x0_steps"] else None)
-            got_s = x0.flatten()[self.rec["sample_idx"].to(x0.device)].cpu()
-            row = dict(block=blk, step=j, rel_sample=rel_l2(got_s, b["x0_samples"][j]), cos_sample=cosine(got_s, b["x0_samples"][j]))
-            if full is not None:
-                row.update(rel=rel_l2(x0.cpu(), full), cos=cosine(x0.cpu(), full))
-                if self.teacher:
-                    out = (out[0], full.to(device=x0.device, dtype=x0.dtype))
-            self.rows.append(row)
-        else:
-            torch.cuda.synchronize()                     # the context pass may run on the pipeline's second stream
-            kv = k["kv_cache"]
-            idx = (int(kv[0]["global_end_index"]), int(kv[0]["local_end_index"]))
-            assert idx == tuple(b["idx"]), (blk, idx, b["idx"])
-            sl = self.rec["slots"].to(DEV)
-            for li, layer in enumerate(self.rec["layers"]):
-                for nm in ("k", "v"):
-                    got, want = kv[layer][nm][0, sl].cpu(), b[nm][li]
-                    za, zb = got.float().abs().sum(dim=(1, 2)) == 0, want.float().abs().sum(dim=(1, 2)) == 0
-                    assert torch.equal(za, zb) or not self.check, f"block {blk} layer {layer} {nm}: different slot occupancy"
-                    self.kv_rows.append(dict(block=blk, layer=layer, what=nm, rel=rel_l2(got, want)))
-        return out
-
-
-def _config2_run(real30, teacher, check=True):
-    from longlive_amd.pipeline import CausalInferencePipeline
-    rec = load_golden("config2_pipe.pt")
-    cfg, gen = real30
-    prompt = {"prompt_embeds": synth.synth_prompt_embeds(cfg, seed=rec["prompt_seed"], device=DEV)}
-    P = CausalInferencePipeline(_pipe_args(), DEV, generator=gen, text_encoder=lambda text_prompts: prompt)
-    P.randn_like = TD.HashRandn(rec["renoise_seed"])
-    assert [float(x) for x in P.denoising_step_list] == rec["steps"]
-    with _Config2Spy(gen, rec, teacher, check) as spy:
-        _, lat = P.inference(synth.synth_noise(cfg, rec["T"], seed=rec["noise_seed"], device=DEV), ["p0"], return_latents=True)
-    assert spy.n == 35
-    tag = "teacher-forced" if teacher else "free-running"
-    for r in spy.rows:
-        print(f"config 2 {tag}: block {r['block']} step {r['step']}: "
-              + (f"relL2 {r['rel']:.2e} cos {r['cos']:.6f}  " if "rel" in r else "")
-              + f"(8192-sample relL2 {r['rel_sample']:.2e} cos {r['cos_sample']:.6f})")
-    for blk in range(7):
-        rows = [r for r in spy.kv_rows if r["block"] == blk]
-        print(f"config 2 {tag}: block {blk} cache slots: "
-              + "  ".join(f"L{r['layer']}.{r['what']} {r['rel']:.1e}" for r in rows))
-    return rec, P, lat, spy
 
 
 @pytest.mark.skipif(not _have("config2_pipe.pt"), reason="golden missing")
@@ -475,28 +281,6 @@ def test_config2_pipeline_vs_reference_free_running(real30):
         print(f"config 2 free-running: block {blk} latents relL2 {r:.2e} cos {c:.6f}")
         assert r < 3e-2 and c > 0.9995, (blk, r, c)
     assert (P.kv_cache1[0]["global_end_index"], P.kv_cache1[29]["local_end_index"]) == (21 * cfg_fs(real30), 12 * cfg_fs(real30))
-
-
-@pytest.mark.skipif(not _have("config2_pipe.pt"), reason="golden missing")
-def test_config2_int8_free_running_vs_reference_bf16(real30):
-    """Config 5's arithmetic THROUGH THE AR LOOP: the 21-frame run of config 2 with W8A8 linears, free-running (its own x0 re-noised,
-    its own caches through the roll), against the reference's bf16 latents.  The reference ships no INT8 code, so this is a distance,
-    not a parity: per block rel-L2 <= 7e-2 / cosine >= 0.997 (the one-forward bound of `test_int8_steady_state_vs_reference`), and it
-    must not GROW along the stream: the last block within 1.25x of the first."""
-    cfg, gen = real30
-    gen.model.set_quant("int8")
-    try:
-        rec, P, lat, spy = _config2_run(real30, teacher=False, check=False)
-    finally:
-        gen.model.set_quant(None)
-    rs = []
-    for blk in range(7):
-        a, b = lat[:, 3 * blk: 3 * blk + 3].cpu(), rec["latents"][:, 3 * blk: 3 * blk + 3]
-        r, c = rel_l2(a, b), cosine(a, b)
-        rs.append(r)
-        print(f"config 2 int8 free-running: block {blk} latents vs reference bf16: relL2 {r:.2e} cos {c:.6f}")
-        assert r < 7e-2 and c > 0.997, (blk, r, c)
-    assert rs[-1] < 1.25 * rs[0], rs
 
 
 def cfg_fs(real30):
