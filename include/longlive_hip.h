@@ -58,7 +58,8 @@ enum ll_epilogue {
  * ll_jpeg_coefficients_u8), and so do the clip-intake entry points (ll_jpeg_decode_sizes, ll_jpeg_decode_coefficients,
  * ll_jpeg_decode_pixels, ll_jpeg_decode_u8, ll_resize_u8), and so do the split entropy route's (ll_jpeg_decode_split_sizes,
  * ll_jpeg_decode_coefficients_split, ll_jpeg_decode_u8_split), and so do the planar YUV entry points (ll_frames_u8_to_yuv420,
- * ll_cl_to_yuv420, ll_yuv_to_frames_u8): 111 covers them too. */
+ * ll_cl_to_yuv420, ll_yuv_to_frames_u8), and so do the lossless frames-out entry points (ll_png_sizes, ll_png_encode_u8,
+ * ll_png_filter_u8, ll_zlib_sizes, ll_zlib_compress_u8): 111 covers them too. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);
@@ -552,6 +553,31 @@ int ll_jpeg_encode_u8(const uint8_t* frames, long long stride_t, int T, int H, i
 /* The first stage alone: colour conversion, 8 x 8 DCT and quantisation -> coef int16 [T, ceil(H/16), ceil(W/16), 6, 64], blocks
  * Y00 Y01 Y10 Y11 Cb Cr of every MCU, each in zigzag order (what the tests pin the arithmetic with). */
 int ll_jpeg_coefficients_u8(const uint8_t* frames, long long stride_t, int T, int H, int W, int quality, int16_t* coef, ll_stream stream);
+
+/* Lossless frames out: PNG (8 bits, colour type 2, no interlace), one complete file per frame: signature, IHDR, one IDAT per deflate
+ * chunk of 16384 filtered bytes (the first begins with the zlib header 78 01), one IDAT with the Adler-32, IEND; every CRC-32 is
+ * computed on the device.  Filter per row: the type of the five (bpp = 3, row 0 against a zero row) with the smallest sum of
+ * min(b, 256 - b), the lower type on a tie.  DEFLATE, deterministic: literals and distance-1 matches (zlib's Z_RLE parse), one
+ * dynamic-Huffman block per chunk (15-bit codes, 7-bit code-length code) followed by an empty stored block unless it is the last,
+ * or a stored block when that is shorter; csrc/png.h's head comment is the definition, tests/png_ref.py its restatement.
+ *
+ * ll_png_sizes (host only): *out_stride = the worst case of one frame = 33 + n + 17 * ceil(n / 16384) + 2 + 28 with
+ * n = H * (1 + 3 W), rounded up to 16; *scratch_bytes = what ll_png_encode_u8 needs for T frames. */
+int ll_png_sizes(int T, int H, int W, long long* out_stride, long long* scratch_bytes);
+/* frames uint8 [T,H,W,3] RGB (stride_t in BYTES >= H*W*3) -> out + t * out_stride holds frame t's file, sizes[t] its length in bytes
+ * (device int32 [T]); bytes of out past sizes[t] are left alone.  No allocation, no synchronisation; scratch (16-byte aligned,
+ * scratch_bytes >= ll_png_sizes') may hold anything.  Refused before any launch: null operands, T, H, W < 1, a frame whose worst
+ * case passes 2 GiB, short stride_t / out_stride / scratch_bytes. */
+int ll_png_encode_u8(const uint8_t* frames, long long stride_t, int T, int H, int W, uint8_t* out, long long out_stride, int32_t* sizes,
+                     void* scratch, long long scratch_bytes, ll_stream stream);
+/* The first stage alone: out uint8 [T, H, 1 + 3 W], each row's filter type and its filtered bytes. */
+int ll_png_filter_u8(const uint8_t* frames, long long stride_t, int T, int H, int W, uint8_t* out, ll_stream stream);
+/* The compressor alone over T byte rows of n bytes (stride in BYTES >= n): out + t * out_stride holds row t's zlib stream (78 01,
+ * the chunks, Adler-32), sizes[t] its length.  ll_zlib_sizes (host only): *out_stride = 2 + n + 5 * ceil(n / 16384) + 4 rounded up
+ * to 16.  Scratch and refusals as for ll_png_encode_u8. */
+int ll_zlib_sizes(int T, long long n, long long* out_stride, long long* scratch_bytes);
+int ll_zlib_compress_u8(const uint8_t* src, long long stride, int T, long long n, uint8_t* out, long long out_stride, int32_t* sizes,
+                        void* scratch, long long scratch_bytes, ll_stream stream);
 
 /* Clip intake: a baseline JPEG decoder (SOF0, 8 bits; 1 component, or 3 as YCbCr with luma sampling hs x vs = 1x1, 2x1 or 2x2 and
  * chroma 1x1; any tables; any restart interval) and an antialiased resize.  The host parses the files (longlive_amd/jpeg_files.py);

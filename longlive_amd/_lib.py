@@ -70,6 +70,11 @@ SIGNATURES = {
     "ll_jpeg_sizes": [_i, _i, _i, C.POINTER(_ll), C.POINTER(_ll)],
     "ll_jpeg_encode_u8": [_p, _ll, _i, _i, _i, _i, _p, _ll, _p, _p, _ll, _p],
     "ll_jpeg_coefficients_u8": [_p, _ll, _i, _i, _i, _i, _p, _p],
+    "ll_png_sizes": [_i, _i, _i, C.POINTER(_ll), C.POINTER(_ll)],
+    "ll_png_encode_u8": [_p, _ll, _i, _i, _i, _p, _ll, _p, _p, _ll, _p],
+    "ll_png_filter_u8": [_p, _ll, _i, _i, _i, _p, _p],
+    "ll_zlib_sizes": [_i, _ll, C.POINTER(_ll), C.POINTER(_ll)],
+    "ll_zlib_compress_u8": [_p, _ll, _i, _ll, _p, _ll, _p, _p, _ll, _p],
     "ll_jpeg_decode_sizes": [_i] * 6 + [C.POINTER(_ll), C.POINTER(_ll)],
     "ll_jpeg_decode_coefficients": [_p, _ll, _p, _i, _p, _p] + [_i] * 6 + [_p, _p, _p],
     "ll_jpeg_decode_pixels": [_p, _p] + [_i] * 6 + [_p, _ll, _p, _ll, _p],

@@ -23,6 +23,9 @@ rate, `input_range: full` names the range of a header without one (DESIGN.md sec
 `input_decode: gpu` decodes such a file's frames on the GPU instead (ops.jpeg_decode: baseline JPEG as this project, libjpeg, Pillow
 or ffmpeg write it), and `input_fit: cover | stretch` resizes a clip of another size to the model's on the GPU (ops.resize_u8);
 without the two keys intake is as before ("Clip intake on the GPU").
+`video_codec: png` writes the exact frames as `<name>.frames/00000.png ...`, `video_codec: apng` as one animated `<name>.png` at
+16 frames/s, both encoded on the GPU (ops.png_encode; DESIGN.md section 5c, "Lossless frames: PNG"); `input_video: clip.png` (a
+still or an APNG, through PIL) continues from exactly those frames.
 """
 from __future__ import annotations
 
@@ -377,12 +380,13 @@ def is_y4m_input(path) -> bool:
         return False
 
 
-VIDEO_CODECS = ("mjpeg", "y4m")
+VIDEO_CODECS = ("mjpeg", "y4m", "png", "apng")
 
 
 def video_codec(value) -> Optional[str]:
     """The yaml's `video_codec:` key: absent / none = write_video's path, `mjpeg` = Motion JPEG in an .avi from the GPU encoder,
-    `y4m` = I420 frames from the decoder's last kernel in a YUV4MPEG2 stream (`ffmpeg -i out.y4m out.mp4` makes an mp4 of it)."""
+    `y4m` = I420 frames from the decoder's last kernel in a YUV4MPEG2 stream (`ffmpeg -i out.y4m out.mp4` makes an mp4 of it),
+    `png` = one lossless PNG file per frame from the GPU encoder, `apng` = the same frames as one animated PNG."""
     if str(value).strip().lower() == "none":                    # the word, or the absent key
         return None
     return _one_of("video_codec", value, VIDEO_CODECS, None, " (or absent)")
@@ -410,7 +414,8 @@ def write_video(path: str, frames: torch.Tensor, fps: int = 16) -> str:
 
 
 # One writer per `video_codec`: (run()'s .mp4 name, one sample's frames in the form the pipeline was asked for) -> (the path written,
-# its frame count, the record's codec keys).  Absent key: uint8 [T', H, W, 3] on the host; mjpeg: the same on the device; y4m: I420.
+# its frame count, the record's codec keys).  Absent key: uint8 [T', H, W, 3] on the host; mjpeg, png, apng: the same on the device;
+# y4m: I420.
 def _write_default(path: str, frames: torch.Tensor):
     return write_video(path, frames, fps=16), int(frames.shape[0]), {}
 
@@ -429,6 +434,92 @@ def _write_y4m(path: str, frames: torch.Tensor, width: int, height: int, out_ran
     path = os.path.splitext(path)[0] + ".y4m"
     size = y4m.write_y4m(path, iter(host), width, height, fps=16, range=out_range)
     return path, int(host.shape[0]), {"codec": "y4m", "bytes": size, "range": out_range}
+
+
+def _png_chunk(kind: bytes, data: bytes) -> bytes:
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
+
+
+def png_chunks(data: bytes) -> List:
+    """[(type, payload)] of a PNG file; the signature and every chunk's length and CRC-32 are checked."""
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("png_chunks: not a PNG file")
+    at, out = 8, []
+    while at < len(data):
+        if at + 12 > len(data):
+            raise ValueError(f"png_chunks: a chunk header at byte {at} passes the end of the file")
+        n, = struct.unpack(">I", data[at:at + 4])
+        kind, payload = data[at + 4:at + 8], data[at + 8:at + 8 + n]
+        if at + 12 + n > len(data) or struct.unpack(">I", data[at + 8 + n:at + 12 + n])[0] != zlib.crc32(kind + payload):
+            raise ValueError(f"png_chunks: the {kind!r} chunk at byte {at} is cut short or fails its CRC-32")
+        out.append((kind, payload))
+        at += 12 + n
+    return out
+
+
+def write_apng(path: str, files: Sequence[bytes], fps: int = 16) -> int:
+    """One animated PNG from complete PNG files of one size and format (what ops.png_encode makes): the first file's IHDR, acTL, then
+    per frame an fcTL and its image data -- the first frame's IDAT chunks as they are, later frames' re-wrapped as fdAT behind a
+    sequence number, which changes their CRC-32s (recomputed here, on the host) -- and IEND.  Returns the file's bytes."""
+    if not files:
+        raise ValueError("write_apng: no frames")
+    if isinstance(fps, bool) or not isinstance(fps, int) or not 1 <= fps <= 65535:
+        raise ValueError(f"write_apng: fps={fps!r} must be an integer 1..65535")
+    parsed = [png_chunks(f) for f in files]
+    ihdr = parsed[0][0]
+    if ihdr[0] != b"IHDR":
+        raise ValueError("write_apng: frame 0 does not begin with IHDR")
+    width, height = struct.unpack(">II", ihdr[1][:8])
+    out = [b"\x89PNG\r\n\x1a\n", _png_chunk(*ihdr), _png_chunk(b"acTL", struct.pack(">II", len(files), 0))]
+    seq = 0
+    for t, chunks in enumerate(parsed):
+        if chunks[0] != ihdr:
+            raise ValueError(f"write_apng: frame {t}'s IHDR differs from frame 0's")
+        out.append(_png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, width, height, 0, 0, 1, fps, 0, 0)))
+        seq += 1
+        for kind, payload in chunks:
+            if kind != b"IDAT":
+                continue
+            if t == 0:
+                out.append(_png_chunk(b"IDAT", payload))
+            else:
+                out.append(_png_chunk(b"fdAT", struct.pack(">I", seq) + payload))
+                seq += 1
+    out.append(_png_chunk(b"IEND", b""))
+    blob = b"".join(out)
+    with open(path, "wb") as f:
+        f.write(blob)
+    return len(blob)
+
+
+def read_png_frames(path: str) -> torch.Tensor:
+    """uint8 [T, H, W, 3] RGB frames of a PNG file through PIL: a still gives one frame, an APNG all of its frames."""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as im:
+        frames = []
+        for t in range(getattr(im, "n_frames", 1)):
+            im.seek(t)
+            frames.append(torch.from_numpy(np.asarray(im.convert("RGB")).copy()))
+    return torch.stack(frames)
+
+
+def _write_png(path: str, frames: torch.Tensor):
+    from . import ops
+    files = ops.png_bytes(*ops.png_encode(frames))
+    folder = os.path.splitext(path)[0] + ".frames"
+    os.makedirs(folder, exist_ok=True)
+    for t, data in enumerate(files):
+        with open(os.path.join(folder, f"{t:05d}.png"), "wb") as f:
+            f.write(data)
+    return folder, len(files), {"codec": "png", "bytes": sum(len(d) for d in files)}
+
+
+def _write_apng(path: str, frames: torch.Tensor):
+    from . import ops
+    files = ops.png_bytes(*ops.png_encode(frames))
+    path = os.path.splitext(path)[0] + ".png"
+    return path, len(files), {"codec": "apng", "bytes": write_apng(path, files, fps=16)}
 
 
 def input_frames(cap) -> Optional[int]:
@@ -450,10 +541,13 @@ def select_clip_frames(total: int, cap: Optional[int] = None) -> slice:
 
 def read_input_video(path: str) -> torch.Tensor:
     """uint8 [T, H, W, 3] RGB frames of `path`: an .avi as write_avi_rgb24 or write_avi_mjpeg writes it (chosen by the `strf` chunk's
-    biCompression), a .pt holding such a tensor, anything else through torchvision.io.read_video when torchvision + PyAV exist."""
+    biCompression), a .png (a still or an APNG, through PIL), a .pt holding such a tensor, anything else through
+    torchvision.io.read_video when torchvision + PyAV exist."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".avi":
         frames = read_avi_mjpeg(path) if avi_compression(path) == b"MJPG" else read_avi_rgb24(path)
+    elif ext == ".png":
+        frames = read_png_frames(path)
     elif ext == ".pt":
         frames = torch.load(path, map_location="cpu", weights_only=True)      # a bare tensor: nothing is unpickled
     else:
@@ -712,7 +806,8 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     input_decode(config.get("input_decode")), input_fit(config.get("input_fit")), input_split(config.get("input_split"))
     clip = input_clip(config, shape.lat_h, shape.lat_w, device)    # read (decoded, resized) and checked before any model is built
     write = {None: _write_default, "mjpeg": functools.partial(_write_mjpeg, quality=quality),
-             "y4m": functools.partial(_write_y4m, width=8 * shape.lat_w, height=8 * shape.lat_h, out_range=out_range)}[codec]
+             "y4m": functools.partial(_write_y4m, width=8 * shape.lat_w, height=8 * shape.lat_h, out_range=out_range),
+             "png": _write_png, "apng": _write_apng}[codec]
     wcfg, gen, vae, enc, lora_enabled = build_models(config, device, synthetic)
     gen.model.set_quant(quant_mode(config.get("quant", "none")))       # block linears: bf16, W8A8, MXFP8, FP8 rowwise, MXFP6, W4A6 or W4A4
     gen.model.set_attn_quant(attn_quant_mode(config.get("attn_quant", "none")))   # self-attention: bf16 or MXFP8

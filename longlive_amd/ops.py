@@ -783,6 +783,69 @@ def jpeg_coefficients(frames, quality: int = 90):
     return coef
 
 
+# ---- lossless frames out: PNG files and the zlib compressor inside them ("Lossless frames: PNG") ----
+def png_sizes(T: int, H: int, W: int):
+    """(out_stride, scratch_bytes) of ll_png_encode_u8 for T frames of H x W (host only)."""
+    import ctypes
+    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.check(_lib.load().ll_png_sizes(T, H, W, ctypes.byref(a), ctypes.byref(b)), "ll_png_sizes")
+    return int(a.value), int(b.value)
+
+
+def png_encode(frames):
+    """uint8 frames [T, H, W, 3] RGB (or a view with contiguous frames) -> (buf uint8 [T, out_stride], sizes int32 [T]): frame t's PNG
+    file (8-bit RGB, lossless) is buf[t, :sizes[t]].  Stream-ordered: nothing is read back."""
+    frames, stride_t = _frames_u8(frames, "frames")
+    T, H, W, _ = frames.shape
+    out_stride, scratch_bytes = png_sizes(T, H, W)
+    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=frames.device)
+    sizes = torch.empty(T, dtype=torch.int32, device=frames.device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.load().ll_png_encode_u8(frames.data_ptr(), stride_t, T, H, W, buf.data_ptr(), out_stride, sizes.data_ptr(),
+                                            scratch.data_ptr(), scratch_bytes, _stream()), "ll_png_encode_u8")
+    return buf, sizes
+
+
+png_bytes = jpeg_bytes      # the files of png_encode on the host: the same one read
+
+
+def png_filter(frames):
+    """The encoder's first stage alone: uint8 [T, H, 1 + 3W], each row's filter type and its filtered bytes."""
+    frames, stride_t = _frames_u8(frames, "frames")
+    T, H, W, _ = frames.shape
+    out = torch.empty(T, H, 1 + 3 * W, dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.load().ll_png_filter_u8(frames.data_ptr(), stride_t, T, H, W, out.data_ptr(), _stream()), "ll_png_filter_u8")
+    return out
+
+
+def zlib_sizes(T: int, n: int):
+    """(out_stride, scratch_bytes) of ll_zlib_compress_u8 for T rows of n bytes (host only)."""
+    import ctypes
+    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _lib.check(_lib.load().ll_zlib_sizes(T, n, ctypes.byref(a), ctypes.byref(b)), "ll_zlib_sizes")
+    return int(a.value), int(b.value)
+
+
+def zlib_compress(rows):
+    """uint8 rows [T, n] (unit stride along n, any row stride) -> (buf uint8 [T, out_stride], sizes int32 [T]): row t's zlib stream
+    (the PNG encoder's deterministic DEFLATE, which zlib.decompress reads) is buf[t, :sizes[t]].  Stream-ordered."""
+    if not rows.is_cuda:
+        raise RuntimeError("rows: expected a device tensor (longlive_amd has no CPU path)")
+    if rows.dtype != torch.uint8:
+        raise RuntimeError(f"rows: expected uint8, got {rows.dtype}")
+    assert rows.dim() == 2, f"rows: {tuple(rows.shape)} is not [T, n]"
+    T, n = rows.shape
+    if rows.stride(1) != 1 or (T > 1 and rows.stride(0) < n):
+        rows = rows.contiguous()
+    out_stride, scratch_bytes = zlib_sizes(T, n)
+    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=rows.device)
+    sizes = torch.empty(T, dtype=torch.int32, device=rows.device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=rows.device)
+    _lib.check(_lib.load().ll_zlib_compress_u8(rows.data_ptr(), rows.stride(0) if T > 1 else n, T, n, buf.data_ptr(), out_stride,
+                                               sizes.data_ptr(), scratch.data_ptr(), scratch_bytes, _stream()), "ll_zlib_compress_u8")
+    return buf, sizes
+
+
 # ---- planar YUV: I420 frames out, planes of six layouts in (DESIGN.md section 5c, "Planar YUV and Y4M") -----------------
 YUV_RANGES = ("limited", "full")
 YUV_LAYOUTS = ("420jpeg", "420mpeg2", "420paldv", "422", "444", "mono")     # the index is ll_yuv_to_frames_u8's `layout`
