@@ -109,9 +109,7 @@ def _rowwise(gemm: str) -> Callable:       # the per-row-scale GEMMs take codes 
 _QUANT_MODES = {
     None: _QuantMode(None, None, _op("ln_modulate"), _op("ln_modulate_tab"), _op("layernorm_affine"), _op("gemm"),
                      lambda x, w, b, cache_v, ws, ro, wl, B, L: ops.gemm_qkv_v_insert(x, w, b, cache_v, ws, ro, wl), False, 1),
-    "int8": _quant_mode("quantize_rows", "quantize_rows", "q8", "w8a8", False, 128)._replace(
-        ln_modulate_tab=lambda *a: ops.ln_modulate_tab(*a, q8=True), gemm=_rowwise("gemm_w8a8"),
-        gemm_qkv=lambda x, w, b, cache_v, ws, ro, wl, B, L: ops.gemm_qkv_v_insert(None, w, b, cache_v, ws, ro, wl, xq=x)),
+    "int8": _quant_mode("quantize_rows", "quantize_rows", "q8", "w8a8", False, 128)._replace(gemm=_rowwise("gemm_w8a8")),
     "mxfp8": _quant_mode("quantize_mx", "quantize_mx", "mx", "mx", True, 128),
     "fp8_rowwise": _quant_mode("quantize_rows_f8", "quantize_rows_f8", "f8", "f8", False, 128)._replace(gemm=_rowwise("gemm_f8")),
     "mxfp6": _quant_mode("quantize_mx6", "quantize_mx6", "mx6", "mx6", True, 256),

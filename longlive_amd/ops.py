@@ -4,6 +4,7 @@ a kernel that faults can take the whole 8-GPU host down.
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import math
 from dataclasses import dataclass
@@ -74,14 +75,34 @@ class KernelTimer:
 timer: Optional[KernelTimer] = None
 
 
-def _t0(tag: str):
-    return timer.begin(tag) if timer is not None else None
+def _call(entry: str, *args, tag: Optional[str] = None, work: float = 0.0):
+    """One launch on the current stream: entry(*args, stream), its status checked, and under `tag` timed when a KernelTimer is on.
+    work = the launch's ALGORITHMIC FLOPs (MFMA kernels) or bytes (HBM-bound row kernels), SURVEY.md section 8d."""
+    lib = _lib.load()
+    timed = timer is not None and tag is not None
+    t0 = timer.begin(tag) if timed else None
+    _lib.check(getattr(lib, entry)(*args, _stream()), entry)
+    if timed:
+        timer.end(tag, t0, work)
 
 
-def _t1(tag: str, ev, work: float):
-    """work = the launch's ALGORITHMIC FLOPs (MFMA kernels) or bytes (HBM-bound row kernels), SURVEY.md section 8d."""
-    if timer is not None:
-        timer.end(tag, ev, work)
+def _host(entry: str, *args):
+    """A host-only entry (sizes, plans): no stream, nothing launched."""
+    _lib.check(getattr(_lib.load(), entry)(*args), entry)
+
+
+def _plan(entry: str, *args, size: int = 256) -> str:
+    """The text a *_plan entry writes about the launch it would make."""
+    buf = ctypes.create_string_buffer(size)
+    _host(entry, *args, buf, size)
+    return buf.value.decode()
+
+
+def _sizes(entry: str, *args, n: int = 2):
+    """The n byte counts a *_sizes entry writes through its trailing pointers."""
+    out = [ctypes.c_longlong(0) for _ in range(n)]
+    _host(entry, *args, *map(ctypes.byref, out))
+    return tuple(int(v.value) for v in out)
 
 
 def _chk(t: torch.Tensor, name: str, dtype=bf16) -> torch.Tensor:
@@ -98,88 +119,108 @@ def _ptr(t: Optional[torch.Tensor]) -> int:
     return 0 if t is None else t.data_ptr()
 
 
-def ln_modulate(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, out=None, tag: str = "ln_modulate"):
-    """x [B,L,C]; e [B,F,nmod,C]; mod [nmod,C] (causal_model.py:445,463-464,506-507); mod=None: `e` is a layer's slice of
-    modulation_table(), i.e. already bf16(mod + e)."""
+def _ptrs(ts) -> tuple:
+    return tuple(t.data_ptr() for t in ts)
+
+
+# ---- the three producers of a block linear's input, in bf16 and emitting a format's codes + scales (QFormat, below) ---------------
+def _produced(fmt, x, out=None) -> tuple:
+    """What a producer writes for input x: the bf16 tensor (`out` or a new one), or with a format its (codes, scales)."""
+    if fmt is not None:
+        return fmt.empty(tuple(x.shape), x.device)
+    out = torch.empty_like(x) if out is None else _chk(out, "out")
+    assert out.shape == x.shape
+    return (out,)
+
+
+def _ln_modulate(fmt, x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, out, tag: str):
+    """LN + modulate in bf16 (fmt None) or emitting fmt's codes + scales: the same checks, another allocation and entry."""
     _chk(x, "x"); _chk(e, "e")
     B, L, Cc = x.shape
     nmod = e.shape[-2]
-    assert e.shape == (B, num_frames, nmod, Cc), (e.shape, (B, num_frames, nmod, Cc))
+    assert e.shape == (B, num_frames, nmod, Cc), (e.shape, (B, num_frames, nmod, Cc)) if fmt is None else ""
     if mod is not None:
         _chk(mod, "mod")
         assert mod.numel() == nmod * Cc
-    out = torch.empty_like(x) if out is None else _chk(out, "out")
-    assert out.shape == x.shape
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate(x.data_ptr(), out.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx,
-                                  scale_idx, B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate")
-    _t1(tag, t0, 4.0 * x.numel())                    # read x, write out (bf16)
+    outs = _produced(fmt, x, out)
+    _call("ll_ln_modulate" + ("_" + fmt.name if fmt else ""), x.data_ptr(), *_ptrs(outs), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
+          B, L, Cc, num_frames, eps, tag=tag, work=(fmt.prod_bytes if fmt else 4.0) * x.numel())      # bf16: read x, write out
+    return outs if fmt else outs[0]
+
+
+def ln_modulate(x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, out=None, tag: str = "ln_modulate"):
+    """x [B,L,C]; e [B,F,nmod,C]; mod [nmod,C] (causal_model.py:445,463-464,506-507); mod=None: `e` is a layer's slice of
+    modulation_table(), i.e. already bf16(mod + e)."""
+    return _ln_modulate(None, x, e, mod, shift_idx, scale_idx, num_frames, eps, out, tag)
+
+
+def _ln_modulate_q(fmt: "QFormat", x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate emitting the fmt codes + scales of its bf16 output."""
+    return _ln_modulate(fmt, x, e, mod, shift_idx, scale_idx, num_frames, eps, None, tag)
+
+
+def _modulation_table(entry: str, dtype, e, mods, *mask):
+    _chk(e, "e"); _chk(mods, "mods")
+    B, F, nmod, Cc = e.shape
+    NL = mods.shape[0]
+    assert mods.shape == (NL, nmod, Cc), (mods.shape, e.shape)
+    out = torch.empty(NL, B, F, nmod, Cc, dtype=dtype, device=e.device)
+    _call(entry, e.data_ptr(), mods.data_ptr(), out.data_ptr(), NL, B * F, nmod, Cc, *mask)
     return out
 
 
 def modulation_table_f32(e, mods, one_plus_mask: int):
     """The fp32 form for ln_modulate_tab: [NL,B,F,nmod,C] float32 = float(bf16(mods[l] + e)), chunks in one_plus_mask
     float(bf16(1 + bf16(mods[l] + e))) -- the `1 + e[1]` of causal_model.py:445,463 once per (layer, frame)."""
-    _chk(e, "e"); _chk(mods, "mods")
-    B, F, nmod, Cc = e.shape
-    NL = mods.shape[0]
-    assert mods.shape == (NL, nmod, Cc), (mods.shape, e.shape)
-    out = torch.empty(NL, B, F, nmod, Cc, dtype=torch.float32, device=e.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_modulation_table_f32(e.data_ptr(), mods.data_ptr(), out.data_ptr(), NL, B * F, nmod, Cc, int(one_plus_mask),
-                                           _stream()), "ll_modulation_table_f32")
-    return out
+    return _modulation_table("ll_modulation_table_f32", torch.float32, e, mods, int(one_plus_mask))
 
 
-def ln_modulate_tab(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, q8: bool = False, tag: str = "ln_modulate"):
-    """ln_modulate / ln_modulate_q8 from a layer's slice tab [B,F,nmod,C] (float32) of modulation_table_f32, whose scale chunk
-    already holds 1 + scale: same bits.  Returns bf16 [B,L,C], or (int8 [B,L,C], float32 scale [B*L]) when q8."""
+def _ln_modulate_tab_q(fmt: Optional["QFormat"], x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
+    """ln_modulate_tab emitting the fmt codes + scales of its bf16 output (fmt None: the bf16 output itself)."""
     _chk(x, "x"); _chk(tab, "tab", torch.float32)
     B, L, Cc = x.shape
     nmod = tab.shape[2]
     assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
-    lib = _lib.load()
-    if q8:
-        q = torch.empty(B, L, Cc, dtype=torch.int8, device=x.device)
-        sc = torch.empty(B * L, dtype=torch.float32, device=x.device)
-        out = None
+    outs = _produced(fmt, x)
+    if fmt is None or fmt is Q8:      # one entry writes bf16 or int8 codes + scales, and takes a null for the other
+        entry, ptrs = "ll_ln_modulate_tab", (*_ptrs(outs), 0, 0) if fmt is None else (0, *_ptrs(outs))
     else:
-        out = torch.empty_like(x)
-        q = sc = None
-    t0 = _t0(tag)
-    _lib.check(lib.ll_ln_modulate_tab(x.data_ptr(), _ptr(out), _ptr(q), _ptr(sc), tab.data_ptr(), nmod, shift_idx, scale_idx,
-                                      B, L, Cc, num_frames, eps, _stream()), "ll_ln_modulate_tab")
-    _t1(tag, t0, (3.0 if q8 else 4.0) * B * L * Cc)
-    return (q, sc) if q8 else out
+        entry, ptrs = "ll_ln_modulate_tab_" + fmt.name, _ptrs(outs)
+    _call(entry, x.data_ptr(), *ptrs, tab.data_ptr(), nmod, shift_idx, scale_idx, B, L, Cc, num_frames, eps,
+          tag=tag, work=(fmt.prod_bytes if fmt else 4.0) * B * L * Cc)
+    return outs if fmt else outs[0]
+
+
+def ln_modulate_tab(x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, q8: bool = False, tag: str = "ln_modulate"):
+    """ln_modulate / ln_modulate_q8 from a layer's slice tab [B,F,nmod,C] (float32) of modulation_table_f32, whose scale chunk
+    already holds 1 + scale: same bits.  Returns bf16 [B,L,C], or (int8 [B,L,C], float32 scale [B*L]) when q8 (ln_modulate_tab_q8)."""
+    return _ln_modulate_tab_q(Q8 if q8 else None, x, tab, shift_idx, scale_idx, num_frames, eps, tag)
 
 
 def modulation_table(e, mods):
     """e [B,F,nmod,C] (per forward), mods [NL,nmod,C] (per layer) -> [NL,B,F,nmod,C] = bf16(mods[l] + e): what every block
     computes as `self.modulation.unsqueeze(1) + e` (causal_model.py:440), for all layers in one launch."""
-    _chk(e, "e"); _chk(mods, "mods")
-    B, F, nmod, Cc = e.shape
-    NL = mods.shape[0]
-    assert mods.shape == (NL, nmod, Cc), (mods.shape, e.shape)
-    out = torch.empty(NL, B, F, nmod, Cc, dtype=bf16, device=e.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_modulation_table(e.data_ptr(), mods.data_ptr(), out.data_ptr(), NL, B * F, nmod, Cc, _stream()),
-               "ll_modulation_table")
-    return out
+    return _modulation_table("ll_modulation_table", bf16, e, mods)
 
 
-def layernorm_affine(x, w, b, eps: float, out=None):
+def _layernorm_affine(fmt, x, w, b, eps: float, out=None):
+    """LayerNorm with weight and bias in bf16 (fmt None) or emitting fmt's codes + scales."""
     _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
     Cc = x.shape[-1]
     assert w.numel() == Cc and b.numel() == Cc
-    out = torch.empty_like(x) if out is None else _chk(out, "out")
-    assert out.shape == x.shape
-    lib = _lib.load()
-    t0 = _t0("layernorm_affine")
-    _lib.check(lib.ll_layernorm_affine(x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), x.numel() // Cc, Cc,
-                                       eps, _stream()), "ll_layernorm_affine")
-    _t1("layernorm_affine", t0, 4.0 * x.numel())
-    return out
+    outs = _produced(fmt, x, out)
+    _call("ll_layernorm_affine" + ("_" + fmt.name if fmt else ""), x.data_ptr(), w.data_ptr(), b.data_ptr(), *_ptrs(outs), x.numel() // Cc, Cc,
+          eps, tag="layernorm_affine", work=(fmt.prod_bytes if fmt else 4.0) * x.numel())
+    return outs if fmt else outs[0]
+
+
+def layernorm_affine(x, w, b, eps: float, out=None):
+    return _layernorm_affine(None, x, w, b, eps, out)
+
+
+def _layernorm_affine_q(fmt: "QFormat", x, w, b, eps: float):
+    """layernorm_affine emitting the fmt codes + scales of its bf16 output."""
+    return _layernorm_affine(fmt, x, w, b, eps)
 
 
 def rmsnorm(x, w, eps: float, out=None, C: Optional[int] = None):
@@ -197,11 +238,7 @@ def rmsnorm(x, w, eps: float, out=None, C: Optional[int] = None):
     assert out.dtype == bf16 and out.is_cuda and out.stride(-1) == 1
     o2 = out.flatten(0, -2) if out.dim() > 2 else out
     assert o2.dim() == 2 and o2.data_ptr() == out.data_ptr() and o2.shape[0] == rows and o2.shape[1] >= Cc
-    lib = _lib.load()
-    t0 = _t0("rmsnorm")
-    _lib.check(lib.ll_rmsnorm(x2.data_ptr(), w.data_ptr(), o2.data_ptr(), rows, Cc, ldx, o2.stride(0), eps, _stream()),
-               "ll_rmsnorm")
-    _t1("rmsnorm", t0, 4.0 * rows * Cc)
+    _call("ll_rmsnorm", x2.data_ptr(), w.data_ptr(), o2.data_ptr(), rows, Cc, ldx, o2.stride(0), eps, tag="rmsnorm", work=4.0 * rows * Cc)
     return out
 
 
@@ -222,15 +259,11 @@ def qk_norm_rope_kv_store(qkv, wq, wk, rope_f, rope_hw, q_out, cache_k, cache_v,
     nf = half - 2 * (half // 3)
     assert rope_f.shape == (1024, nf, 2), rope_f.shape
     assert rope_hw.shape == (frame_len, half - nf, 2), rope_hw.shape
-    lib = _lib.load()
-    t0 = _t0("qk_norm_rope_kv_store")
-    _lib.check(lib.ll_qk_norm_rope_kv_store(qkv.data_ptr(), wq.data_ptr(), wk.data_ptr(), rope_f.data_ptr(),
-                                            rope_hw.data_ptr(), q_out.data_ptr(), cache_k.data_ptr(),
-                                            _ptr(cache_v), B, L, Cc, head_dim, frame_len, start_frame, S,
-                                            write_start, roped_offset, write_len, eps, _stream()),
-               "ll_qk_norm_rope_kv_store")
     nv = 1 if cache_v is not None else 0
-    _t1("qk_norm_rope_kv_store", t0, 2.0 * ((2 + nv) * B * L * Cc + B * L * Cc + (1 + nv) * B * write_len * Cc))   # q,k(,v) in; q out; k(,v) -> cache
+    _call("ll_qk_norm_rope_kv_store", qkv.data_ptr(), wq.data_ptr(), wk.data_ptr(), rope_f.data_ptr(), rope_hw.data_ptr(), q_out.data_ptr(),
+          cache_k.data_ptr(), _ptr(cache_v), B, L, Cc, head_dim, frame_len, start_frame, S, write_start, roped_offset, write_len, eps,
+          tag="qk_norm_rope_kv_store",
+          work=2.0 * ((2 + nv) * B * L * Cc + B * L * Cc + (1 + nv) * B * write_len * Cc))   # q,k(,v) in; q out; k(,v) -> cache
     return q_out
 
 
@@ -239,24 +272,28 @@ def kv_roll(cache_k, cache_v, dst: int, src: int, n: int):
     B, S = cache_k.shape[:2]
     Cc = cache_k.numel() // (B * S)
     assert cache_v.shape == cache_k.shape
-    lib = _lib.load()
-    t0 = _t0("kv_roll")
-    _lib.check(lib.ll_kv_roll(cache_k.data_ptr(), cache_v.data_ptr(), B, S, Cc, dst, src, n, _stream()), "ll_kv_roll")
-    _t1("kv_roll", t0, 2.0 * 2 * 2 * B * n * Cc)     # k and v, read + write, bf16
+    _call("ll_kv_roll", cache_k.data_ptr(), cache_v.data_ptr(), B, S, Cc, dst, src, n,
+          tag="kv_roll", work=2.0 * 2 * 2 * B * n * Cc)     # k and v, read + write, bf16
 
 
-def gemm(x, w, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
-         rows_per_batch: int = 0, frame_len: int = 0, tag: str = "gemm"):
-    """out[M,N] = epilogue(x[M,K] @ w[N,K]^T + bias).  x may be any [..., K] contiguous tensor."""
+# ---- linears -----------------------------------------------------------------------------------------------------------------------
+def _linear(x, w, bias, out=None, detail: bool = False):
+    """Operands of out[M,N] = x[M,K] @ w[N,K]^T + bias, x any [..., K] contiguous tensor: (M, N, K, out), `out` new when None."""
     _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias")
     K = x.shape[-1]
     M = x.numel() // K
     N = w.shape[0]
-    assert w.shape == (N, K) and bias.numel() == N, (w.shape, bias.shape, K)
+    assert w.shape == (N, K) and bias.numel() == N, (w.shape, bias.shape, K) if detail else ""
     if out is None:
         out = torch.empty(*x.shape[:-1], N, dtype=bf16, device=x.device)
     _chk(out, "out")
     assert out.numel() == M * N
+    return M, N, K, out
+
+
+def _epilogue(epilogue: int, M: int, N: int, res, e, mod, frame_len: int, detail: bool = False) -> int:
+    """The operands gemm()'s epilogues read, checked: res [M,N] (EPI_BIAS_RES, EPI_BIAS_GATE_RES), e [.., nmod, N] per frame and
+    mod [nmod, N] (EPI_BIAS_GATE_RES).  Returns nmod (0 without a gate)."""
     nmod = 0
     if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
         _chk(res, "res")
@@ -264,25 +301,29 @@ def gemm(x, w, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=N
     if epilogue == EPI_BIAS_GATE_RES:
         _chk(e, "e")
         nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N, (e.shape, M, frame_len)
+        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N, (e.shape, M, frame_len) if detail else ""
         if mod is not None:         # None: e already holds bf16(mod + e) (modulation_table)
             _chk(mod, "mod")
             assert mod.numel() == nmod * N
-    lib = _lib.load()
-    t0 = _t0(tag)
-    if M <= 1024 and M * N <= (1 << 22) and epilogue in (EPI_BIAS, EPI_BIAS_RES) and _ksplit_plan(lib, M, N, K):
+    return nmod
+
+
+def gemm(x, w, bias, epilogue: int = EPI_BIAS, out=None, res=None, e=None, mod=None, gate_idx: int = 0,
+         rows_per_batch: int = 0, frame_len: int = 0, tag: str = "gemm"):
+    """out[M,N] = epilogue(x[M,K] @ w[N,K]^T + bias).  x may be any [..., K] contiguous tensor."""
+    M, N, K, out = _linear(x, w, bias, out, detail=True)
+    nmod = _epilogue(epilogue, M, N, res, e, mod, frame_len, detail=True)
+    if M <= 1024 and M * N <= (1 << 22) and epilogue in (EPI_BIAS, EPI_BIAS_RES) and _ksplit_plan(M, N, K):
         # few rows (the text side: umT5 at 512 tokens, text K / V projections): K cut into ranges so that the grid fills the device.
         # Taken by itself only up to 1024 rows: the DiT's own linears (a 1-frame chunk has M = 1560) never come here, so the order
         # of a row's fp32 sum there does not depend on M or on the device's CU count.  Inside this region the number of ranges
         # depends on N and K only (gemm_ksplit_splits); WHETHER the path is taken still depends on M and the CU count.
         ws = ksplit_workspace(x.device, M, N, K)
-        _lib.check(lib.ll_gemm_bf16_ksplit(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, K, N, epilogue,
-                                           _ptr(res), ws.data_ptr(), ws.numel(), _stream()), "ll_gemm_bf16_ksplit")
+        _call("ll_gemm_bf16_ksplit", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, K, N, epilogue, _ptr(res),
+              ws.data_ptr(), ws.numel(), tag=tag, work=2.0 * M * N * K)
     else:
-        _lib.check(lib.ll_gemm_bf16(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, K, N, epilogue,
-                                    _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
-                   "ll_gemm_bf16")
-    _t1(tag, t0, 2.0 * M * N * K)
+        _call("ll_gemm_bf16", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, K, N, epilogue, _ptr(res), _ptr(e),
+              _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, tag=tag, work=2.0 * M * N * K)
     return out
 
 
@@ -295,34 +336,23 @@ def gemm_ssq(x, w, bias, out=None, tag: str = "gemm"):
     """(x @ w^T + bias [.., N] bf16, ssq [N / 128, M] fp32): the bias GEMM whose epilogue also leaves, per row and 128-column n-tile,
     the sum of squares of its bf16 outputs -- the statistics of the RMSNorm that follows a q projection (model.py:172), consumed by
     flash_attn_qnorm.  Only for shapes gemm_ssq_planes() accepts."""
-    _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias")
-    K = x.shape[-1]
-    M = x.numel() // K
-    N = w.shape[0]
-    assert w.shape == (N, K) and bias.numel() == N
-    if out is None:
-        out = torch.empty(*x.shape[:-1], N, dtype=bf16, device=x.device)
-    _chk(out, "out")
-    assert out.numel() == M * N
+    M, N, K, out = _linear(x, w, bias, out)
     planes = gemm_ssq_planes(M, N, K)
     if planes == 0:
         raise RuntimeError(f"gemm_ssq: {M} x {N} x {K} is not covered by the generated kernel (use gemm + rmsnorm)")
     ssq = torch.empty(planes, M, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_bf16_ssq(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), ssq.data_ptr(), M, N, K, K, N, _stream()),
-               "ll_gemm_bf16_ssq")
-    _t1(tag, t0, 2.0 * M * N * K)
+    _call("ll_gemm_bf16_ssq", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), ssq.data_ptr(), M, N, K, K, N,
+          tag=tag, work=2.0 * M * N * K)
     return out, ssq
 
 
 _ksplit_ws = {}
 
 
-def _ksplit_plan(lib, M: int, N: int, K: int) -> int:
+def _ksplit_plan(M: int, N: int, K: int) -> int:
     """K-ranges the small-M path would use (0 = not taken).  Asked per call: the answer follows the library's tuning, and only
     calls with few rows get here (the DiT's block linears do not)."""
-    return int(lib.ll_gemm_ksplit_plan(M, N, K))
+    return int(_lib.load().ll_gemm_ksplit_plan(M, N, K))
 
 
 def _dev_index(device) -> int:
@@ -340,42 +370,29 @@ def ksplit_workspace(device, M: int, N: int, K: int) -> torch.Tensor:
     return buf
 
 
+def _v_cache(cache_v, B: int, N: int) -> int:
+    """cache_v [B, S, H, D] for the V third of a [.., N = 3C] projection: S."""
+    S = cache_v.shape[1]
+    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
+    return S
+
+
 def gemm_qkv_v_insert(x, w, bias, cache_v, write_start: int, roped_offset: int, write_len: int, xq=None, tag: str = "gemm_qkv"):
     """The fused q|k|v projection x [B,L,K] @ w [3C,K]^T + bias with the V third inserted into cache_v [B,S,H,D] by the GEMM
     epilogue (token t -> slot write_start + t - roped_offset for 0 <= t - roped_offset < write_len).  Returns the [B,L,3C]
     buffer whose q and k thirds are valid (the v third is unwritten).  xq = (int8 [B,L,K], scale [B*L]) with int8 w = (wq, sw):
-    the W8A8 form."""
-    _chk(bias, "bias"); _chk(cache_v, "cache_v")
-    int8 = xq is not None
-    if int8:
-        xi, sx = xq
-        wq, sw = w
-        _chk(xi, "xq", torch.int8); _chk(sx, "sx", torch.float32); _chk(wq, "wq", torch.int8); _chk(sw, "sw", torch.float32)
-        B, L, K = xi.shape
-        N = wq.shape[0]
-        assert wq.shape == (N, K) and sx.numel() == B * L and sw.numel() == N
-        dev = xi.device
-    else:
-        _chk(x, "x"); _chk(w, "w")
-        B, L, K = x.shape
-        N = w.shape[0]
-        assert w.shape == (N, K)
-        dev = x.device
-    assert bias.numel() == N and N % 3 == 0
-    S = cache_v.shape[1]
-    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
-    out = torch.empty(B, L, N, dtype=bf16, device=dev)
-    lib = _lib.load()
-    t0 = _t0(tag)
-    if int8:
-        _lib.check(lib.ll_gemm_w8a8_qkv(xi.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                        B * L, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-                   "ll_gemm_w8a8_qkv")
-    else:
-        _lib.check(lib.ll_gemm_bf16_qkv(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B * L, N, K, K, N,
-                                        cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()),
-                   "ll_gemm_bf16_qkv")
-    _t1(tag, t0, 2.0 * B * L * N * K)
+    the W8A8 form (gemm_w8a8_qkv_v_insert)."""
+    if xq is not None:
+        B, L, _ = xq[0].shape
+        assert xq[1].numel() == B * L
+        return gemm_w8a8_qkv_v_insert(xq, w, bias, cache_v, write_start, roped_offset, write_len, B, L, tag=tag)
+    _chk(cache_v, "cache_v")
+    M, N, K, out = _linear(x, w, bias)
+    B, L, _ = x.shape
+    assert N % 3 == 0
+    S = _v_cache(cache_v, B, N)
+    _call("ll_gemm_bf16_qkv", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), B * L, N, K, K, N, cache_v.data_ptr(), B, L, S,
+          write_start, roped_offset, write_len, tag=tag, work=2.0 * B * L * N * K)
     return out
 
 
@@ -390,28 +407,53 @@ def quantize_rows(x, q=None, scale=None):
         scale = torch.empty(rows, dtype=torch.float32, device=x.device)
     _chk(q, "q", torch.int8); _chk(scale, "scale", torch.float32)
     assert q.numel() == x.numel() and scale.numel() == rows
-    lib = _lib.load()
-    t0 = _t0("quantize_rows")
-    _lib.check(lib.ll_quantize_rows(x.data_ptr(), q.data_ptr(), scale.data_ptr(), rows, K, K, _stream()), "ll_quantize_rows")
-    _t1("quantize_rows", t0, 3.0 * x.numel())
+    _call("ll_quantize_rows", x.data_ptr(), q.data_ptr(), scale.data_ptr(), rows, K, K, tag="quantize_rows", work=3.0 * x.numel())
     return q, scale
 
 
 def linear_small(x, w, bias, act_in: int = 0, act_out: int = 0):
     """Few-row linear (time embedding); rows are processed 8 at a time."""
-    _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias")
-    K = x.shape[-1]
-    M = x.numel() // K
-    N = w.shape[0]
-    assert w.shape == (N, K) and bias.numel() == N
-    out = torch.empty(*x.shape[:-1], N, dtype=bf16, device=x.device)
-    lib = _lib.load()
+    M, N, K, out = _linear(x, w, bias)
     x2, o2 = x.view(M, K), out.view(M, N)
     for m0 in range(0, M, 8):
-        m = min(8, M - m0)
-        _lib.check(lib.ll_linear_small(x2[m0:].data_ptr(), w.data_ptr(), bias.data_ptr(), o2[m0:].data_ptr(), m, N, K,
-                                       act_in, act_out, _stream()), "ll_linear_small")
+        _call("ll_linear_small", x2[m0:].data_ptr(), w.data_ptr(), bias.data_ptr(), o2[m0:].data_ptr(), min(8, M - m0), N, K, act_in, act_out)
     return out
+
+
+# ---- attention ---------------------------------------------------------------------------------------------------------------------
+def _segs2(segments, S):
+    """Up to two key ranges [(start, end), ...] within [0, S), empty ones dropped: (s0, e0, s1, e1), the second (0, 0) when absent."""
+    segs = [(int(a), int(b)) for a, b in segments if b > a]
+    assert 1 <= len(segs) <= 2, segments
+    for a, b_ in segs:
+        assert 0 <= a < b_ <= S, (segments, S)
+    (s0, e0) = segs[0]
+    (s1, e1) = segs[1] if len(segs) == 2 else (0, 0)
+    return s0, e0, s1, e1
+
+
+def _attn_q(q):
+    _chk(q, "q")
+    B, Lq, H, D = q.shape
+    assert D == 128, "kernel is specialised for head_dim 128"
+    return B, Lq, H, D
+
+
+def _attn_qkv(q, k, v):
+    """q [B,Lq,H,128], k and v [B,Sk,H,128], all contiguous: (B, Lq, H, D, Sk)."""
+    B, Lq, H, D = _attn_q(q)
+    _chk(k, "k"); _chk(v, "v")
+    Sk = k.shape[1]
+    assert k.shape == (B, Sk, H, D) and v.shape == k.shape
+    return B, Lq, H, D, Sk
+
+
+def _attn_flops(B: int, H: int, Lq: int, nkeys: int, D: int) -> float:
+    return 4.0 * B * H * Lq * nkeys * D      # algorithmic FLOPs: QK^T + PV
+
+
+def _attn_scale(scale, D: int) -> float:
+    return 1.0 / math.sqrt(D) if scale is None else scale
 
 
 def flash_attn(q, k, v, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None, out_fmt: Optional["QFormat"] = None):
@@ -421,32 +463,12 @@ def flash_attn(q, k, v, segments, out=None, scale: Optional[float] = None, tag: 
     epilogue where flash_attn_q_ok says so and by the two launches otherwise."""
     if out_fmt is not None:
         return _flash_attn_q(out_fmt, q, k, v, segments, scale, tag)
-    _chk(q, "q"); _chk(k, "k"); _chk(v, "v")
-    B, Lq, H, D = q.shape
-    assert D == 128, "kernel is specialised for head_dim 128"
-    Sk = k.shape[1]
-    assert k.shape == (B, Sk, H, D) and v.shape == k.shape
-    segs = [(int(a), int(b)) for a, b in segments if b > a]
-    assert 1 <= len(segs) <= 2, segments
-    for a, b_ in segs:
-        assert 0 <= a < b_ <= Sk, (segments, Sk)
-    (s0, e0) = segs[0]
-    (s1, e1) = segs[1] if len(segs) == 2 else (0, 0)
+    B, Lq, H, D, Sk = _attn_qkv(q, k, v)
+    s0, e0, s1, e1 = _segs2(segments, Sk)
     out = torch.empty_like(q) if out is None else _chk(out, "out")
     assert out.shape == q.shape
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    lib = _lib.load()
-    t0 = None
-    if timer is not None:
-        nkeys = (e0 - s0) + (e1 - s1)
-        tag = tag or "flash_attn"
-        t0 = timer.begin(tag)
-    _lib.check(lib.ll_flash_attn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Lq, H, H * D, H * D,
-                                 H * D, Sk * H * D, s0, e0 - s0, s1, e1 - s1, scale, _stream()),
-               "ll_flash_attn")
-    if timer is not None:
-        timer.end(tag, t0, 4.0 * B * H * Lq * nkeys * D)     # algorithmic FLOPs: QK^T + PV
+    _call("ll_flash_attn", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Lq, H, H * D, H * D, H * D, Sk * H * D,
+          s0, e0 - s0, s1, e1 - s1, _attn_scale(scale, D), tag=tag or "flash_attn", work=_attn_flops(B, H, Lq, (e0 - s0) + (e1 - s1), D))
     return out
 
 
@@ -470,31 +492,20 @@ def flash_attn_q_ok(fmt, H: int, segments) -> bool:
 
 def flash_attn_q_plan(fmt, Lq: int, H: int, B: int, segments) -> str:
     """Kernel and grid of a flash_attn(..., out_fmt=fmt) call, or that it takes two launches (host only)."""
-    import ctypes
     s0, e0, s1, e1 = _segs2(segments, 1 << 30)
-    buf = ctypes.create_string_buffer(512)
-    _lib.check(_lib.load().ll_flash_attn_q_plan(_qfmt_id(fmt), Lq, H, B, s0, e0 - s0, s1, e1 - s1, buf, 512), "ll_flash_attn_q_plan")
-    return buf.value.decode()
+    return _plan("ll_flash_attn_q_plan", _qfmt_id(fmt), Lq, H, B, s0, e0 - s0, s1, e1 - s1, size=512)
 
 
 def _flash_attn_q(fmt, q, k, v, segments, scale, tag):
     B, Lq, H, D = q.shape
     if not flash_attn_q_ok(fmt, H, segments):
         return _quantize(fmt, flash_attn(q, k, v, segments, scale=scale, tag=tag).view(B, Lq, H * D))
-    _chk(q, "q"); _chk(k, "k"); _chk(v, "v")
-    assert D == 128, "kernel is specialised for head_dim 128"
-    Sk = k.shape[1]
-    assert k.shape == (B, Sk, H, D) and v.shape == k.shape
+    B, Lq, H, D, Sk = _attn_qkv(q, k, v)
     s0, e0, s1, e1 = _segs2(segments, Sk)
     codes, scales = fmt.empty((B, Lq, H * D), q.device)
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    tag = tag or "flash_attn"
-    t0 = _t0(tag)
-    _lib.check(_lib.load().ll_flash_attn_q(_qfmt_id(fmt), q.data_ptr(), k.data_ptr(), v.data_ptr(), codes.data_ptr(), scales.data_ptr(), B, Lq,
-                                           H, H * D, codes.shape[-1], scales.shape[-1], H * D, Sk * H * D, s0, e0 - s0, s1, e1 - s1, scale,
-                                           _stream()), "ll_flash_attn_q")
-    _t1(tag, t0, 4.0 * B * H * Lq * ((e0 - s0) + (e1 - s1)) * D)     # algorithmic FLOPs: QK^T + PV
+    _call("ll_flash_attn_q", _qfmt_id(fmt), q.data_ptr(), k.data_ptr(), v.data_ptr(), codes.data_ptr(), scales.data_ptr(), B, Lq, H, H * D,
+          codes.shape[-1], scales.shape[-1], H * D, Sk * H * D, s0, e0 - s0, s1, e1 - s1, _attn_scale(scale, D),
+          tag=tag or "flash_attn", work=_attn_flops(B, H, Lq, (e0 - s0) + (e1 - s1), D))
     return codes, scales
 
 
@@ -504,18 +515,13 @@ def flash_attn_qnorm(q, ssq, norm_w, eps: float, k, v, nkeys: int, out=None, sca
     _chk(q, "q"); _chk(k, "k"); _chk(v, "v"); _chk(norm_w, "norm_w"); _chk(ssq, "ssq", torch.float32)
     B, Lq, H, D = q.shape
     assert D == 128 and norm_w.numel() == H * D and ssq.shape == (H, B * Lq), (q.shape, ssq.shape, norm_w.shape)
-    Sk = k.shape[1]
-    assert k.shape == (B, Sk, H, D) and v.shape == k.shape and 0 < nkeys <= Sk
+    Sk = _attn_qkv(q, k, v)[4]
+    assert 0 < nkeys <= Sk
     out = torch.empty_like(q) if out is None else _chk(out, "out")
     assert out.shape == q.shape
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    lib = _lib.load()
-    tag = tag or "flash_attn"
-    t0 = _t0(tag)
-    _lib.check(lib.ll_flash_attn_qnorm(q.data_ptr(), ssq.data_ptr(), norm_w.data_ptr(), eps, k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                       B, Lq, H, H * D, H * D, H * D, Sk * H * D, 0, nkeys, scale, _stream()), "ll_flash_attn_qnorm")
-    _t1(tag, t0, 4.0 * B * H * Lq * nkeys * D)
+    _call("ll_flash_attn_qnorm", q.data_ptr(), ssq.data_ptr(), norm_w.data_ptr(), eps, k.data_ptr(), v.data_ptr(), out.data_ptr(),
+          B, Lq, H, H * D, H * D, H * D, Sk * H * D, 0, nkeys, _attn_scale(scale, D),
+          tag=tag or "flash_attn", work=_attn_flops(B, H, Lq, nkeys, D))
     return out
 
 
@@ -524,8 +530,7 @@ def patchify(x):
     _chk(x, "x")
     B, F, Cin, H, W = x.shape
     out = torch.empty(B, F * (H // 2) * (W // 2), Cin * 4, dtype=bf16, device=x.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_patchify(x.data_ptr(), out.data_ptr(), B, F, Cin, H, W, _stream()), "ll_patchify")
+    _call("ll_patchify", x.data_ptr(), out.data_ptr(), B, F, Cin, H, W)
     return out
 
 
@@ -534,8 +539,7 @@ def sinusoid(t, dim: int):
     _chk(t, "t", torch.float32)
     n = t.numel()
     out = torch.empty(n, dim, dtype=bf16, device=t.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_sinusoid(t.data_ptr(), out.data_ptr(), n, dim, _stream()), "ll_sinusoid")
+    _call("ll_sinusoid", t.data_ptr(), out.data_ptr(), n, dim)
     return out
 
 
@@ -546,9 +550,7 @@ def unpatchify_x0(head, xt, sigma) -> Tuple[torch.Tensor, torch.Tensor]:
     assert head.shape == (B, F * (H // 2) * (W // 2), 4 * Cout), head.shape
     assert sigma.numel() == B * F
     flow, x0 = torch.empty_like(xt), torch.empty_like(xt)
-    lib = _lib.load()
-    _lib.check(lib.ll_unpatchify_x0(head.data_ptr(), xt.data_ptr(), sigma.data_ptr(), flow.data_ptr(), x0.data_ptr(),
-                                    B, F, Cout, H, W, _stream()), "ll_unpatchify_x0")
+    _call("ll_unpatchify_x0", head.data_ptr(), xt.data_ptr(), sigma.data_ptr(), flow.data_ptr(), x0.data_ptr(), B, F, Cout, H, W)
     return flow, x0
 
 
@@ -558,9 +560,7 @@ def add_noise(x0, noise, sigma):
     N = x0.shape[0]
     assert noise.shape == x0.shape and sigma.numel() == N
     out = torch.empty_like(x0)
-    lib = _lib.load()
-    _lib.check(lib.ll_add_noise(x0.data_ptr(), noise.data_ptr(), sigma.data_ptr(), out.data_ptr(), N,
-                                x0.numel() // N, _stream()), "ll_add_noise")
+    _call("ll_add_noise", x0.data_ptr(), noise.data_ptr(), sigma.data_ptr(), out.data_ptr(), N, x0.numel() // N)
     return out
 
 
@@ -569,9 +569,7 @@ def sigma_lookup(t, timesteps, sigmas):
     _chk(t, "t", torch.float32); _chk(timesteps, "timesteps", torch.float32); _chk(sigmas, "sigmas", torch.float32)
     assert timesteps.numel() == sigmas.numel()
     out = torch.empty(t.numel(), dtype=torch.float32, device=t.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_sigma_lookup(t.data_ptr(), timesteps.data_ptr(), sigmas.data_ptr(), out.data_ptr(), t.numel(),
-                                   timesteps.numel(), _stream()), "ll_sigma_lookup")
+    _call("ll_sigma_lookup", t.data_ptr(), timesteps.data_ptr(), sigmas.data_ptr(), out.data_ptr(), t.numel(), timesteps.numel())
     return out
 
 
@@ -604,17 +602,25 @@ def pack_conv_weight(w: torch.Tensor, bias: torch.Tensor):
     return packed.contiguous(), b, (cin, cout8, kpad, kt, kh)
 
 
+def _conv_in(x, packed, bias, geo, hist: int, name: Optional[str] = None, takes: str = ""):
+    """Input, weights and bias of a channels-last convolution against its pack_conv_weight geometry: x is [hist + T, H, W, Cin], the
+    stream's previous `hist` input frames first.  Returns (T, H, W).  `name`: the wrapper the refusals speak for."""
+    cin, cout, kpad, kt, kh = geo
+    _chk(x, "x"); _chk(packed, "w"); _chk(bias, "bias")
+    T, H, W, C = x.shape[0] - hist, x.shape[1], x.shape[2], x.shape[3]
+    assert T >= 1, f"{name}: {takes}" if name else ""
+    assert C == cin, f"{name}: input has {C} channels, weights expect {cin}" if name else ""
+    assert packed.shape == (cout, kpad) and bias.numel() == cout
+    return T, H, W
+
+
 def conv_cl(x, packed, bias, geo, upsample: bool = False, res=None, out=None):
     """Channels-last convolution.  Temporal kernels (kt == 3): x is [2 + T, H, W, Cin] -- the stream's previous two input
     frames (zeros at its start) followed by the T new ones; otherwise x is [T, H, W, Cin].  packed/bias/geo from
     pack_conv_weight.  Returns [T, H<<up, W<<up, Cout8]."""
     cin, cout, kpad, kt, kh = geo
-    _chk(x, "x"); _chk(packed, "w"); _chk(bias, "bias")
     hist = 2 if kt > 1 else 0
-    T, H, W, C = x.shape[0] - hist, x.shape[1], x.shape[2], x.shape[3]
-    assert T >= 1, "conv_cl: a temporal convolution takes [2 + T, H, W, Cin] (two history frames first)"
-    assert C == cin, f"conv_cl: input has {C} channels, weights expect {cin}"
-    assert packed.shape == (cout, kpad) and bias.numel() == cout
+    T, H, W = _conv_in(x, packed, bias, geo, hist, "conv_cl", "a temporal convolution takes [2 + T, H, W, Cin] (two history frames first)")
     Ho, Wo = (2 * H, 2 * W) if upsample else (H, W)
     if out is None:
         out = torch.empty(T, Ho, Wo, cout, dtype=bf16, device=x.device)
@@ -622,13 +628,8 @@ def conv_cl(x, packed, bias, geo, upsample: bool = False, res=None, out=None):
     if res is not None:
         _chk(res, "res")
         assert res.shape == out.shape
-    lib = _lib.load()
-    t0 = timer.begin("conv") if timer is not None else None
-    _lib.check(lib.ll_conv_cl(x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(),
-                              _ptr(res), out.data_ptr(), T, H, W, cin, cout, kpad, kt, kh, 1 if upsample else 0, cout,
-                              _stream()), "ll_conv_cl")
-    if timer is not None:
-        timer.end("conv", t0, 2.0 * T * Ho * Wo * cout * (kt * kh * kh * cin))
+    _call("ll_conv_cl", x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(), _ptr(res), out.data_ptr(),
+          T, H, W, cin, cout, kpad, kt, kh, 1 if upsample else 0, cout, tag="conv", work=2.0 * T * Ho * Wo * cout * (kt * kh * kh * cin))
     return out
 
 
@@ -643,23 +644,19 @@ def conv_cl_rms(x, packed, bias, geo, gamma, out_rms, silu: bool = True, upsampl
     ResidualBlock feeds its next convolution (vae.py:193-220).  want_raw: also return the un-normalised tensor (the next block's
     shortcut), else None.  Only where conv_cl_rms_ok(...)."""
     cin, cout, kpad, kt, kh = geo
-    _chk(x, "x"); _chk(packed, "w"); _chk(bias, "bias"); _chk(gamma, "gamma"); _chk(out_rms, "out_rms")
     hist = 2 if kt > 1 else 0
-    T, H, W, C = x.shape[0] - hist, x.shape[1], x.shape[2], x.shape[3]
-    assert T >= 1 and C == cin and packed.shape == (cout, kpad) and bias.numel() == cout and gamma.numel() == cout
+    T, H, W = _conv_in(x, packed, bias, geo, hist)
+    _chk(gamma, "gamma"); _chk(out_rms, "out_rms")
+    assert gamma.numel() == cout
     Ho, Wo = (2 * H, 2 * W) if upsample else (H, W)
     assert out_rms.shape == (T, Ho, Wo, cout) and out_rms.is_contiguous()
     out = torch.empty(T, Ho, Wo, cout, dtype=bf16, device=x.device) if want_raw else None
     if res is not None:
         _chk(res, "res")
         assert res.shape == out_rms.shape
-    lib = _lib.load()
-    t0 = timer.begin("conv") if timer is not None else None
-    _lib.check(lib.ll_conv_cl_rms(x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(), _ptr(res),
-                                  _ptr(out), gamma.data_ptr(), out_rms.data_ptr(), 1 if silu else 0, T, H, W, cin, cout, kpad, kt, kh,
-                                  1 if upsample else 0, cout, _stream()), "ll_conv_cl_rms")
-    if timer is not None:
-        timer.end("conv", t0, 2.0 * T * Ho * Wo * cout * (kt * kh * kh * cin))
+    _call("ll_conv_cl_rms", x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(), _ptr(res), _ptr(out),
+          gamma.data_ptr(), out_rms.data_ptr(), 1 if silu else 0, T, H, W, cin, cout, kpad, kt, kh, 1 if upsample else 0, cout,
+          tag="conv", work=2.0 * T * Ho * Wo * cout * (kt * kh * kh * cin))
     return out
 
 
@@ -669,9 +666,7 @@ def rms_silu_cl(x, gamma, silu: bool = True, out=None):
     assert gamma.numel() == C
     if out is None:
         out = torch.empty_like(x)
-    lib = _lib.load()
-    _lib.check(lib.ll_rms_silu_cl(x.data_ptr(), gamma.data_ptr(), out.data_ptr(), x.numel() // C, C, 1 if silu else 0,
-                                  _stream()), "ll_rms_silu_cl")
+    _call("ll_rms_silu_cl", x.data_ptr(), gamma.data_ptr(), out.data_ptr(), x.numel() // C, C, 1 if silu else 0)
     return out
 
 
@@ -682,9 +677,7 @@ def softmax_rows(s, scale: float, n_valid: Optional[int] = None, out=None):
     N = ld if n_valid is None else n_valid
     if out is None:
         out = torch.empty_like(s)
-    lib = _lib.load()
-    _lib.check(lib.ll_softmax_rows(s.data_ptr(), out.data_ptr(), s.numel() // ld, N, ld, float(scale), _stream()),
-               "ll_softmax_rows")
+    _call("ll_softmax_rows", s.data_ptr(), out.data_ptr(), s.numel() // ld, N, ld, float(scale))
     return out
 
 
@@ -694,9 +687,7 @@ def vae_unscale_cl(z, mean, inv_std):
     T, C, h, w = z.shape
     assert mean.numel() == C and inv_std.numel() == C
     out = torch.empty(T, h, w, C, dtype=bf16, device=z.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_vae_unscale_cl(z.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), out.data_ptr(), T, C, h, w, _stream()),
-               "ll_vae_unscale_cl")
+    _call("ll_vae_unscale_cl", z.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), out.data_ptr(), T, C, h, w)
     return out
 
 
@@ -705,23 +696,55 @@ def cl_to_tchw_clamp(x):
     _chk(x, "x")
     T, H, W, C = x.shape
     out = torch.empty(T, 3, H, W, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_cl_to_tchw_clamp(x.data_ptr(), out.data_ptr(), T, H, W, C, _stream()), "ll_cl_to_tchw_clamp")
+    _call("ll_cl_to_tchw_clamp", x.data_ptr(), out.data_ptr(), T, H, W, C)
     return out
 
 
 # ---- frames out: uint8 frames from the decoder, baseline JPEG ----------------------------------------------------------
+def _u8_items(t, name: str, shape_ok: bool, shape: str):
+    """A uint8 device tensor [T, ...] of the stated shape -- frames [H, W, 3], planes [h, w], rows [n] -- with each item contiguous and
+    the items not overlapping (copied when they are not), and its item stride in bytes.  The stride of a single item is its size:
+    torch leaves the stride of a dimension of one undefined."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a device tensor (longlive_amd has no CPU path)")
+    if t.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: expected uint8, got {t.dtype}")
+    assert shape_ok, f"{name}: {tuple(t.shape)} is not {shape}"
+    T, n = t.shape[0], math.prod(t.shape[1:])
+    if t.stride()[1:] != _item_strides(t) or (T > 1 and t.stride(0) < n):
+        t = t.contiguous()
+    return t, (t.stride(0) if T > 1 else n)
+
+
+def _item_strides(t) -> tuple:
+    strides, n = [], 1
+    for d in reversed(t.shape[1:]):
+        strides.append(n)
+        n *= d
+    return tuple(reversed(strides))
+
+
 def _frames_u8(frames, what: str):
     """uint8 [T, H, W, 3] on the device with contiguous frames (copied when they are not) and its frame stride in bytes."""
-    if not frames.is_cuda:
-        raise RuntimeError(f"{what}: expected a device tensor (longlive_amd has no CPU path)")
-    if frames.dtype != torch.uint8:
-        raise RuntimeError(f"{what}: expected uint8, got {frames.dtype}")
-    assert frames.dim() == 4 and frames.shape[3] == 3, f"{what}: {tuple(frames.shape)} is not [T, H, W, 3]"
-    T, H, W, _ = frames.shape
-    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W or (T > 1 and frames.stride(0) < 3 * H * W):
-        frames = frames.contiguous()
-    return frames, (frames.stride(0) if T > 1 else 3 * H * W)
+    return _u8_items(frames, what, frames.dim() == 4 and frames.shape[3] == 3, "[T, H, W, 3]")
+
+
+def _u8_out(out, shape: tuple, device, what: str):
+    """`out` (new when None): a uint8 device tensor of `shape` = [T, ...] whose items -- frames [H, W, 3], I420 frames [n] -- are
+    contiguous and do not overlap, at any stride; and that stride in bytes."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=device)
+    if not out.is_cuda or out.dtype != torch.uint8:
+        raise RuntimeError("out: expected a uint8 device tensor")
+    assert out.shape == shape and out.stride()[1:] == _item_strides(out), f"out: {tuple(out.shape)} strides {out.stride()} is not {what} with contiguous frames"
+    n = math.prod(shape[1:])
+    stride = out.stride(0) if shape[0] > 1 else n
+    assert stride >= n
+    return out, stride
+
+
+def _frames_out(out, T: int, H: int, W: int, device):
+    return _u8_out(out, (T, H, W, 3), device, "[T, H, W, 3]")
 
 
 def cl_to_frames_u8(x, out=None):
@@ -729,24 +752,27 @@ def cl_to_frames_u8(x, out=None):
     frame by frame, bit for bit, in one pass.  `out`: a uint8 [T,H,W,3] view whose frames are contiguous (any frame stride)."""
     _chk(x, "x")
     T, H, W, C = x.shape
-    if out is None:
-        out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=x.device)
-    if not out.is_cuda or out.dtype != torch.uint8:
-        raise RuntimeError("out: expected a uint8 device tensor")
-    assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
-        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
-    stride_t = out.stride(0) if T > 1 else 3 * H * W
-    assert stride_t >= 3 * H * W
-    _lib.check(_lib.load().ll_cl_to_frames_u8(x.data_ptr(), out.data_ptr(), stride_t, T, H, W, C, _stream()), "ll_cl_to_frames_u8")
+    out, stride_t = _frames_out(out, T, H, W, x.device)
+    _call("ll_cl_to_frames_u8", x.data_ptr(), out.data_ptr(), stride_t, T, H, W, C)
     return out
+
+
+def _encode(entry: str, sizes, src, *head):
+    """The body of the three encoders: entry(src, *head, buf, out_stride, sizes, scratch, scratch_bytes) for T = src.shape[0] items,
+    with `sizes` = (out_stride, scratch_bytes) as the encoder's *_sizes entry gives them.  Returns (buf uint8 [T, out_stride], sizes
+    int32 [T])."""
+    out_stride, scratch_bytes = sizes
+    T = src.shape[0]
+    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=src.device)
+    used = torch.empty(T, dtype=torch.int32, device=src.device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=src.device)
+    _call(entry, src.data_ptr(), *head, buf.data_ptr(), out_stride, used.data_ptr(), scratch.data_ptr(), scratch_bytes)
+    return buf, used
 
 
 def jpeg_sizes(T: int, H: int, W: int):
     """(out_stride, scratch_bytes) of ll_jpeg_encode_u8 for T frames of H x W (host only)."""
-    import ctypes
-    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    _lib.check(_lib.load().ll_jpeg_sizes(T, H, W, ctypes.byref(a), ctypes.byref(b)), "ll_jpeg_sizes")
-    return int(a.value), int(b.value)
+    return _sizes("ll_jpeg_sizes", T, H, W)
 
 
 def jpeg_encode(frames, quality: int = 90):
@@ -754,13 +780,7 @@ def jpeg_encode(frames, quality: int = 90):
     baseline JPEG file (4:2:0, one restart interval per MCU row) is buf[t, :sizes[t]].  Stream-ordered: nothing is read back."""
     frames, stride_t = _frames_u8(frames, "frames")
     T, H, W, _ = frames.shape
-    out_stride, scratch_bytes = jpeg_sizes(T, H, W)
-    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=frames.device)
-    sizes = torch.empty(T, dtype=torch.int32, device=frames.device)
-    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=frames.device)
-    _lib.check(_lib.load().ll_jpeg_encode_u8(frames.data_ptr(), stride_t, T, H, W, int(quality), buf.data_ptr(), out_stride,
-                                             sizes.data_ptr(), scratch.data_ptr(), scratch_bytes, _stream()), "ll_jpeg_encode_u8")
-    return buf, sizes
+    return _encode("ll_jpeg_encode_u8", jpeg_sizes(T, H, W), frames, stride_t, T, H, W, int(quality))
 
 
 def jpeg_bytes(buf, sizes) -> list:
@@ -778,18 +798,14 @@ def jpeg_coefficients(frames, quality: int = 90):
     frames, stride_t = _frames_u8(frames, "frames")
     T, H, W, _ = frames.shape
     coef = torch.empty(T, (H + 15) // 16, (W + 15) // 16, 6, 64, dtype=torch.int16, device=frames.device)
-    _lib.check(_lib.load().ll_jpeg_coefficients_u8(frames.data_ptr(), stride_t, T, H, W, int(quality), coef.data_ptr(), _stream()),
-               "ll_jpeg_coefficients_u8")
+    _call("ll_jpeg_coefficients_u8", frames.data_ptr(), stride_t, T, H, W, int(quality), coef.data_ptr())
     return coef
 
 
 # ---- lossless frames out: PNG files and the zlib compressor inside them ("Lossless frames: PNG") ----
 def png_sizes(T: int, H: int, W: int):
     """(out_stride, scratch_bytes) of ll_png_encode_u8 for T frames of H x W (host only)."""
-    import ctypes
-    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    _lib.check(_lib.load().ll_png_sizes(T, H, W, ctypes.byref(a), ctypes.byref(b)), "ll_png_sizes")
-    return int(a.value), int(b.value)
+    return _sizes("ll_png_sizes", T, H, W)
 
 
 def png_encode(frames):
@@ -797,13 +813,7 @@ def png_encode(frames):
     file (8-bit RGB, lossless) is buf[t, :sizes[t]].  Stream-ordered: nothing is read back."""
     frames, stride_t = _frames_u8(frames, "frames")
     T, H, W, _ = frames.shape
-    out_stride, scratch_bytes = png_sizes(T, H, W)
-    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=frames.device)
-    sizes = torch.empty(T, dtype=torch.int32, device=frames.device)
-    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=frames.device)
-    _lib.check(_lib.load().ll_png_encode_u8(frames.data_ptr(), stride_t, T, H, W, buf.data_ptr(), out_stride, sizes.data_ptr(),
-                                            scratch.data_ptr(), scratch_bytes, _stream()), "ll_png_encode_u8")
-    return buf, sizes
+    return _encode("ll_png_encode_u8", png_sizes(T, H, W), frames, stride_t, T, H, W)
 
 
 png_bytes = jpeg_bytes      # the files of png_encode on the host: the same one read
@@ -814,36 +824,21 @@ def png_filter(frames):
     frames, stride_t = _frames_u8(frames, "frames")
     T, H, W, _ = frames.shape
     out = torch.empty(T, H, 1 + 3 * W, dtype=torch.uint8, device=frames.device)
-    _lib.check(_lib.load().ll_png_filter_u8(frames.data_ptr(), stride_t, T, H, W, out.data_ptr(), _stream()), "ll_png_filter_u8")
+    _call("ll_png_filter_u8", frames.data_ptr(), stride_t, T, H, W, out.data_ptr())
     return out
 
 
 def zlib_sizes(T: int, n: int):
     """(out_stride, scratch_bytes) of ll_zlib_compress_u8 for T rows of n bytes (host only)."""
-    import ctypes
-    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    _lib.check(_lib.load().ll_zlib_sizes(T, n, ctypes.byref(a), ctypes.byref(b)), "ll_zlib_sizes")
-    return int(a.value), int(b.value)
+    return _sizes("ll_zlib_sizes", T, n)
 
 
 def zlib_compress(rows):
     """uint8 rows [T, n] (unit stride along n, any row stride) -> (buf uint8 [T, out_stride], sizes int32 [T]): row t's zlib stream
     (the PNG encoder's deterministic DEFLATE, which zlib.decompress reads) is buf[t, :sizes[t]].  Stream-ordered."""
-    if not rows.is_cuda:
-        raise RuntimeError("rows: expected a device tensor (longlive_amd has no CPU path)")
-    if rows.dtype != torch.uint8:
-        raise RuntimeError(f"rows: expected uint8, got {rows.dtype}")
-    assert rows.dim() == 2, f"rows: {tuple(rows.shape)} is not [T, n]"
+    rows, stride = _u8_items(rows, "rows", rows.dim() == 2, "[T, n]")
     T, n = rows.shape
-    if rows.stride(1) != 1 or (T > 1 and rows.stride(0) < n):
-        rows = rows.contiguous()
-    out_stride, scratch_bytes = zlib_sizes(T, n)
-    buf = torch.empty(T, out_stride, dtype=torch.uint8, device=rows.device)
-    sizes = torch.empty(T, dtype=torch.int32, device=rows.device)
-    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=rows.device)
-    _lib.check(_lib.load().ll_zlib_compress_u8(rows.data_ptr(), rows.stride(0) if T > 1 else n, T, n, buf.data_ptr(), out_stride,
-                                               sizes.data_ptr(), scratch.data_ptr(), scratch_bytes, _stream()), "ll_zlib_compress_u8")
-    return buf, sizes
+    return _encode("ll_zlib_compress_u8", zlib_sizes(T, n), rows, stride, T, n)
 
 
 # ---- planar YUV: I420 frames out, planes of six layouts in (DESIGN.md section 5c, "Planar YUV and Y4M") -----------------
@@ -873,14 +868,7 @@ def yuv_chroma_shape(layout: str, H: int, W: int):
 
 def _yuv420_out(out, T: int, H: int, W: int, device):
     n = yuv420_bytes(H, W)
-    if out is None:
-        out = torch.empty(T, n, dtype=torch.uint8, device=device)
-    if not out.is_cuda or out.dtype != torch.uint8:
-        raise RuntimeError("out: expected a uint8 device tensor")
-    assert out.shape == (T, n) and out.stride(1) == 1, f"out: {tuple(out.shape)} strides {out.stride()} is not [T, {n}] with contiguous frames"
-    stride = out.stride(0) if T > 1 else n
-    assert stride >= n
-    return out, stride
+    return _u8_out(out, (T, n), device, f"[T, {n}]")
 
 
 def frames_u8_to_yuv420(frames, range: str = "limited", out=None):
@@ -890,8 +878,7 @@ def frames_u8_to_yuv420(frames, range: str = "limited", out=None):
     frames, stride_t = _frames_u8(frames, "frames")
     T, H, W, _ = frames.shape
     out, ost = _yuv420_out(out, T, H, W, frames.device)
-    _lib.check(_lib.load().ll_frames_u8_to_yuv420(frames.data_ptr(), stride_t, T, H, W, full, out.data_ptr(), ost, _stream()),
-               "ll_frames_u8_to_yuv420")
+    _call("ll_frames_u8_to_yuv420", frames.data_ptr(), stride_t, T, H, W, full, out.data_ptr(), ost)
     return out
 
 
@@ -902,7 +889,7 @@ def cl_to_yuv420(x, range: str = "limited", out=None):
     _chk(x, "x")
     T, H, W, C = x.shape
     out, ost = _yuv420_out(out, T, H, W, x.device)
-    _lib.check(_lib.load().ll_cl_to_yuv420(x.data_ptr(), T, H, W, C, full, out.data_ptr(), ost, _stream()), "ll_cl_to_yuv420")
+    _call("ll_cl_to_yuv420", x.data_ptr(), T, H, W, C, full, out.data_ptr(), ost)
     return out
 
 
@@ -916,14 +903,7 @@ def yuv420_planes(buf, H: int, W: int):
 
 def _yuv_plane(p, name: str, T: int, h: int, w: int):
     """A [T, h, w] uint8 device plane stack with contiguous planes (copied when they are not) and its plane stride in bytes."""
-    if not p.is_cuda:
-        raise RuntimeError(f"{name}: expected a device tensor (longlive_amd has no CPU path)")
-    if p.dtype != torch.uint8:
-        raise RuntimeError(f"{name}: expected uint8, got {p.dtype}")
-    assert tuple(p.shape) == (T, h, w), f"{name}: {tuple(p.shape)} is not [{T}, {h}, {w}]"
-    if p.stride(2) != 1 or p.stride(1) != w or (T > 1 and p.stride(0) < h * w):
-        p = p.contiguous()
-    return p, (p.stride(0) if T > 1 else h * w)
+    return _u8_items(p, name, tuple(p.shape) == (T, h, w), f"[{T}, {h}, {w}]")
 
 
 def yuv_to_frames_u8(y, cb=None, cr=None, layout: str = "420jpeg", range: str = "limited", out=None):
@@ -947,16 +927,8 @@ def yuv_to_frames_u8(y, cb=None, cr=None, layout: str = "420jpeg", range: str = 
         if stc_r != stc:
             cb, cr = cb.contiguous(), cr.contiguous()
             stc = hc * wc
-    if out is None:
-        out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=y.device)
-    if not out.is_cuda or out.dtype != torch.uint8:
-        raise RuntimeError("out: expected a uint8 device tensor")
-    assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
-        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
-    ost = out.stride(0) if T > 1 else 3 * H * W
-    assert ost >= 3 * H * W
-    _lib.check(_lib.load().ll_yuv_to_frames_u8(y.data_ptr(), _ptr(cb), _ptr(cr), sty, stc, T, H, W, YUV_LAYOUTS.index(layout), full,
-                                               out.data_ptr(), ost, _stream()), "ll_yuv_to_frames_u8")
+    out, ost = _frames_out(out, T, H, W, y.device)
+    _call("ll_yuv_to_frames_u8", y.data_ptr(), _ptr(cb), _ptr(cr), sty, stc, T, H, W, YUV_LAYOUTS.index(layout), full, out.data_ptr(), ost)
     return out
 
 
@@ -974,15 +946,11 @@ JPEG_SPLIT_ROUNDS = 12
 def jpeg_decode_sizes(T: int, H: int, W: int, components: int, hs: int, vs: int, split=None, rounds=None):
     """(coef_bytes, scratch_bytes) of ll_jpeg_decode_u8 (host only); with split=(segments, subsequences), the shape of the split table,
     also the work bytes of ll_jpeg_decode_u8_split: (coef_bytes, scratch_bytes, work_bytes).  `rounds` is checked, it changes no size."""
-    import ctypes
-    a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)
-    _lib.check(_lib.load().ll_jpeg_decode_sizes(T, H, W, components, hs, vs, ctypes.byref(a), ctypes.byref(b)), "ll_jpeg_decode_sizes")
+    sizes = _sizes("ll_jpeg_decode_sizes", T, H, W, components, hs, vs)
     if split is None:
-        return int(a.value), int(b.value)
+        return sizes
     _jpeg_rounds(rounds)
-    c = ctypes.c_longlong(0)
-    _lib.check(_lib.load().ll_jpeg_decode_split_sizes(int(split[0]), int(split[1]), ctypes.byref(c)), "ll_jpeg_decode_split_sizes")
-    return int(a.value), int(b.value), int(c.value)
+    return sizes + _sizes("ll_jpeg_decode_split_sizes", int(split[0]), int(split[1]), n=1)
 
 
 def _jpeg_rounds(rounds) -> int:
@@ -1082,6 +1050,27 @@ def _jpeg_checked(status, info, pk):
         _jpeg_status(status, pk)
 
 
+def _jpeg_launch(entry: str, head, mid, pk, d, device, sub, rounds, check: bool, return_info: bool, info, work, refusal: str):
+    """entry(*head, status, *mid) on the serial route (sub None, or no segment long enough to cut), entry_split(.., *tail) on the split
+    route; the status read back once under `check`.  Returns info (None on the serial route)."""
+    if sub is None:
+        if return_info or info is not None or work is not None:
+            raise ValueError(refusal)
+        status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=device)
+        _call(entry, *head, status.data_ptr(), *mid)
+        if check:
+            _jpeg_status(status, pk)
+        return None
+    status, info, tail = _jpeg_split_args(pk, d, device, _jpeg_rounds(rounds), info, work)
+    if tail is None:
+        _call(entry, *head, status.data_ptr(), *mid)
+    else:
+        _call(entry + "_split", *head, status.data_ptr(), *mid, *tail)
+    if check:
+        _jpeg_checked(status, info, pk)
+    return info
+
+
 def jpeg_decode_coefficients(files, device=None, out=None, check: bool = True, split=None, rounds=None, return_info: bool = False,
                              info=None, work=None):
     """Baseline JPEG files (bytes, same size and sampling) -> int16 [T, rows, cols, bpm, 64] on the device: the entropy stage alone, in
@@ -1092,22 +1081,8 @@ def jpeg_decode_coefficients(files, device=None, out=None, check: bool = True, s
     coef = _jpeg_coef_out(pk, d["data"].device, out)
     head = (d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0], d["huff"].data_ptr(), d["sel"].data_ptr(),
             pk.frames, pk.height, pk.width, pk.components, pk.hs, pk.vs, coef.data_ptr())
-    if sub is None:
-        if return_info or info is not None or work is not None:
-            raise ValueError("return_info, info and work belong to the split route: pass split=")
-        status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=coef.device)
-        _lib.check(_lib.load().ll_jpeg_decode_coefficients(*head, status.data_ptr(), _stream()), "ll_jpeg_decode_coefficients")
-        if check:
-            _jpeg_status(status, pk)
-        return coef
-    status, info, tail = _jpeg_split_args(pk, d, coef.device, _jpeg_rounds(rounds), info, work)
-    if tail is None:
-        _lib.check(_lib.load().ll_jpeg_decode_coefficients(*head, status.data_ptr(), _stream()), "ll_jpeg_decode_coefficients")
-    else:
-        _lib.check(_lib.load().ll_jpeg_decode_coefficients_split(*head, status.data_ptr(), *tail, _stream()),
-                   "ll_jpeg_decode_coefficients_split")
-    if check:
-        _jpeg_checked(status, info, pk)
+    info = _jpeg_launch("ll_jpeg_decode_coefficients", head, (), pk, d, coef.device, sub, rounds, check, return_info, info, work,
+                        "return_info, info and work belong to the split route: pass split=")
     return (coef, info) if return_info else coef
 
 
@@ -1134,31 +1109,12 @@ def jpeg_decode(files, device=None, check: bool = True, out=None, scratch=None, 
     if planes is None:
         planes = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
     assert planes.is_cuda and planes.dtype == torch.uint8 and planes.numel() >= scratch_bytes and planes.is_contiguous()
-    if out is None:
-        out = torch.empty(T, H, W, 3, dtype=torch.uint8, device=device)
-    if not out.is_cuda or out.dtype != torch.uint8:
-        raise RuntimeError("out: expected a uint8 device tensor")
-    assert out.shape == (T, H, W, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * W, \
-        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
-    stride_t = out.stride(0) if T > 1 else 3 * H * W
+    out, stride_t = _frames_out(out, T, H, W, device)
     head = (d["data"].data_ptr(), pk.data.nbytes, d["segs"].data_ptr(), pk.segs.shape[0], d["huff"].data_ptr(), d["sel"].data_ptr(),
             d["qt"].data_ptr(), T, H, W, pk.components, pk.hs, pk.vs, coef.data_ptr())
     mid = (out.data_ptr(), stride_t, planes.data_ptr(), planes.numel())
-    if sub is None:
-        if return_info or info is not None or work is not None:
-            raise ValueError("return_info, info and a work buffer belong to the split route: pass split=")
-        status = torch.empty(pk.segs.shape[0], dtype=torch.int32, device=device)
-        _lib.check(_lib.load().ll_jpeg_decode_u8(*head, status.data_ptr(), *mid, _stream()), "ll_jpeg_decode_u8")
-        if check:
-            _jpeg_status(status, pk)
-        return out
-    status, info, tail = _jpeg_split_args(pk, d, device, _jpeg_rounds(rounds), info, work)
-    if tail is None:
-        _lib.check(_lib.load().ll_jpeg_decode_u8(*head, status.data_ptr(), *mid, _stream()), "ll_jpeg_decode_u8")
-    else:
-        _lib.check(_lib.load().ll_jpeg_decode_u8_split(*head, status.data_ptr(), *mid, *tail, _stream()), "ll_jpeg_decode_u8_split")
-    if check:
-        _jpeg_checked(status, info, pk)
+    info = _jpeg_launch("ll_jpeg_decode_u8", head, mid, pk, d, device, sub, rounds, check, return_info, info, work,
+                        "return_info, info and a work buffer belong to the split route: pass split=")
     return (out, info) if return_info else out
 
 
@@ -1209,18 +1165,12 @@ def resize_u8(frames, size, fit: str = "cover", out=None):
     Hd, Wd = int(size[0]), int(size[1])
     assert T >= 1 and Hd >= 1 and Wd >= 1
     y0, x0, Hc, Wc = cover_window(Hs, Ws, Hd, Wd) if fit == "cover" else (0, 0, Hs, Ws)
-    if out is None:
-        out = torch.empty(T, Hd, Wd, 3, dtype=torch.uint8, device=frames.device)
-    if not out.is_cuda or out.dtype != torch.uint8:
-        raise RuntimeError("out: expected a uint8 device tensor")
-    assert out.shape == (T, Hd, Wd, 3) and out.stride(3) == 1 and out.stride(2) == 3 and out.stride(1) == 3 * Wd, \
-        f"out: {tuple(out.shape)} strides {out.stride()} is not [T, H, W, 3] with contiguous frames"
+    out, ost = _frames_out(out, T, Hd, Wd, frames.device)
     idx = _dev_index(frames.device)
     ys, yn, yw = _resize_tables(Hc, Hd, idx)
     xs, xn, xw = _resize_tables(Wc, Wd, idx)
-    _lib.check(_lib.load().ll_resize_u8(frames.data_ptr(), stride_t, Hs, Ws, y0, x0, Hc, Wc, out.data_ptr(),
-                                        out.stride(0) if T > 1 else 3 * Hd * Wd, Hd, Wd, T, ys.data_ptr(), yn.data_ptr(), yw.data_ptr(),
-                                        yw.shape[1], xs.data_ptr(), xn.data_ptr(), xw.data_ptr(), xw.shape[1], _stream()), "ll_resize_u8")
+    _call("ll_resize_u8", frames.data_ptr(), stride_t, Hs, Ws, y0, x0, Hc, Wc, out.data_ptr(), ost, Hd, Wd, T, ys.data_ptr(), yn.data_ptr(),
+          yw.data_ptr(), yw.shape[1], xs.data_ptr(), xn.data_ptr(), xw.data_ptr(), xw.shape[1])
     return out
 
 
@@ -1228,25 +1178,16 @@ def resize_u8(frames, size, fit: str = "cover", out=None):
 def _conv_down(kind: int, x, packed, bias, geo, out):
     cin, cout, kpad, kt, kh = geo
     name = "conv_cl_tdown" if kind else "conv_cl_down"
-    _chk(x, "x"); _chk(packed, "w"); _chk(bias, "bias")
     assert (kt, kh) == ((3, 1) if kind else (1, 3)), f"{name}: weights are {kt}x{kh}x{kh}"
     hist = 1 if kind else 0
-    T, H, W, C = x.shape[0] - hist, x.shape[1], x.shape[2], x.shape[3]
-    assert T >= 1, f"{name}: takes [1 + T, H, W, Cin] (the stream's previous frame first)"
-    assert C == cin, f"{name}: input has {C} channels, weights expect {cin}"
-    assert packed.shape == (cout, kpad) and bias.numel() == cout
+    T, H, W = _conv_in(x, packed, bias, geo, hist, name, "takes [1 + T, H, W, Cin] (the stream's previous frame first)")
     To, Ho, Wo = (T // 2, H, W) if kind else (T, H // 2, W // 2)
     if out is None:
         out = torch.empty(To, Ho, Wo, cout, dtype=bf16, device=x.device)
     _chk(out, "out")
     assert out.shape[:3] == (To, Ho, Wo) and out.shape[3] >= cout, f"{name}: out {tuple(out.shape)} for {(To, Ho, Wo, cout)}"
-    lib = _lib.load()
-    fn = lib.ll_conv_cl_tdown if kind else lib.ll_conv_cl_down
-    t0 = timer.begin(name) if timer is not None else None
-    _lib.check(fn(x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(), out.data_ptr(), T, H, W, cin,
-                  cout, kpad, out.shape[3], _stream()), "ll_" + name)
-    if timer is not None:
-        timer.end(name, t0, 2.0 * To * Ho * Wo * cout * (kt * kh * kh * cin))
+    _call("ll_" + name, x[hist:].data_ptr(), zero_row(x.device).data_ptr(), packed.data_ptr(), bias.data_ptr(), out.data_ptr(), T, H, W, cin,
+          cout, kpad, out.shape[3], tag=name, work=2.0 * To * Ho * Wo * cout * (kt * kh * kh * cin))
     return out
 
 
@@ -1264,20 +1205,21 @@ def conv_cl_tdown(x, packed, bias, geo, out=None):
 
 def conv_down_plan(kind: int, T: int, H: int, W: int, cin: int, cout: int) -> str:
     """Kernel instance, tile, grid and k-steps conv_cl_down (kind 0) / conv_cl_tdown (kind 1) launch for this shape (host only)."""
-    import ctypes
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_conv_down_plan(kind, T, H, W, cin, cout, buf, 256), "ll_conv_down_plan")
-    return buf.value.decode()
+    return _plan("ll_conv_down_plan", kind, T, H, W, cin, cout)
 
 
 def conv_plan(T: int, H: int, W: int, geo, upsample: bool = False, res: bool = False, rms: bool = False) -> str:
     """ll_conv_plan's text for a pack_conv_weight geometry."""
-    import ctypes
     cin, cout, kpad, kt, kh = geo
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_conv_plan(T, H, W, cin, cout, kt, kh, 1 if upsample else 0, 1 if res else 0, 1 if rms else 0, buf, 256),
-               "ll_conv_plan")
-    return buf.value.decode()
+    return _plan("ll_conv_plan", T, H, W, cin, cout, kt, kh, 1 if upsample else 0, 1 if res else 0, 1 if rms else 0)
+
+
+def _cl_out(out, T: int, H: int, W: int, cpad: int, device):
+    if out is None:
+        out = torch.empty(T, H, W, cpad, dtype=bf16, device=device)
+    _chk(out, "out")
+    assert out.shape == (T, H, W, cpad)
+    return out
 
 
 def pixels_to_cl(px, channel_dim: int, cpad: int = 8, out=None):
@@ -1291,34 +1233,19 @@ def pixels_to_cl(px, channel_dim: int, cpad: int = 8, out=None):
     T, H, W = px.shape[1 - channel_dim], px.shape[2], px.shape[3]
     if px.stride(3) != 1 or px.stride(2) != W:
         px = px.contiguous()
-    if out is None:
-        out = torch.empty(T, H, W, cpad, dtype=bf16, device=px.device)
-    _chk(out, "out")
-    assert out.shape == (T, H, W, cpad)
-    lib = _lib.load()
-    _lib.check(lib.ll_pixels_to_cl(px.data_ptr(), 1 if px.dtype == torch.float32 else 0, px.stride(channel_dim), px.stride(1 - channel_dim),
-                                   out.data_ptr(), T, H, W, cpad, _stream()), "ll_pixels_to_cl")
+    out = _cl_out(out, T, H, W, cpad, px.device)
+    _call("ll_pixels_to_cl", px.data_ptr(), 1 if px.dtype == torch.float32 else 0, px.stride(channel_dim), px.stride(1 - channel_dim),
+          out.data_ptr(), T, H, W, cpad)
     return out
 
 
 def pixels_u8_to_cl(frames, cpad: int = 8, out=None):
     """Video frames uint8 [T, H, W, 3] (any view whose frames are contiguous) -> channels-last bf16 [T, H, W, cpad], channels >= 3
     zero, values `(u.float() / 127.5 - 1).to(bfloat16)` bit for bit."""
-    if not frames.is_cuda:
-        raise RuntimeError("frames: expected a device tensor (longlive_amd has no CPU path)")
-    if frames.dtype != torch.uint8:
-        raise RuntimeError(f"frames: expected uint8, got {frames.dtype}")
-    assert frames.dim() == 4 and frames.shape[3] == 3, f"frames: {tuple(frames.shape)} is not [T, H, W, 3]"
+    frames, stride_t = _frames_u8(frames, "frames")          # uint8: elements are bytes
     T, H, W, _ = frames.shape
-    if frames.stride(3) != 1 or frames.stride(2) != 3 or frames.stride(1) != 3 * W or (T > 1 and frames.stride(0) < 3 * H * W):
-        frames = frames.contiguous()
-    if out is None:
-        out = torch.empty(T, H, W, cpad, dtype=bf16, device=frames.device)
-    _chk(out, "out")
-    assert out.shape == (T, H, W, cpad)
-    lib = _lib.load()
-    stride_t = frames.stride(0) if T > 1 else 3 * H * W          # uint8: elements are bytes
-    _lib.check(lib.ll_pixels_u8_to_cl(frames.data_ptr(), stride_t, out.data_ptr(), T, H, W, cpad, _stream()), "ll_pixels_u8_to_cl")
+    out = _cl_out(out, T, H, W, cpad, frames.device)
+    _call("ll_pixels_u8_to_cl", frames.data_ptr(), stride_t, out.data_ptr(), T, H, W, cpad)
     return out
 
 
@@ -1329,9 +1256,7 @@ def vae_scale_tchw(mu, mean, inv_std):
     z = mean.numel()
     assert inv_std.numel() == z and ld >= z
     out = torch.empty(T, z, h, w, dtype=torch.float32, device=mu.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_vae_scale_tchw(mu.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), out.data_ptr(), T, z, h, w, ld, _stream()),
-               "ll_vae_scale_tchw")
+    _call("ll_vae_scale_tchw", mu.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), out.data_ptr(), T, z, h, w, ld)
     return out
 
 
@@ -1341,29 +1266,20 @@ def t5_rmsnorm(x, w, eps: float = 1e-6):
     C = x.shape[-1]
     assert w.numel() == C
     out = torch.empty_like(x)
-    lib = _lib.load()
-    _lib.check(lib.ll_t5_rmsnorm(x.data_ptr(), w.data_ptr(), out.data_ptr(), x.numel() // C, C, float(eps), _stream()),
-               "ll_t5_rmsnorm")
+    _call("ll_t5_rmsnorm", x.data_ptr(), w.data_ptr(), out.data_ptr(), x.numel() // C, C, float(eps))
     return out
 
 
 def gemm_res_t5norm(x, w, bias, res, norm_w, eps: float = 1e-6, tag: str = "gemm"):
     """(x_new, h) = (res + (x @ w^T + bias), T5LayerNorm(x_new; norm_w)): umT5's `x = x + linear(.)` and the norm that follows it
     (t5.py:119-160) -- on the small-M path one pass over the rows does the K-range sum, bias, residual and norm."""
-    _chk(x, "x"); _chk(w, "w"); _chk(bias, "bias"); _chk(res, "res"); _chk(norm_w, "norm_w")
-    K = x.shape[-1]
-    M = x.numel() // K
-    N = w.shape[0]
-    assert w.shape == (N, K) and bias.numel() == N and res.numel() == M * N and norm_w.numel() == N
-    out = torch.empty(*x.shape[:-1], N, dtype=bf16, device=x.device)
+    M, N, K, out = _linear(x, w, bias)
+    _chk(res, "res"); _chk(norm_w, "norm_w")
+    assert res.numel() == M * N and norm_w.numel() == N
     h = torch.empty_like(out)
-    lib = _lib.load()
-    ws = ksplit_workspace(x.device, M, N, K) if _ksplit_plan(lib, M, N, K) else None
-    t0 = _t0(tag)
-    _lib.check(lib.ll_gemm_bf16_ksplit_t5norm(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, K, N, res.data_ptr(),
-                                              norm_w.data_ptr(), float(eps), h.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0,
-                                              _stream()), "ll_gemm_bf16_ksplit_t5norm")
-    _t1(tag, t0, 2.0 * M * N * K)
+    ws = ksplit_workspace(x.device, M, N, K) if _ksplit_plan(M, N, K) else None
+    _call("ll_gemm_bf16_ksplit_t5norm", x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, K, N, res.data_ptr(),
+          norm_w.data_ptr(), float(eps), h.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, tag=tag, work=2.0 * M * N * K)
     return out, h
 
 
@@ -1373,8 +1289,7 @@ def t5_gated_gelu(h):
     M, F2 = h.numel() // h.shape[-1], h.shape[-1]
     assert F2 % 16 == 0
     out = torch.empty(*h.shape[:-1], F2 // 2, dtype=bf16, device=h.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_t5_gated_gelu(h.data_ptr(), out.data_ptr(), M, F2 // 2, _stream()), "ll_t5_gated_gelu")
+    _call("ll_t5_gated_gelu", h.data_ptr(), out.data_ptr(), M, F2 // 2)
     return out
 
 
@@ -1383,9 +1298,7 @@ def gather_rows(table, ids):
     _chk(table, "table"); _chk(ids, "ids", torch.int64)
     V, C = table.shape
     out = torch.empty(ids.numel(), C, dtype=bf16, device=table.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_gather_rows(table.data_ptr(), ids.data_ptr(), out.data_ptr(), ids.numel(), C, V, _stream()),
-               "ll_gather_rows")
+    _call("ll_gather_rows", table.data_ptr(), ids.data_ptr(), out.data_ptr(), ids.numel(), C, V)
     return out
 
 
@@ -1397,9 +1310,8 @@ def t5_attention(qk, vt, bias_tab, num_heads: int, seq_len: int):
     assert two_c == 2 * C and vt.shape == (C, L) and bias_tab.shape == (num_heads, 2 * L - 1)
     assert 1 <= seq_len <= L
     out = torch.empty(L, C, dtype=bf16, device=qk.device)
-    lib = _lib.load()
-    _lib.check(lib.ll_t5_attention(qk.data_ptr(), qk[:, C:].data_ptr(), vt.data_ptr(), bias_tab.data_ptr(), out.data_ptr(),
-                                   L, num_heads, two_c, C, int(seq_len), _stream()), "ll_t5_attention")
+    _call("ll_t5_attention", qk.data_ptr(), qk[:, C:].data_ptr(), vt.data_ptr(), bias_tab.data_ptr(), out.data_ptr(), L, num_heads, two_c, C,
+          int(seq_len))
     return out
 
 
@@ -1462,10 +1374,8 @@ def _quantize(fmt: QFormat, x, tag: Optional[str] = None):
     _chk(x, "x")
     K = x.shape[-1]
     q, s = fmt.empty(tuple(x.shape), x.device)
-    tag = tag or fmt.quantizer[3:]
-    t0 = _t0(tag)
-    _lib.check(getattr(_lib.load(), fmt.quantizer)(x.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // K, K, K, _stream()), fmt.quantizer)
-    _t1(tag, t0, fmt.quant_bytes * x.numel())
+    _call(fmt.quantizer, x.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // K, K, K,
+          tag=tag or fmt.quantizer[3:], work=fmt.quant_bytes * x.numel())
     return q, s
 
 
@@ -1478,17 +1388,7 @@ def _qgemm(entry: str, afmt: QFormat, wfmt: QFormat, xm, wm, bias, epilogue: int
     wq, sw, N, Kw = wfmt.pair(wm, "wq")
     _chk(bias, "bias")
     assert Kw == K and wq.dim() == 2 and bias.numel() == N, (wq.shape, K, bias.shape)
-    nmod = 0
-    if epilogue in (EPI_BIAS_GATE_RES, EPI_BIAS_RES):
-        _chk(res, "res")
-        assert res.numel() == M * N
-    if epilogue == EPI_BIAS_GATE_RES:
-        _chk(e, "e")
-        nmod = e.shape[-2]
-        assert e.shape[-1] == N and e.numel() == (M // frame_len) * nmod * N
-        if mod is not None:
-            _chk(mod, "mod")
-            assert mod.numel() == nmod * N
+    nmod = _epilogue(epilogue, M, N, res, e, mod, frame_len)
     if mx_out:
         assert afmt.block and epilogue == EPI_BIAS_GELU and out is None
         qo, so = afmt.empty((*xq.shape[:-1], N), xq.device)
@@ -1499,11 +1399,8 @@ def _qgemm(entry: str, afmt: QFormat, wfmt: QFormat, xm, wm, bias, epilogue: int
         _chk(out, "out")
         assert out.numel() == M * N
     outs = (_ptr(out), _ptr(qo), _ptr(so)) if afmt.block else (out.data_ptr(),)      # only the block-scaled entries can write codes
-    t0 = _t0(tag)
-    _lib.check(getattr(_lib.load(), entry)(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), *outs, M, N, K, N,
-                                           epilogue, _ptr(res), _ptr(e), _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, _stream()),
-               entry)
-    _t1(tag, t0, 2.0 * M * N * K)
+    _call(entry, xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), *outs, M, N, K, N, epilogue, _ptr(res), _ptr(e),
+          _ptr(mod), nmod, gate_idx, rows_per_batch, frame_len, tag=tag, work=2.0 * M * N * K)
     return (qo, so) if mx_out else out
 
 
@@ -1523,77 +1420,25 @@ def _qgemm_qkv(entry: str, afmt: QFormat, wfmt: QFormat, xm, wm, bias, cache_v, 
     wq, sw, N, Kw = wfmt.pair(wm, "wq")
     _chk(bias, "bias"); _chk(cache_v, "cache_v")
     assert Kw == K and M == B * L and bias.numel() == N and N % 3 == 0
-    S = cache_v.shape[1]
-    assert cache_v.shape[0] == B and cache_v.numel() == B * S * (N // 3), (cache_v.shape, B, S, N)
+    S = _v_cache(cache_v, B, N)
     out = torch.empty(B, L, N, dtype=bf16, device=xq.device)
-    t0 = _t0(tag)
-    _lib.check(getattr(_lib.load(), entry)(xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                           M, N, K, N, cache_v.data_ptr(), B, L, S, write_start, roped_offset, write_len, _stream()), entry)
-    _t1(tag, t0, 2.0 * M * N * K)
+    _call(entry, xq.data_ptr(), sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), bias.data_ptr(), out.data_ptr(), M, N, K, N, cache_v.data_ptr(),
+          B, L, S, write_start, roped_offset, write_len, tag=tag, work=2.0 * M * N * K)
     return out
-
-
-def _ln_modulate_q(fmt: QFormat, x, e, mod, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate emitting the fmt codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(e, "e")
-    B, L, Cc = x.shape
-    nmod = e.shape[-2]
-    assert e.shape == (B, num_frames, nmod, Cc)
-    if mod is not None:
-        _chk(mod, "mod")
-        assert mod.numel() == nmod * Cc
-    q, s = fmt.empty((B, L, Cc), x.device)
-    entry = "ll_ln_modulate_" + fmt.name
-    t0 = _t0(tag)
-    _lib.check(getattr(_lib.load(), entry)(x.data_ptr(), q.data_ptr(), s.data_ptr(), e.data_ptr(), _ptr(mod), nmod, shift_idx, scale_idx,
-                                           B, L, Cc, num_frames, eps, _stream()), entry)
-    _t1(tag, t0, fmt.prod_bytes * x.numel())
-    return q, s
-
-
-def _ln_modulate_tab_q(fmt: QFormat, x, tab, shift_idx: int, scale_idx: int, num_frames: int, eps: float, tag: str = "ln_modulate"):
-    """ln_modulate_tab emitting the fmt codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(tab, "tab", torch.float32)
-    B, L, Cc = x.shape
-    nmod = tab.shape[2]
-    assert tab.shape == (B, num_frames, nmod, Cc), (tab.shape, (B, num_frames, nmod, Cc))
-    q, s = fmt.empty((B, L, Cc), x.device)
-    entry = "ll_ln_modulate_tab_" + fmt.name
-    t0 = _t0(tag)
-    _lib.check(getattr(_lib.load(), entry)(x.data_ptr(), q.data_ptr(), s.data_ptr(), tab.data_ptr(), nmod, shift_idx, scale_idx,
-                                           B, L, Cc, num_frames, eps, _stream()), entry)
-    _t1(tag, t0, fmt.prod_bytes * B * L * Cc)
-    return q, s
-
-
-def _layernorm_affine_q(fmt: QFormat, x, w, b, eps: float):
-    """layernorm_affine emitting the fmt codes + scales of its bf16 output."""
-    _chk(x, "x"); _chk(w, "w"); _chk(b, "b")
-    Cc = x.shape[-1]
-    assert w.numel() == Cc and b.numel() == Cc
-    q, s = fmt.empty(tuple(x.shape), x.device)
-    entry = "ll_layernorm_affine_" + fmt.name
-    t0 = _t0("layernorm_affine")
-    _lib.check(getattr(_lib.load(), entry)(x.data_ptr(), w.data_ptr(), b.data_ptr(), q.data_ptr(), s.data_ptr(), x.numel() // Cc, Cc,
-                                           eps, _stream()), entry)
-    _t1("layernorm_affine", t0, fmt.prod_bytes * x.numel())
-    return q, s
 
 
 def _gemm_plan(entry: str, M: int, N: int, K: int) -> str:
     """Kernel instance, tile and grid of the GEMM (and its QKV V-insert form) behind a ll_gemm_plan_* entry (host only)."""
-    import ctypes
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(getattr(_lib.load(), entry)(M, N, K, buf, 256), entry)
-    return buf.value.decode()
+    return _plan(entry, M, N, K)
 
 
 # The public names.  Per format: the quantiser and the three producers, each returning (codes, scales) equal bit for bit to the
-# quantiser applied to the bf16 form's output (int8: quantize_rows and ln_modulate_tab(q8=True) above share their C entry points with
-# the bf16 forms).  Per activation x weight pairing: the GEMM, its QKV V-insert form and its plan string.
+# quantiser applied to the bf16 form's output (int8: quantize_rows above, and ln_modulate_tab_q8 shares its C entry point with the
+# bf16 form).  Per activation x weight pairing: the GEMM, its QKV V-insert form and its plan string.
 quantize_rows_f8, quantize_mx, quantize_mx6, quantize_mx4 = (_bind(_quantize, f) for f in (F8, MX, MX6, MX4))
 ln_modulate_q8, ln_modulate_f8, ln_modulate_mx, ln_modulate_mx6, ln_modulate_mx4 = (_bind(_ln_modulate_q, f) for f in (Q8, F8, MX, MX6, MX4))
-ln_modulate_tab_f8, ln_modulate_tab_mx, ln_modulate_tab_mx6, ln_modulate_tab_mx4 = (_bind(_ln_modulate_tab_q, f) for f in (F8, MX, MX6, MX4))
+ln_modulate_tab_q8, ln_modulate_tab_f8, ln_modulate_tab_mx, ln_modulate_tab_mx6, ln_modulate_tab_mx4 = (
+    _bind(_ln_modulate_tab_q, f) for f in (Q8, F8, MX, MX6, MX4))
 layernorm_affine_q8, layernorm_affine_f8, layernorm_affine_mx, layernorm_affine_mx6, layernorm_affine_mx4 = (
     _bind(_layernorm_affine_q, f) for f in (Q8, F8, MX, MX6, MX4))
 
@@ -1603,6 +1448,7 @@ gemm_mx = _bind(_qgemm, "ll_gemm_mx", MX, MX)
 gemm_mx6 = _bind(_qgemm, "ll_gemm_mx6", MX6, MX6)
 gemm_mx4w6 = _bind(_qgemm, "ll_gemm_mx4w6", MX6, MX4)      # MXFP4 weights over MXFP6 activations
 gemm_mx4 = _bind(_qgemm, "ll_gemm_mx4", MX4, MX4)
+gemm_w8a8_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_w8a8_qkv", Q8, Q8)
 gemm_f8_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_f8_qkv", F8, F8)
 gemm_mx_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_mx_qkv", MX, MX)
 gemm_mx6_qkv_v_insert = _bind(_qgemm_qkv, "ll_gemm_mx6_qkv", MX6, MX6)
@@ -1628,6 +1474,10 @@ def kv_shadow_mx_alloc(cache_k) -> dict:
                 vs=torch.zeros(B, H, S32 // 32, D, dtype=u8, device=dev), S=S)
 
 
+def _shadow_ptrs(shadow: dict) -> tuple:
+    return _ptrs(shadow[k] for k in ("kq", "ks", "vq", "vs"))
+
+
 def kv_shadow_mx(cache_k, cache_v, shadow: dict, lo: int, hi: int, tag: str = "kv_shadow_mx"):
     """Re-derive the shadow of cache slots [lo, hi) (widened to whole 32-slot blocks) from the bf16 cache.  Replaces nothing in
     the reference: it follows the cache writes of causal_model.py:257-311 in MX attention mode."""
@@ -1635,23 +1485,9 @@ def kv_shadow_mx(cache_k, cache_v, shadow: dict, lo: int, hi: int, tag: str = "k
     B, S, H, D = cache_k.shape
     assert cache_v.shape == cache_k.shape and shadow["S"] == S and shadow["kq"].shape[:1] == (B,), (cache_k.shape, shadow["kq"].shape)
     S32 = shadow["kq"].shape[1]
-    lib = _lib.load()
-    t0 = _t0(tag)
-    _lib.check(lib.ll_kv_shadow_mx(cache_k.data_ptr(), cache_v.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(),
-                                   shadow["vq"].data_ptr(), shadow["vs"].data_ptr(), B, S, S32, H, D, int(lo), int(hi), _stream()),
-               "ll_kv_shadow_mx")
     n = ((int(hi) + 31) // 32 - int(lo) // 32) * 32
-    _t1(tag, t0, 2.0 * B * n * H * D * (2 + 1))         # bytes: k and v read (bf16), codes written
-
-
-def _segs2(segments, S):
-    segs = [(int(a), int(b)) for a, b in segments if b > a]
-    assert 1 <= len(segs) <= 2, segments
-    for a, b_ in segs:
-        assert 0 <= a < b_ <= S, (segments, S)
-    (s0, e0) = segs[0]
-    (s1, e1) = segs[1] if len(segs) == 2 else (0, 0)
-    return s0, e0, s1, e1
+    _call("ll_kv_shadow_mx", cache_k.data_ptr(), cache_v.data_ptr(), *_shadow_ptrs(shadow), B, S, S32, H, D, int(lo), int(hi),
+          tag=tag, work=2.0 * B * n * H * D * (2 + 1))         # bytes: k and v read (bf16), codes written
 
 
 def flash_attn_mx(q, shadow: dict, segments, out=None, scale: Optional[float] = None, tag: Optional[str] = None,
@@ -1659,41 +1495,28 @@ def flash_attn_mx(q, shadow: dict, segments, out=None, scale: Optional[float] = 
     """flash_attn over the MX shadow of the cache: q [B,Lq,H,128] bf16 (quantised per row in the kernel), keys = up to two slot
     ranges [(start, end), ...].  Returns [B,Lq,H,128] bf16, or with out_fmt (MX, MX6, MX4) the (codes, scales) of those rows: the
     bytes quantize_<fmt>(flash_attn_mx(...)) gives, from the kernel's epilogue (two launches for a packed format over an odd H)."""
-    _chk(q, "q")
-    B, Lq, H, D = q.shape
-    assert D == 128, "kernel is specialised for head_dim 128"
+    B, Lq, H, D = _attn_q(q)
     S, S32 = shadow["S"], shadow["kq"].shape[1]
     assert shadow["kq"].shape == (B, S32, H, D) and shadow["vq"].shape == (B, H, S32 // 32, D, 32), (q.shape, shadow["kq"].shape)
     s0, e0, s1, e1 = _segs2(segments, S)
-    if scale is None:
-        scale = 1.0 / math.sqrt(D)
-    lib = _lib.load()
+    scale = _attn_scale(scale, D)
     tag = tag or "flash_attn_mx"
+    work = _attn_flops(B, H, Lq, (e0 - s0) + (e1 - s1), D)
     if out_fmt is not None:
         if _qfmt_id(out_fmt) != 1 and H % 2:
             return _quantize(out_fmt, flash_attn_mx(q, shadow, segments, scale=scale, tag=tag).view(B, Lq, H * D))
         codes, scales = out_fmt.empty((B, Lq, H * D), q.device)
-        t0 = _t0(tag)
-        _lib.check(lib.ll_flash_attn_mx_q(_qfmt_id(out_fmt), q.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(),
-                                          shadow["vq"].data_ptr(), shadow["vs"].data_ptr(), codes.data_ptr(), scales.data_ptr(), B, Lq, H, D,
-                                          H * D, codes.shape[-1], scales.shape[-1], S, S32, s0, e0 - s0, s1, e1 - s1, scale, _stream()),
-                   "ll_flash_attn_mx_q")
-        _t1(tag, t0, 4.0 * B * H * Lq * ((e0 - s0) + (e1 - s1)) * D)
+        _call("ll_flash_attn_mx_q", _qfmt_id(out_fmt), q.data_ptr(), *_shadow_ptrs(shadow), codes.data_ptr(), scales.data_ptr(), B, Lq, H, D,
+              H * D, codes.shape[-1], scales.shape[-1], S, S32, s0, e0 - s0, s1, e1 - s1, scale, tag=tag, work=work)
         return codes, scales
     out = torch.empty_like(q) if out is None else _chk(out, "out")
     assert out.shape == q.shape
-    t0 = _t0(tag)
-    _lib.check(lib.ll_flash_attn_mx(q.data_ptr(), shadow["kq"].data_ptr(), shadow["ks"].data_ptr(), shadow["vq"].data_ptr(),
-                                    shadow["vs"].data_ptr(), out.data_ptr(), B, Lq, H, D, H * D, H * D, S, S32, s0, e0 - s0, s1, e1 - s1,
-                                    scale, _stream()), "ll_flash_attn_mx")
-    _t1(tag, t0, 4.0 * B * H * Lq * ((e0 - s0) + (e1 - s1)) * D)     # algorithmic FLOPs: QK^T + PV
+    _call("ll_flash_attn_mx", q.data_ptr(), *_shadow_ptrs(shadow), out.data_ptr(), B, Lq, H, D, H * D, H * D, S, S32, s0, e0 - s0, s1, e1 - s1,
+          scale, tag=tag, work=work)
     return out
 
 
 def flash_attn_mx_plan(Lq: int, H: int, B: int, segments) -> str:
     """Kernel, tile and grid of a flash_attn_mx call (host only)."""
-    import ctypes
     s0, e0, s1, e1 = _segs2(segments, 1 << 30)
-    buf = ctypes.create_string_buffer(256)
-    _lib.check(_lib.load().ll_flash_attn_mx_plan(Lq, H, B, s0, e0 - s0, s1, e1 - s1, buf, 256), "ll_flash_attn_mx_plan")
-    return buf.value.decode()
+    return _plan("ll_flash_attn_mx_plan", Lq, H, B, s0, e0 - s0, s1, e1 - s1)
