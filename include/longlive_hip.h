@@ -59,7 +59,8 @@ enum ll_epilogue {
  * ll_jpeg_decode_pixels, ll_jpeg_decode_u8, ll_resize_u8), and so do the split entropy route's (ll_jpeg_decode_split_sizes,
  * ll_jpeg_decode_coefficients_split, ll_jpeg_decode_u8_split), and so do the planar YUV entry points (ll_frames_u8_to_yuv420,
  * ll_cl_to_yuv420, ll_yuv_to_frames_u8), and so do the lossless frames-out entry points (ll_png_sizes, ll_png_encode_u8,
- * ll_png_filter_u8, ll_zlib_sizes, ll_zlib_compress_u8): 111 covers them too. */
+ * ll_png_filter_u8, ll_zlib_sizes, ll_zlib_compress_u8): 111 covers them too.  The animated-preview (GIF) entry points are declared
+ * in longlive_gif.h, not here, and are exported by the same library under ABI 111. */
 #define LL_ABI_VERSION 111
 int ll_version(void);
 const char* ll_last_error(void);

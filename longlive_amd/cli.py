@@ -26,6 +26,10 @@ without the two keys intake is as before ("Clip intake on 
 `video_codec: png` writes the exact frames as `<name>.frames/00000.png ...`, `video_codec: apng` as one animated `<name>.png` at
 16 frames/s, both encoded on the GPU (ops.png_encode; DESIGN.md section 5c, "Lossless frames: PNG"); `input_video: clip.png` (a
 still or an APNG, through PIL) continues from exactly those frames.
+`gif_preview: true` writes an animated `<name>.gif` beside the video, whatever `video_codec` is: 256 colours per clip
+(`gif_palette: clip | frame`), ordered dither (`gif_dither: bayer | none`), every `gif_every`-th frame, resized to `gif_size: [H, W]`,
+quantised and LZW-coded on the GPU (longlive_amd.gif; DESIGN.md section 5c, "Animated previews: GIF").  It is a preview, not a codec:
+`video_codec: gif` stays refused.  `input_video: clip.gif` is read through PIL.
 """
 from __future__ import annotations
 
@@ -522,6 +526,59 @@ def _write_apng(path: str, frames: torch.Tensor):
     return path, len(files), {"codec": "apng", "bytes": write_apng(path, files, fps=16)}
 
 
+class GifPreview(NamedTuple):
+    """The yaml's `gif_*` keys, checked: keep every `every`-th frame, resize to `size` = (H, W) (None: the video's), `palette` clip |
+    frame, `dither` bayer | none (gif.encode's)."""
+    every: int
+    size: Optional[tuple]
+    palette: str
+    dither: str
+
+
+def gif_preview(config) -> Optional[GifPreview]:
+    """The yaml's `gif_preview: true` and the keys that shape it (`gif_every`, `gif_size: [H, W]`, `gif_palette`, `gif_dither`): an
+    animated `<name>.gif` beside whatever `video_codec` writes.  None without `gif_preview`; the other keys are checked either way."""
+    from . import gif
+    on = config.get("gif_preview")
+    if on is not None and not isinstance(on, bool):
+        raise ValueError(f"gif_preview: {on!r} must be true or false")
+    every = config.get("gif_every")
+    if every is not None and (isinstance(every, bool) or not isinstance(every, int) or every < 1):
+        raise ValueError(f"gif_every: {every!r} must be an integer >= 1")
+    size = config.get("gif_size")
+    if size is not None:
+        ok = isinstance(size, (list, tuple)) and len(size) == 2 and all(
+            isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= 65535 for v in size)
+        if not ok:
+            raise ValueError(f"gif_size: {size!r} must be [H, W], two integers 1..65535")
+        size = (int(size[0]), int(size[1]))
+    palette = _one_of("gif_palette", config.get("gif_palette"), gif.PALETTES, "clip")
+    dither = _one_of("gif_dither", config.get("gif_dither"), gif.DITHERS, "bayer")
+    return GifPreview(1 if every is None else every, size, palette, dither) if on else None
+
+
+def _preview_frames(frames: torch.Tensor, codec: Optional[str], width: int, height: int, out_range: str, device) -> torch.Tensor:
+    """One sample's frames in the form `video_codec` asked the pipeline for -> uint8 [T', H, W, 3] on the device."""
+    from . import ops
+    if codec != "y4m":
+        return frames.to(device)                                    # absent key: the host's uint8 frames go up again
+    y, c = height * width, (height // 2) * (width // 2)             # I420 payloads [T', bytes]
+    return ops.yuv_to_frames_u8(frames[:, :y].unflatten(1, (height, width)), frames[:, y:y + c].unflatten(1, (height // 2, width // 2)),
+                                frames[:, y + c:].unflatten(1, (height // 2, width // 2)), layout="420jpeg", range=out_range)
+
+
+def _write_gif_preview(path: str, frames: torch.Tensor, preview: GifPreview) -> Dict:
+    """`<name>.gif` beside the video: every `every`-th frame, resized when asked, quantised and coded on the GPU (gif.encode), joined on
+    the host (gif.write_gif).  Returns the record's keys."""
+    from . import gif, ops
+    kept = frames[::preview.every]
+    if preview.size is not None and preview.size != tuple(kept.shape[1:3]):
+        kept = ops.resize_u8(kept, preview.size, fit="stretch")
+    path = os.path.splitext(path)[0] + ".gif"
+    size = gif.write_gif(path, gif.files(*gif.encode(kept, preview.palette, preview.dither)), every=preview.every, fps=16)
+    return {"gif": path, "gif_bytes": size}
+
+
 def input_frames(cap) -> Optional[int]:
     """The yaml's `input_frames:` key: at most so many frames of the clip are used (absent = all of them)."""
     if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
@@ -541,13 +598,16 @@ def select_clip_frames(total: int, cap: Optional[int] = None) -> slice:
 
 def read_input_video(path: str) -> torch.Tensor:
     """uint8 [T, H, W, 3] RGB frames of `path`: an .avi as write_avi_rgb24 or write_avi_mjpeg writes it (chosen by the `strf` chunk's
-    biCompression), a .png (a still or an APNG, through PIL), a .pt holding such a tensor, anything else through
+    biCompression), a .png (a still or an APNG, through PIL), a .gif (through PIL), a .pt holding such a tensor, anything else through
     torchvision.io.read_video when torchvision + PyAV exist."""
     ext = os.path.splitext(path)[1].lower()
     if ext == ".avi":
         frames = read_avi_mjpeg(path) if avi_compression(path) == b"MJPG" else read_avi_rgb24(path)
     elif ext == ".png":
         frames = read_png_frames(path)
+    elif ext == ".gif":
+        from .gif import read_gif_frames
+        frames = read_gif_frames(path)
     elif ext == ".pt":
         frames = torch.load(path, map_location="cpu", weights_only=True)      # a bare tensor: nothing is unpickled
     else:
@@ -790,7 +850,8 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     """The body of inference.py (mode 'inference') / interactive_inference.py (mode 'interactive').  Returns one record per
     written video: {"path", "idx", "frames", "seconds"}, "input_frames" when the yaml's `input_video` gave a clip to continue,
     "input_size" ([W, H] of the clip) when `input_fit` resized it, "input_rate" ([num, den] of a .y4m clip's header) when
-    `input_rate: match` selected by it, "codec" and "bytes" when `video_codec` chose one, and "range" for `video_codec: y4m`."""
+    `input_rate: match` selected by it, "codec" and "bytes" when `video_codec` chose one, "range" for `video_codec: y4m`, and "gif"
+    (the path) and "gif_bytes" under `gif_preview: true`."""
     from .pipeline import CausalInferencePipeline, InteractiveCausalInferencePipeline
     local_rank, rank, world = _dist_env()
     if device is None:
@@ -804,6 +865,7 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
     out_range = yuv_range(config.get("yuv_range"))
     input_range(config.get("input_range")), input_rate(config.get("input_rate"))
     input_decode(config.get("input_decode")), input_fit(config.get("input_fit")), input_split(config.get("input_split"))
+    preview = gif_preview(config)
     clip = input_clip(config, shape.lat_h, shape.lat_w, device)    # read (decoded, resized) and checked before any model is built
     write = {None: _write_default, "mjpeg": functools.partial(_write_mjpeg, quality=quality),
              "y4m": functools.partial(_write_y4m, width=8 * shape.lat_w, height=8 * shape.lat_h, out_range=out_range),
@@ -863,6 +925,9 @@ def run(mode: str, config, synthetic: bool = False, device: Optional[torch.devic
         for seed_idx in range(config.num_samples):
             name = output_name(rank, idx, seed_idx, model_type, config.save_with_index, first_prompt, interactive)
             path, count, coded = write(os.path.join(config.output_folder, name), video[seed_idx])
+            if preview is not None:
+                rgb = _preview_frames(video[seed_idx], codec, 8 * shape.lat_w, 8 * shape.lat_h, out_range, device)
+                coded = {**coded, **_write_gif_preview(os.path.join(config.output_folder, name), rgb, preview)}
             records.append({"path": path, "idx": idx, "frames": count, "seconds": dt, **coded, **extra})
         if config.inference_iter != -1 and i >= config.inference_iter:
             break
